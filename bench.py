@@ -2,6 +2,7 @@
 """Headline benchmark: rays/sec at 800x800, DepthNet + 64 samples/ray (BASELINE.json configs[1]); PSNR vs reference.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N rank processes, one per GPU)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed frame: DIR/rgb.npy, DIR/disp.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one full 800x800 frame of the reference's spiral render path (pose k of 40): ray generation,
@@ -59,7 +60,13 @@ def parse_args(argv=None):
                     "the one-kernel renderer (ns_render_rays_fused): same bits, for A/B timing")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank path on a one-GPU box, all ranks sharing cuda:0)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step as DIR/rgb.npy [H,W,3] and "
+                         "DIR/disp.npy [H,W] (float32); above 64 MB, the same fixed seeded sample of pixels of both")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _launch_ranks(n: int, port: int):
@@ -210,6 +217,30 @@ def host_cores() -> int:
     except (OSError, ValueError):
         pass
     return min(n, 32)  # one GPU's share of the host; more threads than that only oversubscribes
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, rgb, disp, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the frame a caller of the timed path receives, rgb [H,W,3] and disp [H,W], as float32 .npy files.
+    A frame larger than ``max_bytes`` in all is cut to the same fixed sample of pixels (seed 0, row-major order) in both
+    files, rgb [n,3] and disp [n], so two builds run with the same arguments compare pixel for pixel."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    disp = np.ascontiguousarray(disp, dtype=np.float32)
+    n_pix = disp.size
+    per_pixel = rgb.itemsize * 3 + disp.itemsize
+    header = 2 * 128                                  # an .npy header is 128 bytes for these shapes
+    if n_pix * per_pixel + header > max_bytes:
+        n = (max_bytes - header) // per_pixel
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, n, replace=False))
+        rgb, disp = rgb.reshape(-1, 3)[idx], disp.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, a in (("rgb", rgb), ("disp", disp)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return {"dir": out_dir, "files": files, "pixels": int(disp.size), "of_pixels": int(n_pix)}
 
 
 def psnr(a, b):
@@ -651,6 +682,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the last timed frame, before any other leg runs
+        dumped = dump_outputs(args.dump_outputs, rgb.cpu().numpy(), disp.cpu().numpy())
+        dumped["pose"] = (args.warmup + args.steps - 1) % 40
     assert os.environ.get("NS_BENCH_NOCHECK") or torch.isfinite(rgb).all()
 
     # dominant kernel (NeRF MLP), timed with HIP events on its own stream inside the timed region
@@ -702,6 +737,8 @@ def main():
                        "parallelism": f"rows sharded over {world} GPU(s), one all-gather per frame"},
             "roofline": roofline,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline and args.mode == "depthnet":
             mid = H // 2
             rows = (max(0, mid - args.cpu_rows // 2), min(H, mid - args.cpu_rows // 2 + args.cpu_rows))

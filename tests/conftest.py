@@ -1,14 +1,20 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# The golden vectors hold the reference's fp32 outputs to the last bit, and the oracle is checked against them at (near)
+# zero tolerance.  MKL picks its sgemm kernels by CPU (another vendor or vector width sums in another order), so its
+# code branch is pinned here, before torch first calls it: the one tools/make_golden.py captures with.
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+GOLDEN_THREADS = 8          # torch.set_num_threads of tools/make_golden.py
 
 
 def pytest_configure(config):
@@ -17,7 +23,11 @@ def pytest_configure(config):
 
 @pytest.fixture(autouse=True)
 def _reset_process_wide_switches():
-    """The compute dtype and the PSNR guard are process-wide settings (the CLIs set them): no test inherits another's."""
+    """The compute dtype and the PSNR guard are process-wide settings (the CLIs set them): no test inherits another's.
+    Nor the CPU thread count: it starts at the golden capture's (MKL's results on a many-core host depend on it)."""
+    import torch
+
+    torch.set_num_threads(GOLDEN_THREADS)
     yield
     if "nerf_sampling_amd.ops" in sys.modules:
         ops = sys.modules["nerf_sampling_amd.ops"]

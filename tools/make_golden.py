@@ -15,9 +15,14 @@ import io
 import os
 import sys
 import types
+import zipfile
 
 import numpy as np
-import torch
+
+# MKL's code branch pinned to the one tests/conftest.py pins: the same sgemm summation order on every x86 host
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,8 +40,12 @@ def npy(x):
 
 
 def save(name, **arrays):
+    """The .npz layout np.load reads, with LZMA members: a fifth smaller than np.savez_compressed on float vectors."""
     path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **{k: npy(v) for k, v in arrays.items()})
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            with z.open(k + ".npy", "w") as f:
+                np.lib.format.write_array(f, npy(v), allow_pickle=False)
     print(f"  {name}.npz  {os.path.getsize(path) / 1024:.1f} KB  keys={sorted(arrays)}")
 
 
@@ -115,12 +124,20 @@ def main():
     t1, p1 = ref.utils.find_intersection_points_with_sphere(known_o, known_d, torch.tensor([1.0]))
     o = torch.randn(256, 3, generator=g) * 2.5
     d = torch.randn(256, 3, generator=g)
-    t2, p2 = ref.utils.find_intersection_points_with_sphere(o, d, torch.tensor([2.0]))
+    # the square roots torch.sqrt returns here (MKL vector math) differ in the last bit between CPU vendors whatever
+    # MKL_CBWR says: record them with their arguments, tests/test_oracle_golden.py replays them
+    sqrt, calls = torch.sqrt, []
+    torch.sqrt = lambda x: calls.append((x.clone(), sqrt(x))) or calls[-1][1]
+    try:
+        t2, p2 = ref.utils.find_intersection_points_with_sphere(o, d, torch.tensor([2.0]))
+    finally:
+        torch.sqrt = sqrt
+    (sqrt_in, sqrt_out), = calls
     qa = torch.tensor([1., 4, 5, 1, 4, 5]); qb = torch.tensor([1., 4, 6, 1, 4, 6])
     qc = torch.ones(6)
     qs = ref.utils.solve_quadratic_equation(qa, qb, qc)
     save("sphere", known_o=known_o, known_d=known_d, known_t=t1, known_p=p1, o=o, d=d, t=t2,
-         p=p2, qa=qa, qb=qb, qc=qc, qs=qs)
+         p=p2, sqrt_in=sqrt_in, sqrt_out=sqrt_out, qa=qa, qb=qb, qc=qc, qs=qs)
 
     # ---- a3 posenc ----------------------------------------------------------------
     print("a3 posenc")
@@ -257,8 +274,14 @@ def main():
                     ray_batch=rb, network_fn=kw["network_fn"], network_fine=kw["network_fine"],
                     network_query_fn=kw["network_query_fn"], N_samples=64, trainer=tr, perturb=0.0,
                     raw_noise_std=0.0, lindisp=lindisp, white_bkgd=True, kwargs={}, pytest=False)
+                # not stored: density is raw[..., 3] and pts is o + d z, to the bit (the tests derive them)
+                density, z, pts, raw = res[0], res[1], res[2], res[7]
+                assert torch.equal(density, raw[..., 3])
+                assert torch.equal(pts, rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None])
                 for nm, v in zip(names8, res):
-                    if nm in ("pts", "raw", "density", "alphas") and n == "lego_synth":
+                    if nm in ("density", "pts"):
+                        continue
+                    if nm in ("raw", "alphas") and n == "lego_synth":
                         v = v[:8]
                     out[f"{n}_lin{int(lindisp)}_{nm}"] = v
         # stratified jitter + random inverse-CDF draws under a known seed (perturb=1)
