@@ -14,48 +14,122 @@ namespace {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~static_cast<int64_t>(255); }
 
-struct Layout {
-  int64_t o, d, view, mean, z_last, raw_last, z, raw, total;
+// Hands out 256-byte-aligned slices of a workspace in order and keeps the running total.  Each renderer's layout below is
+// written once: its *_workspace_bytes function runs it on a null base and returns the total, the renderer runs it on the
+// caller's workspace.
+struct Carve {
+  char* base = nullptr;
+  int64_t total = 0;
+  float* take(int64_t bytes) {
+    float* p = base ? reinterpret_cast<float*>(base + total) : nullptr;
+    total += align256(bytes);
+    return p;
+  }
 };
 
-Layout layout(int64_t R, int N) {
-  Layout l{};
-  int64_t off = 0;
-  l.o = off; off += align256(R * 3 * 4);
-  l.d = off; off += align256(R * 3 * 4);
-  l.view = off; off += align256(R * 3 * 4);
-  l.mean = off; off += align256(R * 4);
-  l.z_last = off; off += align256(R * 4);          // the guard pass (ns_render_args::nerf_guard): depth and raw of every
-  l.raw_last = off; off += align256(R * 16);       // ray's last sample
-  l.z = off; off += align256(R * N * 4);
-  l.raw = off; off += align256(R * N * 16);
-  l.total = off;
+struct RaySlices { float *o, *d, *view; };
+RaySlices take_rays(Carve& ws, int64_t R) { return {ws.take(R * 12), ws.take(R * 12), ws.take(R * 12)}; }
+
+struct ChainLayout { RaySlices rays; float *mean, *z_last, *raw_last, *z, *raw; };
+ChainLayout chain_layout(Carve& ws, int64_t R, int N) {
+  ChainLayout l;
+  l.rays = take_rays(ws, R);
+  l.mean = ws.take(R * 4);
+  l.z_last = ws.take(R * 4);          // the guard pass (ns_render_args::nerf_guard): depth and raw of every ray's last sample
+  l.raw_last = ws.take(R * 16);
+  l.z = ws.take(R * N * 4); l.raw = ws.take(R * N * 16);
   return l;
 }
 
+struct FusedLayout { RaySlices rays; float *mean, *z_last, *raw_last; uint32_t* fix_count; float* fix_rec; RaySlices fix_rays; };
+FusedLayout fused_layout(Carve& ws, int64_t R) {
+  FusedLayout l;
+  l.rays = take_rays(ws, R);
+  l.mean = ws.take(R * 4);
+  l.z_last = ws.take(R * 4);          // the every-ray guard's depth and raw of the last sample; the selective guard's z and raw
+  l.raw_last = ws.take(R * 16);       // of the flagged rays' last samples
+  l.fix_count = reinterpret_cast<uint32_t*>(ws.take(256));   // the selective guard: counter, 64-byte records, compacted rays
+  l.fix_rec = ws.take(R * 64);
+  l.fix_rays = take_rays(ws, R);
+  return l;
+}
+
+struct HierLayout { RaySlices rays; float *z_c, *raw_c, *w_c, *z_f, *raw_f; };
+HierLayout hier_layout(Carve& ws, int64_t R, int Nc, int Nt) {
+  HierLayout l;
+  l.rays = take_rays(ws, R);
+  l.z_c = ws.take(R * Nc * 4); l.raw_c = ws.take(R * Nc * 16); l.w_c = ws.take(R * Nc * 4);
+  l.z_f = ws.take(R * Nt * 4); l.raw_f = ws.take(R * Nt * 16);
+  return l;
+}
+
+struct Rays { int64_t R = 0; const float *o = nullptr, *d = nullptr, *view = nullptr; };   // R = 0: nothing to render
+
+// The ray source of the three renderers: explicit rays (o_dev != NULL, R of them) or rows [row0, row1) of the camera image,
+// generated into the o / d / viewdirs slices of the renderer's layout.  carve_layout(ws, R) lays the workspace out for R rays
+// and returns those slices.
+template <class Args, class CarveLayout>
+int resolve_rays(const Args* a, CarveLayout carve_layout, Rays* r, void* stream) {
+  *r = Rays{};
+  if (a->o_dev == nullptr ? (a->row1 == a->row0 || a->W == 0) : a->R == 0) return NS_OK;  // nothing to render
+  NS_REQUIRE(a->workspace_dev && a->rgb_dev && a->disp_dev, "workspace, rgb and disp are required");
+  NS_REQUIRE(a->o_dev || (a->row0 >= 0 && a->row1 <= a->H && a->row0 <= a->row1 && a->W > 0), "bad camera rows");
+  NS_REQUIRE(!a->o_dev || (a->d_dev && a->viewdirs_dev), "explicit rays need o, d and viewdirs");
+  NS_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace_dev) & 255) == 0, "workspace must be 256-byte aligned");
+  const int64_t R = a->o_dev ? a->R : static_cast<int64_t>(a->row1 - a->row0) * a->W;
+  Carve ws{static_cast<char*>(a->workspace_dev)};
+  const RaySlices s = carve_layout(ws, R);
+  if (a->o_dev) { *r = Rays{R, a->o_dev, a->d_dev, a->viewdirs_dev}; return NS_OK; }
+  const int rc = ns_get_rays(a->H, a->W, a->fx, a->fy, a->cx, a->cy, a->c2w, a->row0, a->row1, a->near_, a->far_, s.o, s.d,
+                             s.view, nullptr, stream);
+  if (rc == NS_OK) *r = Rays{R, s.o, s.d, s.view};
+  return rc;
+}
+
+// The caller's per-ray outputs, strides resolved (0 = packed: 3 / 1).
+struct Outputs { float* rgb; int64_t rgb_stride; float* disp; int64_t disp_stride; float* weights; };
+template <class Args>
+Outputs outputs(const Args* a) {
+  return {a->rgb_dev, a->rgb_stride ? a->rgb_stride : 3, a->disp_dev, a->disp_stride ? a->disp_stride : 1, a->weights_dev};
+}
+
+// raw [R,N,4] composited into the caller's rgb / disp (/ weights)
+int composite(const Outputs& out, const float* raw, const float* z, const float* d, int64_t R, int N, int white_bkgd,
+              void* stream) {
+  return ns_raw2outputs_strided(raw, z, d, nullptr, R, N, white_bkgd, out.rgb, out.rgb_stride, out.disp, out.disp_stride,
+                                nullptr, nullptr, nullptr, out.weights, stream);
+}
+
+// an optional event (NULL = none) recorded on the stream
+int record(void* ev, void* stream) { return ev ? ns_event_record(ev, stream) : NS_OK; }
+
+// ns::prod_tiles_hint() for the MLP launch in its scope (see ns_common.h): 4 when the call has per-sample outputs, whose host
+// copies will run beside the next MLP kernel; reset on the way out
+struct ProdTilesHint {
+  explicit ProdTilesHint(const ns_render_args* a) { ns::prod_tiles_hint() = (a->z_dev || a->weights_dev || a->pts_dev) ? 4 : 0; }
+  ~ProdTilesHint() { ns::prod_tiles_hint() = 0; }
+};
+
 // The guard pass: the last sample of every ray through a second, fp32-grade (F16X3) handle of the same network; its raw
 // lands in raw_last [R,4].  (nerf_utils.py:836-865 composites that sample with dist = 1e10, sampling_trainer.py:176-180.)
-int guard_check(const ns_render_args* a, int N) {
+// guard_check runs before a renderer launches anything.
+int guard_check(const ns_render_args* a) {
   const ns_weights* gnet = a->nerf_guard;
   if (!(gnet->kind == NS_KIND_NERF && gnet->out_ch == 4 && gnet->use_viewdirs && gnet->width == a->nerf->width &&
         gnet->depth == a->nerf->depth && gnet->skip_mask == a->nerf->skip_mask)) {
     ns::set_error("nerf_guard must be another packing of the same network (a NeRF with view directions, same D / W / skips)");
     return NS_E_INVALID;
   }
-  if (a->mode != NS_MODE_UNIFORM || N < 2) {
+  if (a->mode != NS_MODE_UNIFORM || a->N < 2) {
     ns::set_error("nerf_guard: the guard pass is defined for uniform placement with n_samples >= 2");
     return NS_E_UNSUPPORTED;
   }
   return NS_OK;
 }
-int guard_pass(const ns_render_args* a, const float* o, const float* d, const float* view, const float* mean, int64_t R,
-               int N, float* z_last, float* raw_last, void* stream) {
-  const ns_weights* gnet = a->nerf_guard;
-  int rc = guard_check(a, N);
+int guard_pass(const ns_render_args* a, const Rays& r, const float* mean, float* z_last, float* raw_last, void* stream) {
+  const int rc = ns_place_last_sample(mean, r.R, a->N, a->std_, z_last, stream);
   if (rc != NS_OK) return rc;
-  rc = ns_place_last_sample(mean, R, N, a->std_, z_last, stream);
-  if (rc != NS_OK) return rc;
-  return ns_nerf_forward(gnet, nullptr, o, d, z_last, view, R, 1, raw_last, stream);
+  return ns_nerf_forward(a->nerf_guard, nullptr, r.o, r.d, z_last, r.view, r.R, 1, raw_last, stream);
 }
 
 }  // namespace
@@ -64,7 +138,9 @@ extern "C" {
 
 int64_t ns_render_workspace_bytes(int64_t R, int N) {
   if (R < 0 || N < 1) return 0;
-  return layout(R, N).total;
+  Carve ws;
+  chain_layout(ws, R, N);
+  return ws.total;
 }
 
 int ns_render_rays_depthnet(const ns_render_args* a, void* stream) {
@@ -72,58 +148,33 @@ int ns_render_rays_depthnet(const ns_render_args* a, void* stream) {
   NS_REQUIRE(a->depthnet && a->nerf, "both networks are required");
   NS_REQUIRE(a->nerf->kind == NS_KIND_NERF && a->nerf->out_ch == 4 && a->nerf->use_viewdirs,
              "the one-call path composites raw [R,N,4] of a network with view directions");
-  if (a->o_dev == nullptr ? (a->row1 == a->row0 || a->W == 0) : a->R == 0) return NS_OK;  // nothing to render
-  if (a->o_dev == nullptr && a->H == 0 && a->R == 0) return NS_OK;
-  NS_REQUIRE(a->workspace_dev && a->rgb_dev && a->disp_dev, "workspace, rgb and disp are required");
-  int N = a->mode == NS_MODE_DEPTH_ONLY ? 1 : a->N;
+  const int N = a->mode == NS_MODE_DEPTH_ONLY ? 1 : a->N;
   NS_REQUIRE(N >= 1, "bad sample count");
-  int64_t R = a->R;
-  if (!a->o_dev) {
-    NS_REQUIRE(a->row0 >= 0 && a->row1 <= a->H && a->row0 <= a->row1 && a->W > 0, "bad camera rows");
-    R = static_cast<int64_t>(a->row1 - a->row0) * a->W;
-  } else {
-    NS_REQUIRE(a->d_dev && a->viewdirs_dev, "explicit rays need o, d and viewdirs");
+  int rc = a->nerf_guard ? guard_check(a) : NS_OK;
+  if (rc != NS_OK) return rc;
+  ChainLayout l;
+  Rays r;
+  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = chain_layout(ws, R, N); return l.rays; }, &r, stream);
+  if (rc != NS_OK || r.R == 0) return rc;
+  float* z = a->z_dev ? a->z_dev : l.z;
+  rc = ns_depthnet_forward(a->depthnet, r.o, r.d, r.R, a->near_, a->far_, a->sphere_radius, l.mean, stream);
+  if (rc != NS_OK) return rc;
+  rc = ns_place_samples(a->mode, r.o, r.d, l.mean, a->noise_dev, r.R, N, a->std_, a->pts_dev, z, stream);
+  if (rc != NS_OK) return rc;
+  if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
+  {
+    ProdTilesHint hint(a);
+    rc = ns_nerf_forward(a->nerf, nullptr, r.o, r.d, z, r.view, r.R, N, l.raw, stream);
   }
-  if (R == 0) return NS_OK;
-  const Layout l = layout(R, N);
-  char* ws = static_cast<char*>(a->workspace_dev);
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-  const float* o = a->o_dev;
-  const float* d = a->d_dev;
-  const float* view = a->viewdirs_dev;
-  int rc;
-  if (!o) {
-    float* wo = reinterpret_cast<float*>(ws + l.o);
-    float* wd = reinterpret_cast<float*>(ws + l.d);
-    float* wv = reinterpret_cast<float*>(ws + l.view);
-    rc = ns_get_rays(a->H, a->W, a->fx, a->fy, a->cx, a->cy, a->c2w, a->row0, a->row1, a->near_, a->far_, wo, wd,
-                     wv, nullptr, stream);
-    if (rc != NS_OK) return rc;
-    o = wo; d = wd; view = wv;
-  }
-  float* mean = reinterpret_cast<float*>(ws + l.mean);
-  float* z = a->z_dev ? a->z_dev : reinterpret_cast<float*>(ws + l.z);
-  float* raw = reinterpret_cast<float*>(ws + l.raw);
-  rc = ns_depthnet_forward(a->depthnet, o, d, R, a->near_, a->far_, a->sphere_radius, mean, stream);
   if (rc != NS_OK) return rc;
-  rc = ns_place_samples(a->mode, o, d, mean, a->noise_dev, R, N, a->std_, a->pts_dev, z, stream);
-  if (rc != NS_OK) return rc;
-  if (a->ev_mlp_begin) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_begin), ns::as_stream(stream)));
-  ns::prod_tiles_hint() = (a->z_dev || a->weights_dev || a->pts_dev) ? 4 : 0;   // per-sample outputs: host copies will run beside the next MLP kernel
-  rc = ns_nerf_forward(a->nerf, nullptr, o, d, z, view, R, N, raw, stream);
-  ns::prod_tiles_hint() = 0;
-  if (rc != NS_OK) return rc;
-  if (a->ev_mlp_end) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_end), ns::as_stream(stream)));
+  if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
   if (a->nerf_guard) {
-    float* raw_last = reinterpret_cast<float*>(ws + l.raw_last);
-    rc = guard_pass(a, o, d, view, mean, R, N, reinterpret_cast<float*>(ws + l.z_last), raw_last, stream);
+    rc = guard_pass(a, r, l.mean, l.z_last, l.raw_last, stream);
     if (rc != NS_OK) return rc;
-    rc = ns_patch_sigma_last(raw, raw_last, R, N, stream);
+    rc = ns_patch_sigma_last(l.raw, l.raw_last, r.R, N, stream);
     if (rc != NS_OK) return rc;
   }
-  return ns_raw2outputs_strided(raw, z, d, nullptr, R, N, a->white_bkgd, a->rgb_dev, a->rgb_stride ? a->rgb_stride : 3,
-                                a->disp_dev, a->disp_stride ? a->disp_stride : 1, nullptr, nullptr, nullptr,
-                                a->weights_dev, stream);
+  return composite(outputs(a), l.raw, z, r.d, r.R, N, a->white_bkgd, stream);
 }
 
 // ---- the same branch as ONE kernel per ray tile: rays -> DepthNet -> [placement + radiance-field
@@ -134,8 +185,9 @@ int ns_render_fused_supported(const ns_weights* nerf, int mode, int N) {
 
 int64_t ns_render_fused_workspace_bytes(int64_t R) {
   if (R < 0) return 0;
-  // o, d, viewdirs | DepthNet depth | guard: z_last, raw_last | selective guard: counter, records, compact o, d, viewdirs
-  return 3 * align256(R * 12) + 2 * align256(R * 4) + align256(R * 16) + 256 + align256(R * 64) + 3 * align256(R * 12);
+  Carve ws;
+  fused_layout(ws, R);
+  return ws.total;
 }
 
 int ns_render_rays_fused(const ns_render_args* a, void* stream) {
@@ -147,123 +199,75 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
     return NS_E_UNSUPPORTED;
   }
   NS_REQUIRE(!a->noise_dev, "uniform placement takes no noise");
-  if (a->o_dev == nullptr ? (a->row1 == a->row0 || a->W == 0) : a->R == 0) return NS_OK;  // nothing to render
-  NS_REQUIRE(a->workspace_dev && a->rgb_dev && a->disp_dev, "workspace, rgb and disp are required");
-  int64_t R = a->R;
-  if (!a->o_dev) {
-    NS_REQUIRE(a->row0 >= 0 && a->row1 <= a->H && a->row0 <= a->row1 && a->W > 0, "bad camera rows");
-    R = static_cast<int64_t>(a->row1 - a->row0) * a->W;
-  } else {
-    NS_REQUIRE(a->d_dev && a->viewdirs_dev, "explicit rays need o, d and viewdirs");
-  }
-  if (R == 0) return NS_OK;
-  char* ws = static_cast<char*>(a->workspace_dev);
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
-  const float* o = a->o_dev;
-  const float* d = a->d_dev;
-  const float* view = a->viewdirs_dev;
-  int rc;
-  if (!o) {
-    float* wo = reinterpret_cast<float*>(ws);
-    float* wd = reinterpret_cast<float*>(ws + align256(R * 12));
-    float* wv = reinterpret_cast<float*>(ws + 2 * align256(R * 12));
-    rc = ns_get_rays(a->H, a->W, a->fx, a->fy, a->cx, a->cy, a->c2w, a->row0, a->row1, a->near_, a->far_, wo, wd, wv,
-                     nullptr, stream);
-    if (rc != NS_OK) return rc;
-    o = wo; d = wd; view = wv;
-  }
-  float* mean = reinterpret_cast<float*>(ws + 3 * align256(R * 12));
-  rc = ns_depthnet_forward(a->depthnet, o, d, R, a->near_, a->far_, a->sphere_radius, mean, stream);
+  int rc = a->nerf_guard ? guard_check(a) : NS_OK;
   if (rc != NS_OK) return rc;
+  FusedLayout l;
+  Rays r;
+  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = fused_layout(ws, R); return l.rays; }, &r, stream);
+  if (rc != NS_OK || r.R == 0) return rc;
+  rc = ns_depthnet_forward(a->depthnet, r.o, r.d, r.R, a->near_, a->far_, a->sphere_radius, l.mean, stream);
+  if (rc != NS_OK) return rc;
+  const Outputs out = outputs(a);
   ns_composite_args c{};
-  c.mean_dev = mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
-  c.rgb_dev = a->rgb_dev; c.rgb_stride = a->rgb_stride ? a->rgb_stride : 3;
-  c.disp_dev = a->disp_dev; c.disp_stride = a->disp_stride ? a->disp_stride : 1;
-  c.weights_dev = a->weights_dev; c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
-  float* z_last = reinterpret_cast<float*>(ws + 3 * align256(R * 12) + align256(R * 4));
-  float* raw_last = reinterpret_cast<float*>(ws + 3 * align256(R * 12) + 2 * align256(R * 4));
-  char* fix = ws + 3 * align256(R * 12) + 2 * align256(R * 4) + align256(R * 16);
+  c.mean_dev = l.mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
+  c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
+  c.weights_dev = out.weights; c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
   // (the fix-up launches the split-operand MLP kernel with a device-side count: another packing of the guard handle, e.g. fp32,
   // takes the every-ray pass through the generic dispatch)
   const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && a->N <= 64 && a->nerf_guard->dtype == NS_DTYPE_F16X3 &&
                          a->nerf_guard->layout == 16;
   if (selective) {         // the kernel flags the rays itself; their last samples are re-evaluated after it
-    rc = guard_check(a, a->N);
-    if (rc != NS_OK) return rc;
     c.fix_thr = a->guard_threshold;
-    c.fix_count_dev = reinterpret_cast<uint32_t*>(fix);
-    c.fix_rec_dev = reinterpret_cast<float*>(fix + 256);
-    NS_HIP(hipMemsetAsync(fix, 0, 256, ns::as_stream(stream)));
+    c.fix_count_dev = l.fix_count;
+    c.fix_rec_dev = l.fix_rec;
+    NS_HIP(hipMemsetAsync(l.fix_count, 0, 256, ns::as_stream(stream)));
   } else if (a->nerf_guard) {     // (before the event pair: the pair times the fused kernel alone)
-    rc = guard_pass(a, o, d, view, mean, R, a->N, z_last, raw_last, stream);
+    rc = guard_pass(a, r, l.mean, l.z_last, l.raw_last, stream);
     if (rc != NS_OK) return rc;
-    c.sigma_last_dev = raw_last;
+    c.sigma_last_dev = l.raw_last;
   }
-  if (a->ev_mlp_begin) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_begin), ns::as_stream(stream)));
-  ns::prod_tiles_hint() = (a->z_dev || a->weights_dev || a->pts_dev) ? 4 : 0;   // (see ns_common.h)
-  rc = ns_nerf_forward_ob16(a->nerf, nullptr, o, d, nullptr, view, nullptr, R * a->N, a->N, nullptr, ns::as_stream(stream), &c);
-  ns::prod_tiles_hint() = 0;
+  if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
+  {
+    ProdTilesHint hint(a);
+    rc = ns_nerf_forward_ob16(a->nerf, nullptr, r.o, r.d, nullptr, r.view, nullptr, r.R * a->N, a->N, nullptr,
+                              ns::as_stream(stream), &c);
+  }
   if (rc != NS_OK) return rc;
-  if (a->ev_mlp_end) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_end), ns::as_stream(stream)));
-  if (selective) {
-    float* o_c = reinterpret_cast<float*>(fix + 256 + align256(R * 64));
-    float* d_c = reinterpret_cast<float*>(fix + 256 + align256(R * 64) + align256(R * 12));
-    float* v_c = reinterpret_cast<float*>(fix + 256 + align256(R * 64) + 2 * align256(R * 12));
-    rc = ns_fix_gather(c.fix_rec_dev, c.fix_count_dev, R, o, d, view, o_c, d_c, v_c, z_last, stream);
-    if (rc != NS_OK) return rc;
-    rc = ns_nerf_forward_x3(a->nerf_guard, nullptr, o_c, d_c, z_last, v_c, nullptr, R, 1, raw_last, ns::as_stream(stream),
-                            c.fix_count_dev);
-    if (rc != NS_OK) return rc;
-    rc = ns_fix_last_sample(c.fix_rec_dev, c.fix_count_dev, R, raw_last, a->N, a->white_bkgd, c.rgb_dev, c.rgb_stride, c.disp_dev,
-                            c.disp_stride, a->weights_dev, stream);
-    if (rc != NS_OK) return rc;
-  }
-  return NS_OK;
+  if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
+  if (!selective) return NS_OK;
+  const RaySlices& fr = l.fix_rays;
+  rc = ns_fix_gather(l.fix_rec, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view, l.z_last, stream);
+  if (rc != NS_OK) return rc;
+  rc = ns_nerf_forward_x3(a->nerf_guard, nullptr, fr.o, fr.d, l.z_last, fr.view, nullptr, r.R, 1, l.raw_last,
+                          ns::as_stream(stream), l.fix_count);
+  if (rc != NS_OK) return rc;
+  return ns_fix_last_sample(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride, out.disp,
+                            out.disp_stride, out.weights, stream);
 }
 
 int64_t ns_hier_workspace_bytes(int64_t R, int Nc, int Nf) {
   if (R < 0 || Nc < 3 || Nf < 0) return 0;
-  const int64_t Nt = Nc + Nf;
-  // o, d, view | z_c [R,Nc] | raw_c [R,Nc,4] | w_c [R,Nc] | z_f [R,Nt] | raw_f [R,Nt,4]
-  return 3 * align256(R * 12) + align256(R * Nc * 4) + align256(R * Nc * 16) + align256(R * Nc * 4) +
-         align256(R * Nt * 4) + align256(R * Nt * 16);
+  Carve ws;
+  hier_layout(ws, R, Nc, Nc + Nf);
+  return ws.total;
 }
 
 int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   NS_REQUIRE(a && a->coarse, "null args / coarse network");
   NS_REQUIRE(a->coarse->out_ch == 4 && a->coarse->use_viewdirs && (!a->fine || (a->fine->out_ch == 4 && a->fine->use_viewdirs)),
              "the one-call path composites raw [R,N,4] of networks with view directions");
-  if (a->o_dev == nullptr ? (a->row1 == a->row0 || a->W == 0) : a->R == 0) return NS_OK;  // nothing to render
-  NS_REQUIRE(a->workspace_dev && a->rgb_dev && a->disp_dev, "workspace, rgb and disp are required");
   NS_REQUIRE(a->Nc >= 3 && a->Nf >= 0, "needs at least 3 coarse samples");
-  int64_t R = a->R;
-  if (!a->o_dev) {
-    NS_REQUIRE(a->row0 >= 0 && a->row1 <= a->H && a->row0 <= a->row1 && a->W > 0, "bad camera rows");
-    R = static_cast<int64_t>(a->row1 - a->row0) * a->W;
-  } else {
-    NS_REQUIRE(a->d_dev && a->viewdirs_dev, "explicit rays need o, d and viewdirs");
-  }
-  if (R == 0) return NS_OK;
-  char* ws = static_cast<char*>(a->workspace_dev);
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned");
   const int Nc = a->Nc, Nt = a->Nc + a->Nf;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = ws + off; off += align256(bytes); return reinterpret_cast<float*>(p); };
-  float* wo = take(R * 12); float* wd = take(R * 12); float* wv = take(R * 12);
-  float* z_c = take(R * Nc * 4); float* raw_c = take(R * Nc * 16); float* w_c = take(R * Nc * 4);
-  float* z_f_ws = take(R * Nt * 4); float* raw_f_ws = take(R * Nt * 16);
-  const float* o = a->o_dev; const float* d = a->d_dev; const float* view = a->viewdirs_dev;
-  int rc;
-  if (!o) {
-    rc = ns_get_rays(a->H, a->W, a->fx, a->fy, a->cx, a->cy, a->c2w, a->row0, a->row1, a->near_, a->far_, wo, wd, wv,
-                     nullptr, stream);
-    if (rc != NS_OK) return rc;
-    o = wo; d = wd; view = wv;
-  }
+  HierLayout l;
+  Rays r;
+  int rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = hier_layout(ws, R, Nc, Nt); return l.rays; }, &r, stream);
+  if (rc != NS_OK || r.R == 0) return rc;
+  const int64_t R = r.R;
+  const Outputs out = outputs(a);
   // coarse pass (Trainer.py:579-649); its rgb/disp are not part of the 8-tuple and are not produced
-  rc = ns_coarse_z_scalar(a->near_, a->far_, R, Nc, a->lindisp, a->t_rand_dev, z_c, stream);
+  rc = ns_coarse_z_scalar(a->near_, a->far_, R, Nc, a->lindisp, a->t_rand_dev, l.z_c, stream);
   if (rc != NS_OK) return rc;
-  if (a->ev_coarse_begin) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_coarse_begin), ns::as_stream(stream)));
+  if ((rc = record(a->ev_coarse_begin, stream)) != NS_OK) return rc;
   // A 16-bit field composites in its own epilogue (Nerf16Args::comp == 1: depths from the z array): raw [R,N,4] -- 16 bytes
   // per sample written and read back, 2.6 GB per 800 x 800 frame at 64 + 192 samples -- then never exists.  The coarse
   // pass only yields its weights (its colour goes to a scratch corner of the unused raw_c block).
@@ -272,48 +276,40 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   if (fuse_c) {
     ns_composite_args c{};
     c.white_bkgd = a->white_bkgd;
-    c.rgb_dev = raw_c; c.rgb_stride = 4; c.disp_dev = raw_c + 3; c.disp_stride = 4;
-    c.weights_dev = w_c;
-    rc = ns_nerf_forward_ob16(a->coarse, nullptr, o, d, z_c, view, nullptr, R * Nc, Nc, nullptr, ns::as_stream(stream), &c);
+    c.rgb_dev = l.raw_c; c.rgb_stride = 4; c.disp_dev = l.raw_c + 3; c.disp_stride = 4;
+    c.weights_dev = l.w_c;
+    rc = ns_nerf_forward_ob16(a->coarse, nullptr, r.o, r.d, l.z_c, r.view, nullptr, R * Nc, Nc, nullptr, ns::as_stream(stream), &c);
   } else {
-    rc = ns_nerf_forward(a->coarse, nullptr, o, d, z_c, view, R, Nc, raw_c, stream);
+    rc = ns_nerf_forward(a->coarse, nullptr, r.o, r.d, l.z_c, r.view, R, Nc, l.raw_c, stream);
   }
   if (rc != NS_OK) return rc;
-  if (a->ev_coarse_end) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_coarse_end), ns::as_stream(stream)));
+  if ((rc = record(a->ev_coarse_end, stream)) != NS_OK) return rc;
   if (!fuse_c) {
-    rc = ns_raw2outputs(raw_c, z_c, d, nullptr, R, Nc, a->white_bkgd, nullptr, nullptr, nullptr, nullptr, nullptr, w_c,
+    rc = ns_raw2outputs(l.raw_c, l.z_c, r.d, nullptr, R, Nc, a->white_bkgd, nullptr, nullptr, nullptr, nullptr, nullptr, l.w_c,
                         stream);
     if (rc != NS_OK) return rc;
   }
-  if (a->Nf == 0) {  // no importance samples: the coarse pass is the result
-    return ns_raw2outputs_strided(raw_c, z_c, d, nullptr, R, Nc, a->white_bkgd, a->rgb_dev,
-                                  a->rgb_stride ? a->rgb_stride : 3, a->disp_dev, a->disp_stride ? a->disp_stride : 1,
-                                  nullptr, nullptr, nullptr, a->weights_dev, stream);
-  }
+  if (a->Nf == 0) return composite(out, l.raw_c, l.z_c, r.d, R, Nc, a->white_bkgd, stream);   // the coarse pass is the result
   // fine pass (Trainer.py:651-710)
-  float* z_f = a->z_dev ? a->z_dev : z_f_ws;
-  float* raw_f = a->raw_dev ? a->raw_dev : raw_f_ws;
-  rc = ns_importance_z(z_c, w_c, R, Nc, a->Nf, a->u_dev, z_f, stream);
+  float* z_f = a->z_dev ? a->z_dev : l.z_f;
+  float* raw_f = a->raw_dev ? a->raw_dev : l.raw_f;
+  rc = ns_importance_z(l.z_c, l.w_c, R, Nc, a->Nf, a->u_dev, z_f, stream);
   if (rc != NS_OK) return rc;
-  if (a->ev_mlp_begin) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_begin), ns::as_stream(stream)));
+  if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
   const ns_weights* fine = a->fine ? a->fine : a->coarse;
   if (!chain && ns_nerf_can_composite(fine, Nt)) {
     ns_composite_args c{};
     c.white_bkgd = a->white_bkgd;
-    c.rgb_dev = a->rgb_dev; c.rgb_stride = a->rgb_stride ? a->rgb_stride : 3;
-    c.disp_dev = a->disp_dev; c.disp_stride = a->disp_stride ? a->disp_stride : 1;
-    c.weights_dev = a->weights_dev;
-    rc = ns_nerf_forward_ob16(fine, nullptr, o, d, z_f, view, nullptr, R * Nt, Nt, a->raw_dev, ns::as_stream(stream), &c);
+    c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
+    c.weights_dev = out.weights;
+    rc = ns_nerf_forward_ob16(fine, nullptr, r.o, r.d, z_f, r.view, nullptr, R * Nt, Nt, a->raw_dev, ns::as_stream(stream), &c);
     if (rc != NS_OK) return rc;
-    if (a->ev_mlp_end) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_end), ns::as_stream(stream)));
-    return NS_OK;
+    return record(a->ev_mlp_end, stream);
   }
-  rc = ns_nerf_forward(fine, nullptr, o, d, z_f, view, R, Nt, raw_f, stream);
+  rc = ns_nerf_forward(fine, nullptr, r.o, r.d, z_f, r.view, R, Nt, raw_f, stream);
   if (rc != NS_OK) return rc;
-  if (a->ev_mlp_end) NS_HIP(hipEventRecord(static_cast<hipEvent_t>(a->ev_mlp_end), ns::as_stream(stream)));
-  return ns_raw2outputs_strided(raw_f, z_f, d, nullptr, R, Nt, a->white_bkgd, a->rgb_dev,
-                                a->rgb_stride ? a->rgb_stride : 3, a->disp_dev, a->disp_stride ? a->disp_stride : 1,
-                                nullptr, nullptr, nullptr, a->weights_dev, stream);
+  if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
+  return composite(out, raw_f, z_f, r.d, R, Nt, a->white_bkgd, stream);
 }
 
 int ns_event_create(void** ev) {

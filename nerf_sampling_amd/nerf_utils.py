@@ -510,9 +510,7 @@ def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer
         net = network_fine if network_fine is not None else network_fn
         ev = sink.new_event_pair() if sink is not None else None
         held = _held_sink
-        dn_w, net_w, guard_w = ops.psnr_guard_handles(dn, net)
-        if trainer.sampling_mode != "uniform" or trainer.n_depth_samples < 2:
-            guard_w = None               # (the guard pass is defined for uniform placement)
+        dn_w, net_w, guard_w = ops.psnr_guard_handles(dn, net, mode=trainer.sampling_mode, n_samples=trainer.n_depth_samples)
         out = ops.render_rays_depthnet(dn_w, net_w, rays=(rays_o, rays_d, viewdirs),
                                        n_samples=trainer.n_depth_samples, mode=trainer.sampling_mode, std=trainer.distance,
                                        near=dn.near, far=dn.far, sphere_radius=float(dn.sphere_radius.reshape(-1)[0]),

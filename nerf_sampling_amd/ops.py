@@ -98,11 +98,14 @@ def psnr_guard() -> bool:
     return _psnr_guard
 
 
-def psnr_guard_handles(depth_net, nerf):
+def psnr_guard_handles(depth_net, nerf, mode: Optional[str] = None, n_samples: Optional[int] = None):
     """(DepthNet handle, field handle, guard handle or None) for the current compute dtype and guard setting: what the
-    one-call renderers take.  ``depth_net`` / ``nerf``: this package's DepthNet / NeRF modules."""
+    one-call renderers take.  ``depth_net`` / ``nerf``: this package's DepthNet / NeRF modules.  Given the sampling ``mode``
+    / ``n_samples`` of the render, the guard is None where it does not apply: the guard pass is defined for uniform placement
+    with n_samples >= 2."""
     dn, nf = depth_net.packed(), nerf.packed()
-    guard = nerf.packed("f16x3") if (_psnr_guard and nf.dtype in ("bf16", "f16")) else None
+    applies = mode in (None, "uniform") and (n_samples is None or n_samples >= 2)
+    guard = nerf.packed("f16x3") if (_psnr_guard and applies and nf.dtype in ("bf16", "f16")) else None
     return dn, nf, guard
 
 
@@ -124,6 +127,12 @@ def _stream(dev) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _c2w_host(c2w) -> np.ndarray:
+    """camera-to-world matrix (tensor or array) -> contiguous host float32 [3,4]"""
+    c2w = c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)
+    return np.ascontiguousarray(c2w.astype(np.float32)[:3, :4])
+
+
 # ---- a1 -------------------------------------------------------------------------------------------
 def get_rays(H: int, W: int, K, c2w, row0: int = 0, row1: Optional[int] = None, near: float = 0.0,
              far: float = 1.0, device=None, want_batch: bool = False):
@@ -131,8 +140,7 @@ def get_rays(H: int, W: int, K, c2w, row0: int = 0, row1: Optional[int] = None, 
     lib = _lib.load()
     row1 = H if row1 is None else row1
     device = torch.device(device if device is not None else (c2w.device if isinstance(c2w, Tensor) and c2w.is_cuda else "cuda"))
-    c2w_h = (c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)).astype(np.float32)[:3, :4]
-    c2w_h = np.ascontiguousarray(c2w_h)
+    c2w_h = _c2w_host(c2w)
     R = (row1 - row0) * W
     o = torch.empty((R, 3), dtype=torch.float32, device=device)
     d = torch.empty_like(o)
@@ -441,6 +449,26 @@ class RenderWorkspace:
 _default_ws = RenderWorkspace()
 
 
+def _set_workspace(a, workspace: Optional[RenderWorkspace], nbytes: int, device) -> None:
+    """a.workspace_dev = the 256-byte-aligned base of ``nbytes`` bytes of ``workspace`` (None: the module's own)."""
+    a.workspace_dev = ((workspace or _default_ws).get(nbytes, device).data_ptr() + 255) & ~255
+
+
+def _set_ray_source(a, rays, camera, device):
+    """The ray-source fields of a RenderArgs / HierArgs from rays = (o, d, viewdirs) device tensors or camera = (H, W, K,
+    c2w, row0, row1) -> (R, device, tensors to keep alive until the call)."""
+    if rays is not None:
+        o, d, v = (_dev(t, n) for t, n in zip(rays, ("rays_o", "rays_d", "viewdirs")))
+        a.o_dev, a.d_dev, a.viewdirs_dev, a.R = o.data_ptr(), d.data_ptr(), v.data_ptr(), o.shape[0]
+        return o.shape[0], o.device, [o, d, v]
+    H, W, K, c2w, row0, row1 = camera
+    a.H, a.W, a.row0, a.row1 = H, W, row0, row1
+    a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    a.c2w[:] = _c2w_host(c2w).reshape(-1).tolist()
+    a.R = (row1 - row0) * W
+    return a.R, torch.device(device), []
+
+
 def _rgb_disp_outputs(a, R: int, device, shard: Optional[Tensor]):
     """Per-ray outputs of the one-call renderers: fresh packed tensors, or views of an interleaved [.., 4] shard."""
     if shard is None:
@@ -484,7 +512,6 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     lib = _lib.load()
     a = _lib.RenderArgs()
     a.depthnet, a.nerf = depthnet.handle, nerf.handle
-    keep = []
     if rays is not None and rays[0].shape[0] == 0:     # empty batch: nothing to launch
         dev0, n0 = rays[0].device, (1 if mode == "depth_only" else int(n_samples))
         out = {"rgb": torch.empty((0, 3), device=dev0), "disp": torch.empty((0,), device=dev0)}
@@ -492,22 +519,7 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
             out.update(z=torch.empty((0, n0), device=dev0), weights=torch.empty((0, 0 if n0 == 1 else n0), device=dev0),
                        pts=torch.empty((0, n0, 3), device=dev0))
         return out
-    if rays is not None:
-        o, d, v = (_dev(t, n) for t, n in zip(rays, ("rays_o", "rays_d", "viewdirs")))
-        keep += [o, d, v]
-        device = o.device
-        R = o.shape[0]
-        a.o_dev, a.d_dev, a.viewdirs_dev, a.R = o.data_ptr(), d.data_ptr(), v.data_ptr(), R
-    else:
-        H, W, K, c2w, row0, row1 = camera
-        c2w_h = (c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)).astype(np.float32)[:3, :4]
-        a.H, a.W, a.row0, a.row1 = H, W, row0, row1
-        a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-        for i, val in enumerate(c2w_h.reshape(-1)):
-            a.c2w[i] = float(val)
-        R = (row1 - row0) * W
-        a.R = R
-    device = torch.device(device)
+    R, device, keep = _set_ray_source(a, rays, camera, device)
     N = 1 if mode == "depth_only" else int(n_samples)
     a.mode, a.N, a.std_ = _MODES[mode], N, float(std)
     if mode == "gaussian":
@@ -523,9 +535,7 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
                                   f"n_samples a power of two in [2, 64] or a multiple of 64 up to 512 (mode {mode!r}, n_samples {N}, dtype {getattr(nerf, 'dtype', '?')})")
     use_fused = fused_ok if one_kernel is None else bool(one_kernel)
     nbytes = int(lib.ns_render_fused_workspace_bytes(R) if use_fused else lib.ns_render_workspace_bytes(R, N))
-    ws = (workspace or _default_ws).get(nbytes, device)
-    base = ws.data_ptr()
-    a.workspace_dev = (base + 255) & ~255
+    _set_workspace(a, workspace, nbytes, device)
     out = _rgb_disp_outputs(a, R, device, shard)
     if extras:
         out["z"] = torch.empty((R, N), dtype=torch.float32, device=device)
@@ -559,23 +569,7 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
     a = _lib.HierArgs()
     a.coarse = coarse.handle
     a.fine = fine.handle if fine is not None else None
-    keep = []
-    if rays is not None:
-        o, d, v = (_dev(t, n) for t, n in zip(rays, ("rays_o", "rays_d", "viewdirs")))
-        keep += [o, d, v]
-        device = o.device
-        R = o.shape[0]
-        a.o_dev, a.d_dev, a.viewdirs_dev, a.R = o.data_ptr(), d.data_ptr(), v.data_ptr(), R
-    else:
-        H, W, K, c2w, row0, row1 = camera
-        c2w_h = (c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)).astype(np.float32)[:3, :4]
-        a.H, a.W, a.row0, a.row1 = H, W, row0, row1
-        a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-        for i, val in enumerate(c2w_h.reshape(-1)):
-            a.c2w[i] = float(val)
-        R = (row1 - row0) * W
-        a.R = R
-    device = torch.device(device)
+    R, device, keep = _set_ray_source(a, rays, camera, device)
     a.Nc, a.Nf, a.lindisp, a.white_bkgd = int(n_coarse), int(n_importance), int(bool(lindisp)), int(bool(white_bkgd))
     a.near_, a.far_ = float(near), float(far)
     for name, t in (("t_rand_dev", t_rand), ("u_dev", u)):
@@ -583,9 +577,7 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
             t = _dev(t, name)
             keep.append(t)
             setattr(a, name, t.data_ptr())
-    nbytes = int(lib.ns_hier_workspace_bytes(R, a.Nc, a.Nf))
-    ws = (workspace or _default_ws).get(nbytes, device)
-    a.workspace_dev = (ws.data_ptr() + 255) & ~255
+    _set_workspace(a, workspace, int(lib.ns_hier_workspace_bytes(R, a.Nc, a.Nf)), device)
     Nt = a.Nc + a.Nf
     out = _rgb_disp_outputs(a, R, device, shard)
     if extras:

@@ -456,11 +456,17 @@ def test_psnr_guard_replaces_sigma_of_the_last_sample(gpu_modules, dtype):
     b32 = ops.render_rays_depthnet(dn, nf, rays=(o, d, view), n_samples=64, mode="uniform", std=0.1, one_kernel=False, guard=g32)
     assert torch.equal(a32["rgb"].view(torch.int32), b32["rgb"].view(torch.int32))
     assert float((a32["rgb"] - every["rgb"]).abs().max()) < 1e-3              # (the fp32 and the f16x3 sigma agree to fp32 rounding)
-    with pytest.raises((NotImplementedError, ValueError)):                       # the guard pass is defined for uniform placement
-        ops.render_rays_depthnet(dn, nf, camera=(H, W, K, c2w, 0, H), n_samples=8, mode="gaussian", std=0.1, guard=gw)
-    with pytest.raises(ValueError):                                              # ... and for another packing of the SAME network
-        ops.render_rays_depthnet(dn, nf, camera=(H, W, K, c2w, 0, H), n_samples=8, mode="uniform", std=0.1,
-                                 guard=gpu_modules("tiny_synth")["fine"].packed("f16x3"))
+    # both renderers reject a guard they cannot apply before launching anything: the caller's outputs keep what they held
+    for one in (True, False):
+        shard = torch.full((H * W, 4), -7.0, dtype=torch.float32, device="cuda")
+        with pytest.raises((NotImplementedError, ValueError)):                   # the guard pass is defined for uniform placement
+            ops.render_rays_depthnet(dn, nf, camera=(H, W, K, c2w, 0, H), n_samples=8, mode="gaussian", std=0.1, guard=gw,
+                                     one_kernel=one, shard=shard)
+        with pytest.raises(ValueError):                                          # ... and for another packing of the SAME network
+            ops.render_rays_depthnet(dn, nf, camera=(H, W, K, c2w, 0, H), n_samples=8, mode="uniform", std=0.1,
+                                     guard=gpu_modules("tiny_synth")["fine"].packed("f16x3"), one_kernel=one, shard=shard)
+        torch.cuda.synchronize()
+        assert bool((shard == -7.0).all()), one
 
 
 def step_rule_mask(raw_ref, z_ref, d, rgb_ref, sigma_last_eps, tol=1e-2):

@@ -51,3 +51,44 @@ def test_workspace_sizes_cover_their_parts():
         hier = int(lib.ns_hier_workspace_bytes(R, 64, 128))
         assert hier >= R * 36 + R * 64 * (4 + 16 + 4) + R * 192 * (4 + 16)
     assert int(lib.ns_render_fused_workspace_bytes(-1)) == 0 and int(lib.ns_hier_workspace_bytes(10, 2, 8)) == 0
+
+
+def test_workspace_sizes_are_pinned():
+    """Each renderer's workspace layout is written once and sizes and carves the workspace alike: the byte counts callers
+    allocate stay exactly what they were."""
+    lib = _lib.load()
+    chain = {1: {1: 2048, 64: 2816, 192: 5376}, 1000: {1: 80640, 64: 1340416, 192: 3900416},
+             640000: {1: 51200000, 64: 857600000, 192: 2496000000}}
+    fused = {0: 256, 1: 2816, 1000: 160768, 640000: 102400256}
+    hier = {1: {(64, 128): 6144, (64, 0): 3584, (3, 5): 2048}, 1000: {(64, 128): 5412096, (64, 0): 2852096, (3, 5): 268288},
+            640000: {(64, 128): 3463680000, (64, 0): 1825280000, (3, 5): 171520000}}
+    for R, by_n in chain.items():
+        assert {N: int(lib.ns_render_workspace_bytes(R, N)) for N in by_n} == by_n, R
+    assert {R: int(lib.ns_render_fused_workspace_bytes(R)) for R in fused} == fused
+    for R, by_n in hier.items():
+        assert {n: int(lib.ns_hier_workspace_bytes(R, *n)) for n in by_n} == by_n, R
+    assert int(lib.ns_render_workspace_bytes(0, 64)) == 0 and int(lib.ns_hier_workspace_bytes(0, 64, 128)) == 0
+    for bad in (lib.ns_render_workspace_bytes(-1, 64), lib.ns_render_workspace_bytes(10, 0), lib.ns_render_fused_workspace_bytes(-1),
+                lib.ns_hier_workspace_bytes(-1, 64, 128), lib.ns_hier_workspace_bytes(10, 2, 8), lib.ns_hier_workspace_bytes(10, 64, -1)):
+        assert int(bad) == 0
+
+
+def test_psnr_guard_handles_apply_to_uniform_placement_only():
+    class Module:                                        # stands in for a DepthNet / NeRF module: packed() -> a handle's dtype
+        def packed(self, dtype=None):
+            return type("Handle", (), {"dtype": dtype or ops.get_compute_dtype()})()
+
+    prev = ops.get_compute_dtype()
+    try:
+        ops.set_compute_dtype("bf16")
+        ops.set_psnr_guard(True)
+        assert ops.psnr_guard_handles(Module(), Module())[2].dtype == "f16x3"             # no sampling set-up given: as before
+        assert ops.psnr_guard_handles(Module(), Module(), mode="uniform", n_samples=2)[2].dtype == "f16x3"
+        for mode, n in (("gaussian", 64), ("depth_only", 64), ("uniform", 1)):
+            assert ops.psnr_guard_handles(Module(), Module(), mode=mode, n_samples=n)[2] is None, (mode, n)
+        ops.set_psnr_guard(False)
+        assert ops.psnr_guard_handles(Module(), Module(), mode="uniform", n_samples=64)[2] is None
+    finally:
+        ops.set_psnr_guard(False, threshold=16.0, depthnet="f16x3")
+        ops.set_compute_dtype(prev)
+
