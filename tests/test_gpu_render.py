@@ -325,7 +325,7 @@ def test_fused_compositing_matches_operator_chain_16bit(gpu_modules, dtype, scen
     dn, nf = m["depth"].packed(dtype), m["fine"].packed(dtype)
     o, d, view = ops.get_rays(H, W, K, c2w)[:3]
     mean = ops.depthnet_forward(dn, o, d)
-    for n in (64, 32, 96, 192, 16, 2, 128) + ((256, 512) if scene == "tiny_synth" else ()):   # (512: eight chunks per ray, runs of eight groups)
+    for n in (64, 32, 96, 192, 16, 2, 128, 4, 8) + ((256, 512, 320, 384, 448) if scene == "tiny_synth" else ()):   # (512: eight chunks per ray, runs of eight groups)
         pts, z = ops.place_samples(o, d, mean, n, "uniform", 0.1)
         raw = ops.nerf_forward_rays(nf, o, d, z, view)
         rgb, disp, acc, depth, alphas, weights = ops.raw2outputs(raw, z, d, None, True)
@@ -381,7 +381,7 @@ def test_one_kernel_renderers_on_a_handful_of_rays(gpu_modules):
     o, d, view = ops.get_rays(8, 8, K, O.pose_spherical(10.0, -30.0, 4.0)[:3, :4])[:3]
     for R in (1, 3, 7):
         rays = (o[:R].contiguous(), d[:R].contiguous(), view[:R].contiguous())
-        for n in (64, 2, 192, 512):
+        for n in (64, 2, 192, 512, 4, 8):
             for t in (0, 4, 5):
                 with ops.debug_switch(prod_tiles=t):
                     a = ops.render_rays_depthnet(dn, nf, rays=rays, n_samples=n, mode="uniform", std=0.1, extras=True, one_kernel=True)
@@ -414,7 +414,7 @@ def test_psnr_guard_replaces_sigma_of_the_last_sample(gpu_modules, dtype):
     dn, nf, gw = m["depth"].packed("f16x3"), m["fine"].packed(dtype), m["fine"].packed("f16x3")
     o, d, view = ops.get_rays(H, W, K, c2w)[:3]
     mean = ops.depthnet_forward(dn, o, d)
-    for n in (64, 32, 192):
+    for n in (64, 32, 192, 2, 8, 16):
         pts, z = ops.place_samples(o, d, mean, n, "uniform", 0.1)
         raw = ops.nerf_forward_rays(nf, o, d, z, view)
         raw_last = ops.nerf_forward_rays(gw, o, d, z[:, -1:].contiguous(), view)
@@ -638,7 +638,7 @@ def test_hierarchical_in_kernel_compositing_matches_chain(gpu_modules, dtype):
     _, K = O.blender_intrinsics(H, W)
     c2w = O.pose_spherical(-70.0, -30.0, 4.0)[:3, :4]
     nc, nf = m["coarse"].packed(dtype), m["fine"].packed(dtype)
-    for n_c, n_i in ((64, 128), (32, 32), (64, 64)):
+    for n_c, n_i in ((64, 128), (32, 32), (64, 64), (4, 4), (8, 8)):
         kw = dict(camera=(H, W, K, c2w, 0, H), n_coarse=n_c, n_importance=n_i, lindisp=True, white_bkgd=True)
         with ops.debug_switch(hier_chain=1):
             ref = ops.render_rays_hierarchical(nc, nf, extras=True, **kw)
