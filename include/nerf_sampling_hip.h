@@ -243,7 +243,7 @@ typedef struct ns_render_args {
    * composites to alpha = 0 or 1 either way -- found by the kernel itself, re-evaluated afterwards on a compacted list
    * (three small launches; the count never leaves the device) and their pixels re-added from the kernel's partial sums, bit
    * for bit what the every-ray guard gives wherever |sigma16 - sigma32| < guard_threshold.  The five-launch chain
-   * (ns_render_rays_depthnet) ignores it and guards every ray.                                                            */
+   * (ns_render_rays_depthnet), and the one-kernel renderer on an F16X3 field, ignore it and guard every ray.              */
   float guard_threshold;
 } ns_render_args;
 int64_t ns_render_workspace_bytes(int64_t R, int N);
@@ -254,7 +254,7 @@ int ns_render_rays_depthnet(const ns_render_args* args, void* stream);
  * epilogue by the same wave scan ns_raw2outputs runs: rgb / disp (and z / weights / pts when asked for) are BIT-IDENTICAL
  * to ns_render_rays_depthnet.  Three launches per call (ray generation, DepthNet, the fused kernel); HBM traffic is the
  * rays, 4 B + 16 B per ray and the weight streams.  Supported (ns_render_fused_supported != 0): mode NS_MODE_UNIFORM,
- * a bf16 / f16 NeRF handle with view directions, N a power of two in [2, 64] or a multiple of 64 up to 512 (a ray is then
+ * a bf16, f16 or f16x3 NeRF handle with view directions, N a power of two in [2, 64] or a multiple of 64 up to 512 (a ray is then
  * several 64-sample chunks composited side by side); anything else returns NS_E_UNSUPPORTED and
  * is served by ns_render_rays_depthnet.  Workspace: ns_render_fused_workspace_bytes(R) bytes, 256-byte aligned.        */
 int ns_render_fused_supported(const ns_weights* nerf, int mode, int N);

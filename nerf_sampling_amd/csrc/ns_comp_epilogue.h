@@ -1,0 +1,289 @@
+// In-kernel sample placement and compositing of the radiance-field MLP kernels on the 16x16x32 engine (the one-kernel renderer):
+// the 16-bit kernel (ns_nerf_mlp_ob16.hip, T = 4 / 5 tiles per wave) and the split-fp16 kernel (ns_nerf_mlp_x3.hip, T = 2) run
+// this code with their own group shape.  A group is NWAVES x T tiles of 16 samples = T chunks of 64 consecutive samples; wave w
+// holds samples w * 16 T .. (w + 1) * 16 T - 1 of it, so with T != 4 a chunk straddles waves.
+//
+// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. fix_rec under the same names.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "ns_composite_ray.h"
+#include "ns_mlp_engine.h"
+#include "ns_place.h"
+#include "ns_weights.h"
+
+namespace nsepi {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef v4f __attribute__((address_space(3))) * CrawPtr;
+typedef v2f __attribute__((address_space(3))) * CzdPtr;
+typedef float __attribute__((address_space(3))) * CsigPtr;
+
+// The lane id as a value the compiler cannot hoist: everything the compositing code derives from the lane (LDS record
+// addresses per tile, the scan's lane predicates for six segment widths) would otherwise be computed ONCE before the
+// group loop and kept alive across the ten layer statements -- which leave the compiler 32 VGPRs -- i.e. spilled to
+// scratch and reloaded in the epilogue behind s_waitcnt vmcnt(0), waiting out the weight DMA in flight (measured: +1.5 ms
+// per frame).  Two v_mbcnt per use instead.
+__device__ __forceinline__ int opaque_lane() {
+  uint32_t z = 0;
+  asm volatile("" : "+s"(z));
+  return static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z)));
+}
+
+// The compositing records in LDS, from byte address `base` on (kBytes): sample i (0 .. GS - 1) of the open group
+//   raw float4 per sample | {z, dist * |d|} float2 per sample, two group parities | sigma of a ray's last sample from the guard
+//   pass, one float per ray of the group, two parities | 128 chunk scalars
+template <int T, int NWAVES>
+struct Records {
+  static constexpr int GS = NWAVES * T * 16;
+  static constexpr uint32_t kBytes = GS * 36 + 512;
+  // rays of several chunks: per chunk of the group its transmittance factor (kCP) and its five sums (kCS); the ray that is open
+  // at the group's end: {carry, r, g, b, depth, acc}, two parities (kOPEN + 8 par is read, kOPEN + 8 (par ^ 1) written)
+  static constexpr int kCP = 0, kCS = 8, kOPEN = 8 + 8 * 8;          // float offsets inside the 128-float scalar block
+  static_assert(T <= 8, "eight chunks per group at most");
+  uint32_t base;
+  __device__ __forceinline__ CrawPtr raw(int i) const { return reinterpret_cast<CrawPtr>(static_cast<uintptr_t>(base + static_cast<uint32_t>(i) * 16u)); }
+  __device__ __forceinline__ CzdPtr zd(uint32_t par, int i) const {
+    return reinterpret_cast<CzdPtr>(static_cast<uintptr_t>(base + GS * 16u + (par * GS + static_cast<uint32_t>(i)) * 8u));
+  }
+  __device__ __forceinline__ CsigPtr sig(uint32_t par, int ray) const {      // ray: index within the group (<= GS / 2 rays)
+    return reinterpret_cast<CsigPtr>(static_cast<uintptr_t>(base + GS * 32u + (par * (GS / 2) + static_cast<uint32_t>(ray)) * 4u));
+  }
+  __device__ __forceinline__ CsigPtr scal(int k) const {
+    return reinterpret_cast<CsigPtr>(static_cast<uintptr_t>(base + GS * 36u + static_cast<uint32_t>(k) * 4u));
+  }
+};
+
+// Sample placement + the compositing record {z, dist * |d|} of every sample of the wave, ONE SAMPLE PER LANE (64 at a time: the
+// tile layout holds a sample on four lanes, and a per-tile evaluation would cost T times this): sample i of the wave's 16 T on
+// lane i % 64 of pass i / 64.  The records go to LDS -- the epilogue composites from them, and the caller's tiles read their
+// depth back from there (same wave: LDS order suffices).
+// st(slot, i): staged value `slot` of the wave's sample i -- o 0..2, d 3..5; 6: the ray's DepthNet depth (comp == 2) or the
+// sample's depth (comp == 1); 10: the NEXT sample's depth (comp == 1) or the guard pass's sigma of the ray's last sample.
+template <int T, int NWAVES, class Args, class Staged>
+__device__ __forceinline__ void place_wave(const Args& a, const Records<T, NWAVES>& rec, Staged st, int64_t grp, int gi,
+                                           uint32_t par, int wave) {
+  constexpr int GS = Records<T, NWAVES>::GS;
+  const int lo = opaque_lane();
+  constexpr int kPasses = (16 * T + 63) / 64;
+  // group-level scalars: how many of the group's GS samples exist, and the position of its first sample in its ray
+  // (N <= 64 divides the group size: 0;  N = 64 m: the run starts on a ray, every group adds GS mod N)
+  const int64_t left = a.S - grp * GS;
+  const int rem = left < GS ? static_cast<int>(left) : GS;
+  const int jg0 = a.m_chunks ? (gi * GS) % a.N : 0;                 // (wave-uniform 32-bit arithmetic, gi < 8)
+#pragma unroll
+  for (int pass = 0; pass < kPasses; ++pass) {
+    const int i = pass * 64 + lo;
+    if (i < 16 * T) {
+      // every staged value of the pass in one burst, ahead of the arithmetic (slot 10 holds the next depth, the guard's
+      // sigma, or nothing: read whatever is there, used only where it is defined)
+      const float m_or_z = st(6, i), d0 = st(3, i), d1 = st(4, i), d2 = st(5, i), s10 = st(10, i);
+      const int ig = wave * (16 * T) + i;                             // the sample's index within the group
+      const bool valid = ig < rem;
+      int j, ray_in_group;                                            // (a sample past the end: any in-range j, never used)
+      if (!a.m_chunks) {                                              // N <= 64, a power of two: whole rays per group
+        j = ig & (a.N - 1); ray_in_group = ig >> a.n_shift;
+      } else {                                                        // N >= 128, jg0 + ig < GS + N <= 3.5 N
+        const int x = jg0 + ig;
+        ray_in_group = (x >= a.N) + (x >= 2 * a.N) + (x >= 3 * a.N);
+        j = x - ray_in_group * a.N;
+      }
+      float zz = m_or_z, znext = s10;
+      if (a.comp == 2)        // sample_points_around_mean("uniform"): depths j and j + 1 of the ray from its mean
+        nsplace::uniform_z_pair(m_or_z, a.std_, a.lin_step, a.N - 1, j, zz, znext);
+      const float dist_raw = (j < a.N - 1) ? znext - zz : 1e10f;      // sampling_trainer.py:176-180
+      *rec.zd(par, ig) = v2f{zz, dist_raw * nscomp::ray_norm(d0, d1, d2)};
+      // the guard pass's sigma of this ray's last sample: one slot per ray of the group
+      if (a.sig_last && j == a.N - 1) *rec.sig(par, ray_in_group) = s10;
+      if (valid && (a.z_out || a.pts_out)) {
+        const int64_t sidx = grp * GS + ig;
+        if (a.z_out) a.z_out[sidx] = zz;
+        if (a.pts_out) {
+          float* q = a.pts_out + sidx * 3;
+          q[0] = st(0, i) + d0 * zz; q[1] = st(1, i) + d1 * zz; q[2] = st(2, i) + d2 * zz;
+        }
+      }
+    }
+  }
+}
+
+// The epilogue: raw2outputs (sampling_trainer.py:153-230) of the group whose raw records rec.raw() every wave has written (lane
+// le < 16 of tile t of wave w: sample (w T + t) 16 + le), with the {z, dist} records of parity `par` from place_wave.  Every wave
+// of the workgroup calls it (s_barrier inside unless T == 4); `comp` is a.comp != 0.
+template <int T, int NWAVES, class Args>
+__device__ __forceinline__ void composite_group(const Args& a, const Records<T, NWAVES>& rec, bool comp, int64_t grp, int gi,
+                                                uint32_t par, int wave, int le) {
+  constexpr int GS = Records<T, NWAVES>::GS;
+  constexpr int kCP = Records<T, NWAVES>::kCP, kCS = Records<T, NWAVES>::kCS, kOPEN = Records<T, NWAVES>::kOPEN;
+  if (comp && a.m_chunks) {
+    // Rays of m = N / 64 chunks (N = 128, 192, ...): a ray's chunks sit on different waves, possibly in different groups
+    // of the workgroup's run.  Three phases around two s_barriers, the arithmetic of raw2outputs_kernel's multi-chunk
+    // loop (ns_composite_ray.h: chunk_local, then T = carry * excl with the carry multiplied up chunk by chunk, every
+    // chunk's sums reduced on their own and added in chunk order):
+    //   1  every chunk on its wave: alpha, colours, the chunk's own transmittance scan; its factor P_c -> LDS
+    //   2  carry entering the chunk = (the open ray's carry, if the ray began in an earlier group) x P of the ray's
+    //      earlier chunks of this group, in order; weights; the chunk's five sums -> LDS
+    //   3  lane c of the last wave, for the chunk c that ends a ray or the group: totals in chunk order; a finished ray is written,
+    //      the ray that stays open hands {carry, sums} to the next group
+    const int m = a.m_chunks;
+    const int64_t C0 = grp * T;                      // global index of the group's first chunk
+    constexpr int NCW = (T + NWAVES - 1) / NWAVES;   // chunks a wave may own
+    nscomp::ChunkLocal L[NCW];
+    float zc[NCW];
+    bool okc[NCW];
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave's raw records are in LDS
+    nsmlp::static_for<NCW>([&](auto ci_) {
+      constexpr int ci = decltype(ci_)::value;
+      const int c = wave + NWAVES * ci;
+      if (c < T) {                                   // (wave-uniform)
+        const int i = c * 64 + le;
+        const int64_t s_ = grp * GS + i;
+        okc[ci] = s_ < a.S;
+        const v4f qv = *rec.raw(i);
+        const v2f zd = *rec.zd(par, i);
+        float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);
+        if (a.sig_last) {                            // the guard pass's sigma for the ray's last sample
+          const int x = (gi * GS) % a.N + i;         // position counted from the start of the group's first ray
+          const int k = (x >= a.N) + (x >= 2 * a.N) + (x >= 3 * a.N);
+          if (x - k * a.N == a.N - 1) q.w = *rec.sig(par, k);
+        }
+        L[ci] = nscomp::chunk_local<64>(okc[ci], le, q, zd.y, 1.0f, 0.0f, false);
+        zc[ci] = zd.x;
+        if (le == 63) *rec.scal(kCP + c) = L[ci].p;
+      }
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    nsmlp::static_for<NCW>([&](auto ci_) {
+      constexpr int ci = decltype(ci_)::value;
+      const int c = wave + NWAVES * ci;
+      if (c < T) {
+        const int pos = static_cast<int>((C0 + c) % m);          // the chunk's position in its ray
+        const int first = c - pos;                               // the ray's first chunk, as an index of this group
+        float carry = first < 0 ? *rec.scal(kOPEN + 8 * par) : 1.0f;
+        for (int cc = first < 0 ? 0 : first; cc < c; ++cc) carry = carry * *rec.scal(kCP + cc);
+        const float Tr = carry * L[ci].excl;
+        const float w = L[ci].alpha * Tr;
+        const int64_t s_ = grp * GS + c * 64 + le;
+        if (okc[ci] && a.weights) a.weights[s_] = w;
+        nscomp::RayAccum A;
+        if (okc[ci]) {
+          A.r += w * L[ci].cr; A.g += w * L[ci].cg; A.b += w * L[ci].cb;
+          A.depth += w * zc[ci];
+          A.acc += w;
+        }
+        nscomp::reduce_sums<64>(A, le);
+        if (le == 63) {
+          *rec.scal(kCS + 8 * c + 0) = A.r; *rec.scal(kCS + 8 * c + 1) = A.g; *rec.scal(kCS + 8 * c + 2) = A.b;
+          *rec.scal(kCS + 8 * c + 3) = A.depth; *rec.scal(kCS + 8 * c + 4) = A.acc;
+        }
+      }
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (wave == NWAVES - 1 && le < T) {       // (the last wave: with five tiles wave 0 has had two chunks in phases 1 and 2, this one one)
+      const int c = le;
+      const int pos = static_cast<int>((C0 + c) % m);
+      const bool ends = pos == m - 1;
+      if (ends || c == T - 1) {
+        const int first = c - pos;
+        nscomp::RayAccum tot;                        // tot.carry: the transmittance behind chunk c
+        if (first < 0) {
+          tot.carry = *rec.scal(kOPEN + 8 * par); tot.r = *rec.scal(kOPEN + 8 * par + 1); tot.g = *rec.scal(kOPEN + 8 * par + 2);
+          tot.b = *rec.scal(kOPEN + 8 * par + 3); tot.depth = *rec.scal(kOPEN + 8 * par + 4); tot.acc = *rec.scal(kOPEN + 8 * par + 5);
+        }
+        for (int cc = first < 0 ? 0 : first; cc <= c; ++cc) {
+          tot.carry = tot.carry * *rec.scal(kCP + cc);
+          tot.r = tot.r + *rec.scal(kCS + 8 * cc); tot.g = tot.g + *rec.scal(kCS + 8 * cc + 1); tot.b = tot.b + *rec.scal(kCS + 8 * cc + 2);
+          tot.depth = tot.depth + *rec.scal(kCS + 8 * cc + 3); tot.acc = tot.acc + *rec.scal(kCS + 8 * cc + 4);
+        }
+        if (ends) {
+          const int64_t r = (C0 + c) / m;
+          if (r * a.N < a.S) {
+            float disp;
+            nscomp::finish_totals(tot, a.white_bkgd, disp);
+            float* prgb = a.rgb + r * a.rgb_stride;
+            prgb[0] = tot.r; prgb[1] = tot.g; prgb[2] = tot.b;
+            a.disp[r * a.disp_stride] = disp;
+          }
+        } else {                                     // the ray goes on in the workgroup's next group
+          const uint32_t np = par ^ 1u;
+          *rec.scal(kOPEN + 8 * np) = tot.carry; *rec.scal(kOPEN + 8 * np + 1) = tot.r; *rec.scal(kOPEN + 8 * np + 2) = tot.g;
+          *rec.scal(kOPEN + 8 * np + 3) = tot.b; *rec.scal(kOPEN + 8 * np + 4) = tot.depth; *rec.scal(kOPEN + 8 * np + 5) = tot.acc;
+        }
+      }
+    }
+  } else if (comp) {
+    // raw2outputs in the epilogue (sampling_trainer.py:153-230): the group's samples are T chunks of 64 consecutive
+    // samples -- whole rays (N <= 64, a power of two) -- one chunk per wave pass, composited by the lane-level code the
+    // stand-alone kernel runs (ns_composite_ray.h: same operations in the same order, so bit-identical to it).
+    // Four tiles: a wave's chunk is its own 64 samples, the wave's own LDS order suffices; two or five tiles: chunks straddle
+    // waves, one s_barrier (all four waves reach it: the group loop is workgroup-uniform).
+    if constexpr (T == 4) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    auto composite = [&](auto sw_, int c) {
+      constexpr int SW = decltype(sw_)::value;
+      const int i = c * 64 + le;
+      const int64_t s = grp * GS + i;
+      const bool ok = s < a.S;
+      const v4f qv = *rec.raw(i);
+      const v2f zd = *rec.zd(par, i);
+      float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);
+      if (a.sig_last && (le & (SW - 1)) == SW - 1) q.w = *rec.sig(par, i / SW);      // the guard pass's sigma_last
+      nscomp::RayAccum A, tree;
+      float alpha, w, disp, Tr;
+      const int sub = le & (SW - 1);
+      nscomp::composite_chunk<SW>(A, ok, sub, q, zd.x, zd.y, 1.0f, 0.0f, false, alpha, w, &Tr);
+      if (ok && a.weights) a.weights[s] = w;
+      nscomp::composite_finish<SW>(A, a.white_bkgd, disp, sub, &tree);
+      if (ok && sub == SW - 1) {
+        const int64_t r = s / SW;      // N == SW
+        float* prgb = a.rgb + r * a.rgb_stride;
+        prgb[0] = A.r; prgb[1] = A.g; prgb[2] = A.b;
+        a.disp[r * a.disp_stride] = disp;
+        if (a.fix_rec && __builtin_fabsf(q.w) < a.fix_thr) {      // (a NaN sigma compares false: a NaN ray stays NaN)
+          float* rec16 = a.fix_rec + static_cast<size_t>(atomicAdd(a.fix_count, 1u)) * 16;
+          reinterpret_cast<float4*>(rec16)[0] = make_float4(tree.r, tree.g, tree.b, tree.depth);
+          reinterpret_cast<float4*>(rec16)[1] = make_float4(tree.acc, Tr, q.x, q.y);
+          reinterpret_cast<float4*>(rec16)[2] = make_float4(q.z, zd.x, zd.y, __builtin_bit_cast(float, static_cast<uint32_t>(r)));
+          rec16[12] = __builtin_bit_cast(float, static_cast<uint32_t>(static_cast<uint64_t>(r) >> 32));
+        }
+      }
+    };
+    for (int c = wave; c < T; c += NWAVES) {
+      switch (a.N) {
+        case 64: composite(std::integral_constant<int, 64>{}, c); break;
+        case 32: composite(std::integral_constant<int, 32>{}, c); break;
+        case 16: composite(std::integral_constant<int, 16>{}, c); break;
+        case 8: composite(std::integral_constant<int, 8>{}, c); break;
+        case 4: composite(std::integral_constant<int, 4>{}, c); break;
+        default: composite(std::integral_constant<int, 2>{}, c); break;
+      }
+    }
+  }
+}
+
+// The host side: the compositing fields of Args from the renderer's ns_composite_args (the selective guard's fields are the
+// caller's); sg_groups is set at launch, from the kernel's group size
+template <class Args>
+inline void set_comp_args(Args& a, const ns_composite_args* comp, int N) {
+  a.comp = comp->mean_dev ? 2 : 1;
+  a.mean = comp->mean_dev; a.std_ = comp->std_; a.lin_step = nsplace::linspace_step_of(-comp->std_, comp->std_, N - 1);
+  a.n_shift = -1;
+  for (int k = 0; k < 31; ++k) if (N == (1 << k)) a.n_shift = k;
+  a.m_chunks = N > 64 ? N / 64 : 0;
+  a.white_bkgd = comp->white_bkgd;
+  a.rgb = comp->rgb_dev; a.rgb_stride = comp->rgb_stride; a.disp = comp->disp_dev; a.disp_stride = comp->disp_stride;
+  a.weights = comp->weights_dev; a.z_out = comp->z_out_dev; a.pts_out = comp->pts_out_dev;
+  a.sig_last = comp->sigma_last_dev;
+}
+// runs of lcm(group samples, N) / group samples consecutive groups (whole rays per run) when rays span several chunks, else 1
+inline int run_groups(int group_samples, int m_chunks, int N) {
+  if (!m_chunks) return 1;
+  int x = group_samples, y = N;
+  while (y) { const int t = x % y; x = y; y = t; }
+  return N / x;   // lcm(gs, N) / gs
+}
+
+}  // namespace nsepi

@@ -6,9 +6,8 @@
 // every A fragment (16 output rows x 32 input features, 1 KiB) read from LDS feeds 4 MFMAs; layers are walked one
 // 16-row output sub-block at a time (layer_ob16 in ns_mlp_engine.h; weight stream layout 16 of ns_pack.hip).
 #include "ns_common.h"
-#include "ns_composite_ray.h"
+#include "ns_comp_epilogue.h"
 #include "ns_mlp_engine.h"
-#include "ns_place.h"
 #include "ns_weights.h"
 
 // This file is compiled twice: as itself, and with -DNS_OB16_TU_T5 as a second translation unit that holds only the
@@ -191,37 +190,9 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
   // staging: value slot k (0..10) of sample j (0 .. 16 T - 1) of this wave's group at stage_base + k * kStageRow + j * 4
   constexpr uint32_t kStageRow = T * 64, kStageRows = 11;
   const uint32_t stage_base = stash_region + NWAVES * (T * 3 * 1024) + static_cast<uint32_t>(wave) * (kStageRows * kStageRow);
-  // compositing records (only allocated when a.comp): sample i (0 .. GS - 1) of the open group
-  constexpr int GS = NWAVES * T * 16;
-  const uint32_t comp_region = stash_region + NWAVES * (T * 3 * 1024) + NWAVES * (kStageRows * kStageRow);
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  typedef v4f __attribute__((address_space(3))) * CrawPtr;
-  typedef v2f __attribute__((address_space(3))) * CzdPtr;
-  // The lane id as a value the compiler cannot hoist: everything the compositing code derives from the lane (LDS record
-  // addresses per tile, the scan's lane predicates for six segment widths) would otherwise be computed ONCE before the
-  // group loop and kept alive across the ten layer statements -- which leave the compiler 32 VGPRs -- i.e. spilled to
-  // scratch and reloaded in the epilogue behind s_waitcnt vmcnt(0), waiting out the weight DMA in flight (measured: +1.5 ms
-  // per frame).  Two v_mbcnt per use instead.
-  auto opaque_lane = [] {
-    uint32_t z = 0;
-    asm volatile("" : "+s"(z));
-    return static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z)));
-  };
-  auto craw_at = [&](int i) -> CrawPtr { return reinterpret_cast<CrawPtr>(static_cast<uintptr_t>(comp_region + static_cast<uint32_t>(i) * 16u)); };
-  auto czd_at = [&](uint32_t par, int i) -> CzdPtr {
-    return reinterpret_cast<CzdPtr>(static_cast<uintptr_t>(comp_region + GS * 16u + (par * GS + static_cast<uint32_t>(i)) * 8u));
-  };
-  typedef float __attribute__((address_space(3))) * CsigPtr;
-  auto csig_at = [&](uint32_t par, int ray) -> CsigPtr {      // ray: index within the group (<= GS / 2 rays)
-    return reinterpret_cast<CsigPtr>(static_cast<uintptr_t>(comp_region + GS * 32u + (par * (GS / 2) + static_cast<uint32_t>(ray)) * 4u));
-  };
-  // rays of several chunks: per chunk of the group its transmittance factor (cP) and its five sums (cS); the ray that is open
-  // at the group's end: {carry, r, g, b, depth, acc}, two parities (copen[par] is read, copen[par ^ 1] written)
-  auto cscal_at = [&](int k) -> CsigPtr {
-    return reinterpret_cast<CsigPtr>(static_cast<uintptr_t>(comp_region + GS * 36u + static_cast<uint32_t>(k) * 4u));
-  };
-  constexpr int kCP = 0, kCS = 8, kOPEN = 8 + 8 * 8;          // float offsets inside the 128-float scalar block
+  // compositing records (only allocated when a.comp): ns_comp_epilogue.h
+  const nsepi::Records<T, NWAVES> rec{stash_region + NWAVES * (T * 3 * 1024) + NWAVES * (kStageRows * kStageRow)};
+  using nsepi::v4f;
 
   PipeT ring;
   ring.init(a.stream, smem, a.n_slabs, wave, lane);
@@ -316,63 +287,18 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
       // embedded or stashed: read tile by tile, each read sat right in front of its first use (an exposed LDS latency per
       // value, ~3 % of the kernel: nothing else runs on this SIMD while the lone wave waits).
       float P[T][3], V[T][3];          // (compile-time indices only: a runtime index would park the arrays in scratch)
-      if (a.comp) {   // (wave-uniform)
-        // Sample placement + the compositing record {z, dist * |d|} of every sample of the wave, ONE SAMPLE PER LANE (64 at a
-        // time: the tile layout below holds a sample on four lanes, and a per-tile evaluation would cost T times this):
-        // sample i of the wave's 16 T on lane i % 64 of pass i / 64.  The records go to LDS -- the epilogue composites from
-        // them, and the tiles read their depth back from there a few lines down (same wave: LDS order suffices).
-        const int lo = opaque_lane();
-        constexpr int kPasses = (16 * T + 63) / 64;
-        // group-level scalars: how many of the group's GS samples exist, and the position of its first sample in its ray
-        // (N <= 64 divides the group size: 0;  N = 64 m: the run starts on a ray, every group adds GS mod N)
-        const int64_t left = a.S - grp * GS;
-        const int rem = left < GS ? static_cast<int>(left) : GS;
-        const int jg0 = a.m_chunks ? (gi * GS) % a.N : 0;                 // (wave-uniform 32-bit arithmetic, gi < 8)
-#pragma unroll
-        for (int pass = 0; pass < kPasses; ++pass) {
-          const int i = pass * 64 + lo;
-          if (i < 16 * T) {
-            auto st = [&](int slot) -> float {
-              return *reinterpret_cast<const float __attribute__((address_space(3)))*>(
-                  static_cast<uintptr_t>(stage_base + slot * kStageRow + i * 4));
-            };
-            // every staged value of the pass in one burst, ahead of the arithmetic (slot 10 holds the next depth, the guard's
-            // sigma, or nothing: read whatever is there, used only where it is defined)
-            const float m_or_z = st(6), d0 = st(3), d1 = st(4), d2 = st(5), s10 = st(10);
-            const int ig = wave * (16 * T) + i;                             // the sample's index within the group
-            const bool valid = ig < rem;
-            int j, ray_in_group;                                            // (a sample past the end: any in-range j, never used)
-            if (!a.m_chunks) {                                              // N <= 64, a power of two: whole rays per group
-              j = ig & (a.N - 1); ray_in_group = ig >> a.n_shift;
-            } else {                                                        // N >= 128, jg0 + ig < GS + N <= 3.5 N
-              const int x = jg0 + ig;
-              ray_in_group = (x >= a.N) + (x >= 2 * a.N) + (x >= 3 * a.N);
-              j = x - ray_in_group * a.N;
-            }
-            float zz = m_or_z, znext = s10;
-            if (a.comp == 2)        // sample_points_around_mean("uniform"): depths j and j + 1 of the ray from its mean
-              nsplace::uniform_z_pair(m_or_z, a.std_, a.lin_step, a.N - 1, j, zz, znext);
-            const float dist_raw = (j < a.N - 1) ? znext - zz : 1e10f;      // sampling_trainer.py:176-180
-            *czd_at(par, ig) = v2f{zz, dist_raw * nscomp::ray_norm(d0, d1, d2)};
-            // the guard pass's sigma of this ray's last sample: one slot per ray of the group
-            if (a.sig_last && j == a.N - 1) *csig_at(par, ray_in_group) = s10;
-            if (valid && (a.z_out || a.pts_out)) {
-              const int64_t sidx = grp * GS + ig;
-              if (a.z_out) a.z_out[sidx] = zz;
-              if (a.pts_out) {
-                float* q = a.pts_out + sidx * 3;
-                q[0] = st(0) + d0 * zz; q[1] = st(1) + d1 * zz; q[2] = st(2) + d2 * zz;
-              }
-            }
-          }
-        }
+      if (a.comp) {   // (wave-uniform) placement and the {z, dist} records, one sample per lane (ns_comp_epilogue.h)
+        nsepi::place_wave(a, rec, [&](int slot, int i) -> float {
+          return *reinterpret_cast<const float __attribute__((address_space(3)))*>(
+              static_cast<uintptr_t>(stage_base + slot * kStageRow + i * 4));
+        }, grp, gi, par, wave);
       }
       static_for<T>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
         if (a.pts) {
           static_for<3>([&](auto c_) { P[t][decltype(c_)::value] = staged(t, decltype(c_)::value); });
         } else {
-          const float zz = a.comp ? (*czd_at(par, (wave * T + t) * 16 + n)).x : staged(t, 6);
+          const float zz = a.comp ? (*rec.zd(par, (wave * T + t) * 16 + n)).x : staged(t, 6);
           static_for<3>([&](auto c_) {
             constexpr int c = decltype(c_)::value;
             P[t][c] = staged(t, c) + staged(t, 3 + c) * zz;
@@ -520,7 +446,7 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
 
     bool comp = false;
     if constexpr (!EMBEDDED) comp = a.comp != 0;
-    const int le = opaque_lane();      // the lane id of the epilogue (see opaque_lane)
+    const int le = nsepi::opaque_lane();      // the lane id of the epilogue (see nsepi::opaque_lane)
     if (le < 16) {                     // lane group g == 0 holds the outputs: rows 0..2 = rgb, sigma from the view layer
       static_for<T>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
@@ -528,156 +454,11 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
         const int64_t sidx = sample_of(grp, t, le, valid);
         float4 o4 = make_float4(last[t][0], last[t][1], last[t][2], sigma[t]);
         if ((bad >> t) & 1u) { const float q = __builtin_nanf(""); o4 = make_float4(q, q, q, q); }
-        if (comp) *craw_at((wave * T + t) * 16 + le) = v4f{o4.x, o4.y, o4.z, o4.w};
+        if (comp) *rec.raw((wave * T + t) * 16 + le) = v4f{o4.x, o4.y, o4.z, o4.w};
         if (valid && a.raw) reinterpret_cast<float4*>(a.raw)[sidx] = o4;
       });
     }
-    if constexpr (!EMBEDDED) {
-      if (comp && a.m_chunks) {
-        // Rays of m = N / 64 chunks (N = 128, 192, ...): a ray's chunks sit on different waves, possibly in different groups
-        // of the workgroup's run.  Three phases around two s_barriers, the arithmetic of raw2outputs_kernel's multi-chunk
-        // loop (ns_composite_ray.h: chunk_local, then T = carry * excl with the carry multiplied up chunk by chunk, every
-        // chunk's sums reduced on their own and added in chunk order):
-        //   1  every chunk on its wave: alpha, colours, the chunk's own transmittance scan; its factor P_c -> LDS
-        //   2  carry entering the chunk = (the open ray's carry, if the ray began in an earlier group) x P of the ray's
-        //      earlier chunks of this group, in order; weights; the chunk's five sums -> LDS
-        //   3  lane c of the last wave, for the chunk c that ends a ray or the group: totals in chunk order; a finished ray is written,
-        //      the ray that stays open hands {carry, sums} to the next group
-        const int m = a.m_chunks;
-        const int64_t C0 = grp * T;                      // global index of the group's first chunk
-        constexpr int NCW = (T + NWAVES - 1) / NWAVES;   // chunks a wave may own
-        nscomp::ChunkLocal L[NCW];
-        float zc[NCW];
-        bool okc[NCW];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave's raw records are in LDS
-        static_for<NCW>([&](auto ci_) {
-          constexpr int ci = decltype(ci_)::value;
-          const int c = wave + NWAVES * ci;
-          if (c < T) {                                   // (wave-uniform)
-            const int i = c * 64 + le;
-            const int64_t s_ = grp * GS + i;
-            okc[ci] = s_ < a.S;
-            const v4f qv = *craw_at(i);
-            const v2f zd = *czd_at(par, i);
-            float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);
-            if (a.sig_last) {                            // the guard pass's sigma for the ray's last sample
-              const int x = (gi * GS) % a.N + i;         // position counted from the start of the group's first ray
-              const int k = (x >= a.N) + (x >= 2 * a.N) + (x >= 3 * a.N);
-              if (x - k * a.N == a.N - 1) q.w = *csig_at(par, k);
-            }
-            L[ci] = nscomp::chunk_local<64>(okc[ci], le, q, zd.y, 1.0f, 0.0f, false);
-            zc[ci] = zd.x;
-            if (le == 63) *cscal_at(kCP + c) = L[ci].p;
-          }
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        static_for<NCW>([&](auto ci_) {
-          constexpr int ci = decltype(ci_)::value;
-          const int c = wave + NWAVES * ci;
-          if (c < T) {
-            const int pos = static_cast<int>((C0 + c) % m);          // the chunk's position in its ray
-            const int first = c - pos;                               // the ray's first chunk, as an index of this group
-            float carry = first < 0 ? *cscal_at(kOPEN + 8 * par) : 1.0f;
-            for (int cc = first < 0 ? 0 : first; cc < c; ++cc) carry = carry * *cscal_at(kCP + cc);
-            const float Tr = carry * L[ci].excl;
-            const float w = L[ci].alpha * Tr;
-            const int64_t s_ = grp * GS + c * 64 + le;
-            if (okc[ci] && a.weights) a.weights[s_] = w;
-            nscomp::RayAccum A;
-            if (okc[ci]) {
-              A.r += w * L[ci].cr; A.g += w * L[ci].cg; A.b += w * L[ci].cb;
-              A.depth += w * zc[ci];
-              A.acc += w;
-            }
-            nscomp::reduce_sums<64>(A, le);
-            if (le == 63) {
-              *cscal_at(kCS + 8 * c + 0) = A.r; *cscal_at(kCS + 8 * c + 1) = A.g; *cscal_at(kCS + 8 * c + 2) = A.b;
-              *cscal_at(kCS + 8 * c + 3) = A.depth; *cscal_at(kCS + 8 * c + 4) = A.acc;
-            }
-          }
-        });
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (wave == NWAVES - 1 && le < T) {       // (the last wave: with five tiles wave 0 has had two chunks in phases 1 and 2, this one one)
-          const int c = le;
-          const int pos = static_cast<int>((C0 + c) % m);
-          const bool ends = pos == m - 1;
-          if (ends || c == T - 1) {
-            const int first = c - pos;
-            nscomp::RayAccum tot;                        // tot.carry: the transmittance behind chunk c
-            if (first < 0) {
-              tot.carry = *cscal_at(kOPEN + 8 * par); tot.r = *cscal_at(kOPEN + 8 * par + 1); tot.g = *cscal_at(kOPEN + 8 * par + 2);
-              tot.b = *cscal_at(kOPEN + 8 * par + 3); tot.depth = *cscal_at(kOPEN + 8 * par + 4); tot.acc = *cscal_at(kOPEN + 8 * par + 5);
-            }
-            for (int cc = first < 0 ? 0 : first; cc <= c; ++cc) {
-              tot.carry = tot.carry * *cscal_at(kCP + cc);
-              tot.r = tot.r + *cscal_at(kCS + 8 * cc); tot.g = tot.g + *cscal_at(kCS + 8 * cc + 1); tot.b = tot.b + *cscal_at(kCS + 8 * cc + 2);
-              tot.depth = tot.depth + *cscal_at(kCS + 8 * cc + 3); tot.acc = tot.acc + *cscal_at(kCS + 8 * cc + 4);
-            }
-            if (ends) {
-              const int64_t r = (C0 + c) / m;
-              if (r * a.N < a.S) {
-                float disp;
-                nscomp::finish_totals(tot, a.white_bkgd, disp);
-                float* prgb = a.rgb + r * a.rgb_stride;
-                prgb[0] = tot.r; prgb[1] = tot.g; prgb[2] = tot.b;
-                a.disp[r * a.disp_stride] = disp;
-              }
-            } else {                                     // the ray goes on in the workgroup's next group
-              const uint32_t np = par ^ 1u;
-              *cscal_at(kOPEN + 8 * np) = tot.carry; *cscal_at(kOPEN + 8 * np + 1) = tot.r; *cscal_at(kOPEN + 8 * np + 2) = tot.g;
-              *cscal_at(kOPEN + 8 * np + 3) = tot.b; *cscal_at(kOPEN + 8 * np + 4) = tot.depth; *cscal_at(kOPEN + 8 * np + 5) = tot.acc;
-            }
-          }
-        }
-      } else if (comp) {
-        // raw2outputs in the epilogue (sampling_trainer.py:153-230): the group's samples are T chunks of 64 consecutive
-        // samples -- whole rays (N <= 64, a power of two) -- one chunk per wave pass, composited by the lane-level code the
-        // stand-alone kernel runs (ns_composite_ray.h: same operations in the same order, so bit-identical to it).
-        // Four tiles: a wave's chunk is its own 64 samples, the wave's own LDS order suffices; five tiles: chunks straddle
-        // waves, one s_barrier (all four waves reach it: the group loop is workgroup-uniform).
-        if constexpr (T == 4) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-        else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        auto composite = [&](auto sw_, int c) {
-          constexpr int SW = decltype(sw_)::value;
-          const int i = c * 64 + le;
-          const int64_t s = grp * GS + i;
-          const bool ok = s < a.S;
-          const v4f qv = *craw_at(i);
-          const v2f zd = *czd_at(par, i);
-          float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);
-          if (a.sig_last && (le & (SW - 1)) == SW - 1) q.w = *csig_at(par, i / SW);      // the guard pass's sigma_last
-          nscomp::RayAccum A, tree;
-          float alpha, w, disp, Tr;
-          const int sub = le & (SW - 1);
-          nscomp::composite_chunk<SW>(A, ok, sub, q, zd.x, zd.y, 1.0f, 0.0f, false, alpha, w, &Tr);
-          if (ok && a.weights) a.weights[s] = w;
-          nscomp::composite_finish<SW>(A, a.white_bkgd, disp, sub, &tree);
-          if (ok && sub == SW - 1) {
-            const int64_t r = s / SW;      // N == SW
-            float* prgb = a.rgb + r * a.rgb_stride;
-            prgb[0] = A.r; prgb[1] = A.g; prgb[2] = A.b;
-            a.disp[r * a.disp_stride] = disp;
-            if (a.fix_rec && __builtin_fabsf(q.w) < a.fix_thr) {      // (a NaN sigma compares false: a NaN ray stays NaN)
-              float* rec = a.fix_rec + static_cast<size_t>(atomicAdd(a.fix_count, 1u)) * 16;
-              reinterpret_cast<float4*>(rec)[0] = make_float4(tree.r, tree.g, tree.b, tree.depth);
-              reinterpret_cast<float4*>(rec)[1] = make_float4(tree.acc, Tr, q.x, q.y);
-              reinterpret_cast<float4*>(rec)[2] = make_float4(q.z, zd.x, zd.y, __builtin_bit_cast(float, static_cast<uint32_t>(r)));
-              rec[12] = __builtin_bit_cast(float, static_cast<uint32_t>(static_cast<uint64_t>(r) >> 32));
-            }
-          }
-        };
-        for (int c = wave; c < T; c += NWAVES) {
-          switch (a.N) {
-            case 64: composite(std::integral_constant<int, 64>{}, c); break;
-            case 32: composite(std::integral_constant<int, 32>{}, c); break;
-            case 16: composite(std::integral_constant<int, 16>{}, c); break;
-            case 8: composite(std::integral_constant<int, 8>{}, c); break;
-            case 4: composite(std::integral_constant<int, 4>{}, c); break;
-            default: composite(std::integral_constant<int, 2>{}, c); break;
-          }
-        }
-      }
-    }
+    if constexpr (!EMBEDDED) nsepi::composite_group(a, rec, comp, grp, gi, par, wave, le);
   }
   ring.finish();
 }
@@ -696,7 +477,7 @@ int launch(Nerf16Args& a, hipStream_t stream) {
   const size_t lds = static_cast<size_t>(Pipe<M, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
                      ((static_cast<size_t>(a.bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * TT * 3 * 1024 +
                      static_cast<size_t>(kWaves) * 11 * (TT * 64) +      // ring | bias | embedding stash | input staging
-                     (a.comp && !EMB ? static_cast<size_t>(kWaves) * TT * 16 * 36 + 512 : 0);   // | compositing records (32 B per sample + 8 B per ray pair) + chunk scalars
+                     (a.comp && !EMB ? static_cast<size_t>(nsepi::Records<TT, kWaves>::kBytes) : 0);   // | compositing records
   if (lds > 160 * 1024) {
     ns::set_error("ns_nerf_forward: %zu bytes of LDS needed (too deep a network for the resident bias image)", lds);
     return NS_E_UNSUPPORTED;
@@ -707,13 +488,7 @@ int launch(Nerf16Args& a, hipStream_t stream) {
   const int64_t n_groups = (n_tiles + kWaves * TT - 1) / (kWaves * TT);
   int cus = ns::cu_count();
   if (cus <= 0) cus = 256;
-  a.sg_groups = 1;
-  if (a.m_chunks) {          // runs of lcm(group samples, N) / group samples consecutive groups: whole rays per run
-    const int gs = kWaves * TT * 16;
-    int x = gs, y = a.N;
-    while (y) { const int t = x % y; x = y; y = t; }
-    a.sg_groups = a.N / x;   // lcm(gs, N) / gs
-  }
+  a.sg_groups = nsepi::run_groups(kWaves * TT * 16, a.m_chunks, a.N);
   const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
   const int grid = static_cast<int>(n_runs < cus ? n_runs : cus);
   kern<<<grid, kWaves * 64, lds, stream>>>(a);
@@ -755,11 +530,13 @@ int nsob16::launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t 
 #else
 int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
                        const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev);
+                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
 
-// which (network, sample count) pairs the kernel composites itself (see Nerf16Args::comp)
+// which (network, sample count) pairs the kernel composites itself (see Nerf16Args::comp): the 16-bit fields here, the split-fp16
+// (f16x3) fields in ns_nerf_mlp_x3.hip
 bool ns_nerf_can_composite(const ns_weights* net, int N) {
-  return net && net->kind == NS_KIND_NERF && net->layout == 16 && (net->dtype == NS_DTYPE_BF16 || net->dtype == NS_DTYPE_F16) &&
+  return net && net->kind == NS_KIND_NERF && net->layout == 16 &&
+         (net->dtype == NS_DTYPE_BF16 || net->dtype == NS_DTYPE_F16 || net->dtype == NS_DTYPE_F16X3) &&
          net->use_viewdirs && net->out_ch == 4 &&
          ((N >= 2 && N <= 64 && (N & (N - 1)) == 0) || (N > 64 && N % 64 == 0 && N <= 512));
 }
@@ -770,8 +547,8 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
                          float* raw_dev, hipStream_t stream, const ns_composite_args* comp) {
   if (comp) {
     if (!ns_nerf_can_composite(net, N)) {
-      ns::set_error("in-kernel compositing needs a 16-bit NeRF handle with view directions and N a power of two in [2, 64] or a "
-                    "multiple of 64 up to 512 (N = %d)", N);
+      ns::set_error("in-kernel compositing needs a bf16, f16 or f16x3 NeRF handle with view directions and N a power of two in "
+                    "[2, 64] or a multiple of 64 up to 512 (N = %d)", N);
       return NS_E_UNSUPPORTED;
     }
     if (pts_dev || x90_dev || !(o_dev && d_dev) || !(z_dev || comp->mean_dev) || !(comp->rgb_dev && comp->disp_dev)) {
@@ -780,7 +557,7 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
     }
   }
   if (net->dtype == NS_DTYPE_F16X3)   // split fp16 operands: ns_nerf_mlp_x3.hip
-    return ns_nerf_forward_x3(net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, x90_dev, S, N, raw_dev, stream, nullptr);
+    return ns_nerf_forward_x3(net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, x90_dev, S, N, raw_dev, stream, nullptr, comp);
   if (ob16_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs) != static_cast<int>(net->n_slabs)) {
     ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs,
                   ob16_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs));
@@ -794,14 +571,7 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
   a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = x90_dev;
   a.S = S; a.N = N; a.raw = raw_dev;
   if (comp) {
-    a.comp = comp->mean_dev ? 2 : 1;
-    a.mean = comp->mean_dev; a.std_ = comp->std_; a.lin_step = nsplace::linspace_step_of(-comp->std_, comp->std_, N - 1);
-    a.n_shift = -1;
-    for (int k = 0; k < 31; ++k) if (N == (1 << k)) a.n_shift = k;
-    a.m_chunks = N > 64 ? N / 64 : 0;
-    a.white_bkgd = comp->white_bkgd;
-    a.rgb = comp->rgb_dev; a.rgb_stride = comp->rgb_stride; a.disp = comp->disp_dev; a.disp_stride = comp->disp_stride;
-    a.weights = comp->weights_dev; a.z_out = comp->z_out_dev; a.pts_out = comp->pts_out_dev;
+    nsepi::set_comp_args(a, comp, N);
     if (comp->fix_rec_dev) {
       if (N > 64 || comp->sigma_last_dev) {
         ns::set_error("the selective guard serves rays of one chunk (N <= 64) and excludes the every-ray guard's sigma array");
@@ -809,7 +579,6 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
       }
       a.fix_thr = comp->fix_thr; a.fix_count = comp->fix_count_dev; a.fix_rec = comp->fix_rec_dev;
     }
-    a.sig_last = comp->sigma_last_dev;
   }
   const bool emb = x90_dev != nullptr;
 #ifdef NS_OB16_VARIANT_BUILD   // tools/build_asm_variant.sh: only the kernel under test is instantiated (a 20 s build)

@@ -5,6 +5,7 @@
 // several times the exact-fp32 MFMA path.  A wave owns T = 2 tiles of 16 samples: the hi/lo activation pairs of two
 // tiles fill the registers four plain tiles do.
 #include "ns_common.h"
+#include "ns_comp_epilogue.h"
 #include "ns_mlp_engine.h"
 #include "ns_weights.h"
 
@@ -74,12 +75,33 @@ struct NerfX3Args {
   const uint32_t* count_dev;   // NULL, or the number of samples to evaluate, read by the kernel (<= S: the selective guard pass
                                // launches for its capacity and the device knows how many rays were flagged)
 };
+// ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): the fields of
+// Nerf16Args::comp .. fix_rec (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
+// that form serves 16-bit fields only.
+struct NerfX3CompArgs : NerfX3Args {
+  int comp;
+  int n_shift;
+  const float* mean;
+  float std_, lin_step;
+  int white_bkgd;
+  float* rgb; int64_t rgb_stride;
+  float* disp; int64_t disp_stride;
+  float* weights;
+  float* z_out;
+  float* pts_out;
+  const float* sig_last;
+  int m_chunks, sg_groups;
+  float fix_thr;
+  uint32_t* fix_count;
+  float* fix_rec;
+};
 
 // PROD: the production network (8 x 256, skips = [4], view directions) as straight-line code over the generated layer
-// statements, as in ns_nerf_mlp_ob16.hip
-template <int NKB, bool EMBEDDED, bool PROD = false>   // NKB = W / 32 K-blocks of a hidden layer
-__global__ void __launch_bounds__(kWaves * 64)
-nerf_mlp_x3_kernel(NerfX3Args a) {
+// statements, as in ns_nerf_mlp_ob16.hip.  COMP (Args = NerfX3CompArgs, rays (o, d) in): the samples are placed and composited
+// in the kernel (ns_comp_epilogue.h; a.comp == 0 is not a COMP launch).
+template <int NKB, bool EMBEDDED, bool PROD, bool COMP, class Args>   // NKB = W / 32 K-blocks of a hidden layer
+__device__ __forceinline__ void nerf_x3_body(const Args& a) {
+  static_assert(!(COMP && EMBEDDED), "in-kernel compositing takes rays");
   using M = Mma16F16x3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int T = kT, NWAVES = kWaves, NSB = 2 * NKB;   // 16-row output sub-blocks of a hidden layer
@@ -95,7 +117,8 @@ nerf_mlp_x3_kernel(NerfX3Args a) {
   }
   if (S_ <= 0) return;
 
-  // LDS: [weight ring][bias image][embedding stash: per wave T x 3 blocks x 1 KiB][input staging: per wave 10 x 256 B]
+  // LDS: [weight ring][bias image][embedding stash: per wave T x 3 blocks x 2 KiB][input staging: per wave 10 (COMP: 11) x 256 B]
+  //      [COMP: compositing records, nsepi::Records]
   float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
@@ -110,8 +133,11 @@ nerf_mlp_x3_kernel(NerfX3Args a) {
   };
   auto stash_put = [&](int t, int b, const Block& v) { *stash_at(t, b, 0) = v.hi; *stash_at(t, b, 1) = v.lo; };
   auto stash_get = [&](int t, int b) -> Block { Block v; v.hi = *stash_at(t, b, 0); v.lo = *stash_at(t, b, 1); return v; };
-  // staging: value slot k (0..9) of sample j (0..63) of this wave's group at stage_base + k * 256 + j * 4
-  const uint32_t stage_base = stash_region + NWAVES * (T * 3 * 2048) + static_cast<uint32_t>(wave) * (10 * 256);
+  // staging: value slot k (0..9; COMP: 0..10) of sample j (0..63) of this wave's group at stage_base + k * 256 + j * 4
+  constexpr uint32_t kStageRows = COMP ? 11 : 10;
+  const uint32_t stage_base = stash_region + NWAVES * (T * 3 * 2048) + static_cast<uint32_t>(wave) * (kStageRows * 256);
+  const nsepi::Records<T, NWAVES> rec{stash_region + NWAVES * (T * 3 * 2048) + NWAVES * (kStageRows * 256)};
+  (void)rec;
 
   PipeT ring;
   ring.init(a.stream, smem, a.n_slabs, wave, lane);
@@ -126,7 +152,8 @@ nerf_mlp_x3_kernel(NerfX3Args a) {
   };
   // Inputs of the NEXT group are fetched right after layer 0 of the current one by LDS-DMA (no registers held across
   // the network): lane j of the wave fetches the ten values of the j-th of the wave's 64 consecutive samples.
-  // pts mode: p 0..2, v 7..9;  (o, d, z) mode: o 0..2, d 3..5, z 6, v 7..9.
+  // pts mode: p 0..2, v 7..9;  (o, d, z) mode: o 0..2, d 3..5, z 6, v 7..9;  COMP: slot 6 is the ray's DepthNet depth when
+  // the samples are placed in-kernel (comp == 2), slot 10 the NEXT sample's depth (comp == 1) or the guard pass's sigma.
   auto prefetch = [&](int64_t grp) {
     if constexpr (!EMBEDDED) {
       bool valid;
@@ -142,7 +169,14 @@ nerf_mlp_x3_kernel(NerfX3Args a) {
       } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { put(c, a.o + ray * 3 + c); put(3 + c, a.d + ray * 3 + c); }
-        put(6, a.z + sidx);
+        if constexpr (COMP) {
+          if (a.comp == 2) put(6, a.mean + ray);
+          else put(6, a.z + sidx);
+          if (a.comp == 1) put(10, a.z + (sidx + 1 < S_ ? sidx + 1 : sidx));
+          else if (a.sig_last) put(10, a.sig_last + ray * 4 + 3);
+        } else {
+          put(6, a.z + sidx);
+        }
       }
 if (a.use_viewdirs) {
 #pragma unroll
@@ -155,11 +189,31 @@ if (a.use_viewdirs) {
         static_cast<uintptr_t>(stage_base + slot * 256 + (t * 16 + n) * 4));
   };
 
-  prefetch(blockIdx.x);
+  // group order of a workgroup: a grid stride; COMP: runs of sg consecutive groups (rays of several chunks meet in one workgroup,
+  // see Nerf16Args::m_chunks), then a jump of gridDim.x such runs
+  int sg = 1;
+  if constexpr (COMP) sg = a.sg_groups > 1 ? a.sg_groups : 1;
+  auto group_after = [&](int64_t grp_, int gi_) -> int64_t {
+    if constexpr (COMP) return gi_ + 1 == sg ? grp_ + static_cast<int64_t>(gridDim.x - 1) * sg + 1 : grp_ + 1;
+    else return grp_ + gridDim.x;
+  };
+  const int64_t grp0 = static_cast<int64_t>(blockIdx.x) * sg;
+  prefetch(grp0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+  uint32_t par = 0;      // COMP: parity of the group pass (which {z, dist} record buffer this group writes)
+  int gi = 0;            // COMP: position of the group in its run
+  for (int64_t grp = grp0, nxt_grp = 0; grp < n_groups; grp = nxt_grp, gi = (gi + 1 == sg ? 0 : gi + 1), par ^= 1u) {
+    nxt_grp = group_after(grp, gi);
     Block xe[T][2];   // embedded point (63 -> 64 features); registers for layer 0 only
     asm volatile("" ::: "memory");   // the staged inputs landed several slab steps ago (in-order vmcnt)
+    if constexpr (COMP) {
+      if (a.comp) {   // (wave-uniform) placement and the {z, dist} records, one sample per lane; the tiles read z back below
+        nsepi::place_wave(a, rec, [&](int slot, int i) -> float {
+          return *reinterpret_cast<const float __attribute__((address_space(3)))*>(
+              static_cast<uintptr_t>(stage_base + slot * 256 + i * 4));
+        }, grp, gi, par, wave);
+      }
+    }
     static_for<T>([&](auto t_) {
       constexpr int t = decltype(t_)::value;
       Block ve[1];    // embedded view direction (27 -> 32)
@@ -174,7 +228,9 @@ if (a.use_viewdirs) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) p[c] = staged(t, c);
         } else {
-          const float zz = staged(t, 6);
+          float zz;
+          if constexpr (COMP) zz = a.comp ? (*rec.zd(par, (wave * T + t) * 16 + n)).x : staged(t, 6);
+          else zz = staged(t, 6);
 #pragma unroll
           for (int c = 0; c < 3; ++c) p[c] = staged(t, c) + staged(t, 3 + c) * zz;
         }
@@ -216,7 +272,7 @@ if (a.use_viewdirs) {
     layer_ob16x3<T, NSB, 2, true>(ring, bias, g, hA, last, in_x); convert_last16x3<true, T, NSB>(hA, last); bias += NSB * 16;
     // next group's inputs (clamped to the last sample past the end: loaded, never used); this group's staged values
     // have been consumed (they fed the embeddings above)
-    prefetch(grp + gridDim.x);
+    prefetch(nxt_grp);
     int l = 1;
     if constexpr (PROD) {
       static_assert(NKB == 8 && T == 2 && NWAVES == 4, "the generated streams are W = 256, two split tiles, four waves");
@@ -288,7 +344,21 @@ if (a.use_viewdirs) {
     layer_ob16x3<T, 1, NKB / 2, kNone>(ring, bias, g, hA, last, in_B);
     }
 
-    if (g == 0) {
+    if constexpr (COMP) {
+      const bool comp = a.comp != 0;
+      const int le = nsepi::opaque_lane();      // the lane id of the epilogue (see nsepi::opaque_lane)
+      if (le < 16) {                           // lane group g == 0 holds the outputs
+        static_for<T>([&](auto t_) {
+          constexpr int t = decltype(t_)::value;
+          bool valid;
+          const int64_t sidx = sample_of(grp, t, le, valid);
+          const float4 o4 = make_float4(last[t][0], last[t][1], last[t][2], sigma[t]);
+          if (comp) *rec.raw((wave * T + t) * 16 + le) = nsepi::v4f{o4.x, o4.y, o4.z, o4.w};
+          if (valid && a.raw) reinterpret_cast<float4*>(a.raw)[sidx] = o4;
+        });
+      }
+      nsepi::composite_group(a, rec, comp, grp, gi, par, wave, le);
+    } else if (g == 0) {
       static_for<T>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
         bool valid;
@@ -298,6 +368,18 @@ if (a.use_viewdirs) {
     }
   }
   ring.finish();
+}
+
+template <int NKB, bool EMBEDDED, bool PROD = false>
+__global__ void __launch_bounds__(kWaves * 64)
+nerf_mlp_x3_kernel(NerfX3Args a) {
+  nerf_x3_body<NKB, EMBEDDED, PROD, false>(a);
+}
+// the one-kernel renderer's form (rays in, rgb / disp out; raw, z, pts, weights optional)
+template <int NKB, bool PROD>
+__global__ void __launch_bounds__(kWaves * 64)
+nerf_mlp_x3_comp_kernel(NerfX3CompArgs a) {
+  nerf_x3_body<NKB, false, PROD, true>(a);
 }
 
 int x3_program_slabs(int W, int D, uint32_t skip_mask, int use_viewdirs) {   // two stream chunks (W_hi, W_lo) per K-block
@@ -327,12 +409,41 @@ int launch(NerfX3Args& a, hipStream_t stream) {
   return NS_OK;
 }
 
+// dynamic LDS of the compositing form: ring | bias | embedding stash (hi, lo) | input staging (11 slots) | compositing records
+size_t comp_lds_bytes(int bias_floats) {
+  return static_cast<size_t>(Pipe<Mma16F16x3, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
+         ((static_cast<size_t>(bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * kT * 3 * 2048 +
+         static_cast<size_t>(kWaves) * 11 * 256 + nsepi::Records<kT, kWaves>::kBytes;
+}
+
+template <int NKB, bool PROD>
+int launch_comp(NerfX3CompArgs& a, hipStream_t stream) {
+  const size_t lds = comp_lds_bytes(a.bias_floats);
+  if (lds > 160 * 1024) {
+    ns::set_error("ns_nerf_forward: %zu bytes of LDS needed (too deep a network for the resident bias image)", lds);
+    return NS_E_UNSUPPORTED;
+  }
+  auto kern = nerf_mlp_x3_comp_kernel<NKB, PROD>;
+  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+  const int64_t n_tiles = (a.S + 15) / 16;
+  const int64_t n_groups = (n_tiles + kWaves * kT - 1) / (kWaves * kT);
+  int cus = ns::cu_count();
+  if (cus <= 0) cus = 256;
+  a.sg_groups = nsepi::run_groups(kWaves * kT * 16, a.m_chunks, a.N);
+  const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
+  const int grid = static_cast<int>(n_runs < cus ? n_runs : cus);
+  kern<<<grid, kWaves * 64, lds, stream>>>(a);
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
 }  // namespace
 
-// called by ns_nerf_forward_ob16 for NS_DTYPE_F16X3 handles (arguments validated by its callers)
+// called by ns_nerf_forward_ob16 for NS_DTYPE_F16X3 handles (arguments validated by its callers, comp included: see
+// ns_nerf_can_composite) and by the selective guard's fix-up (count_dev)
 int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
                        const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev) {
+                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp) {
   if (x3_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs) != static_cast<int>(net->n_slabs)) {
     ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs,
                   x3_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs));
@@ -346,8 +457,19 @@ int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float*
   a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = x90_dev;
   a.S = S; a.N = N; a.raw = raw_dev; a.count_dev = count_dev;
   const bool emb = x90_dev != nullptr, wide = net->width == 256;
-  if (wide && net->depth == 8 && net->skip_mask == (1u << 4) && net->use_viewdirs && !ns::debug_flags().generic_kernels)
-    return emb ? launch<8, true, true>(a, stream) : launch<8, false, true>(a, stream);   // the production network
+  const bool prod = wide && net->depth == 8 && net->skip_mask == (1u << 4) && net->use_viewdirs && !ns::debug_flags().generic_kernels;
+  if (comp) {
+    if (comp->fix_rec_dev || count_dev) {
+      ns::set_error("ns_nerf_forward: the selective guard serves 16-bit fields; an f16x3 field takes the every-ray guard");
+      return NS_E_UNSUPPORTED;
+    }
+    NerfX3CompArgs c{};
+    static_cast<NerfX3Args&>(c) = a;
+    nsepi::set_comp_args(c, comp, N);
+    if (prod) return launch_comp<8, true>(c, stream);
+    return wide ? launch_comp<8, false>(c, stream) : launch_comp<4, false>(c, stream);
+  }
+  if (prod) return emb ? launch<8, true, true>(a, stream) : launch<8, false, true>(a, stream);   // the production network
   if (emb) return wide ? launch<8, true>(a, stream) : launch<4, true>(a, stream);
   return wide ? launch<8, false>(a, stream) : launch<4, false>(a, stream);
 }

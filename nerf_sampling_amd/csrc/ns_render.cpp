@@ -8,7 +8,7 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
                          float* raw_dev, hipStream_t stream, const ns_composite_args* comp);
 int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
                        const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev);
+                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
 
 namespace {
 
@@ -194,8 +194,9 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   NS_REQUIRE(a, "null args");
   NS_REQUIRE(a->depthnet && a->nerf, "both networks are required");
   if (!ns_render_fused_supported(a->nerf, a->mode, a->N)) {
-    ns::set_error("ns_render_rays_fused: uniform placement, a 16-bit NeRF handle with view directions and n_samples a power "
-                  "of two in [2, 64] or a multiple of 64 up to 512 are required (mode %d, N %d); use ns_render_rays_depthnet", a->mode, a->N);
+    ns::set_error("ns_render_rays_fused: uniform placement, a bf16, f16 or f16x3 NeRF handle with view directions and n_samples "
+                  "a power of two in [2, 64] or a multiple of 64 up to 512 are required (mode %d, N %d); use ns_render_rays_depthnet",
+                  a->mode, a->N);
     return NS_E_UNSUPPORTED;
   }
   NS_REQUIRE(!a->noise_dev, "uniform placement takes no noise");
@@ -213,9 +214,9 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
   c.weights_dev = out.weights; c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
   // (the fix-up launches the split-operand MLP kernel with a device-side count: another packing of the guard handle, e.g. fp32,
-  // takes the every-ray pass through the generic dispatch)
+  // takes the every-ray pass through the generic dispatch.  An f16x3 field is fp32-grade itself: its guard is the every-ray one)
   const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && a->N <= 64 && a->nerf_guard->dtype == NS_DTYPE_F16X3 &&
-                         a->nerf_guard->layout == 16;
+                         a->nerf_guard->layout == 16 && a->nerf->dtype != NS_DTYPE_F16X3;
   if (selective) {         // the kernel flags the rays itself; their last samples are re-evaluated after it
     c.fix_thr = a->guard_threshold;
     c.fix_count_dev = l.fix_count;
@@ -239,7 +240,7 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   rc = ns_fix_gather(l.fix_rec, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view, l.z_last, stream);
   if (rc != NS_OK) return rc;
   rc = ns_nerf_forward_x3(a->nerf_guard, nullptr, fr.o, fr.d, l.z_last, fr.view, nullptr, r.R, 1, l.raw_last,
-                          ns::as_stream(stream), l.fix_count);
+                          ns::as_stream(stream), l.fix_count, nullptr);
   if (rc != NS_OK) return rc;
   return ns_fix_last_sample(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride, out.disp,
                             out.disp_stride, out.weights, stream);
@@ -268,7 +269,7 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   rc = ns_coarse_z_scalar(a->near_, a->far_, R, Nc, a->lindisp, a->t_rand_dev, l.z_c, stream);
   if (rc != NS_OK) return rc;
   if ((rc = record(a->ev_coarse_begin, stream)) != NS_OK) return rc;
-  // A 16-bit field composites in its own epilogue (Nerf16Args::comp == 1: depths from the z array): raw [R,N,4] -- 16 bytes
+  // A bf16 / f16 / f16x3 field composites in its own epilogue (Nerf16Args::comp == 1: depths from the z array): raw [R,N,4] -- 16 bytes
   // per sample written and read back, 2.6 GB per 800 x 800 frame at 64 + 192 samples -- then never exists.  The coarse
   // pass only yields its weights (its colour goes to a scratch corner of the unused raw_c block).
   const bool chain = ns::debug_flags().hier_chain != 0;
