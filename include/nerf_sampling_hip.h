@@ -265,7 +265,12 @@ int ns_render_rays_fused(const ns_render_args* args, void* stream);
  * sampling, sorted merge, fine pass.  Rays explicit or generated from the camera (o_dev == NULL).
  * Outputs of the FINE pass: rgb [R,3], disp [R] always; z / weights [R,Nc+Nf] and raw [R,Nc+Nf,4] if
  * non-NULL.  t_rand [R,Nc] (stratified jitter) and u [R,Nf] (inverse-CDF draws) are NULL for the
- * deterministic perturb == 0 path.                                                               */
+ * deterministic perturb == 0 path.
+ * The max-weight fine sample (nerf_utils.py:813-819: argmax of the fine weights, first index on ties, NaN the largest):
+ * max_z [R,1], max_w [R,1] and max_rgb [R,3] (sigmoid of the sample's raw rgb), all three or none, bit-identical to
+ * ns_argmax_gather on the call's own weights / z / raw; they need Nf > 0 and a workspace of
+ * ns_hier_max_workspace_bytes(R, Nc, Nf) bytes.  A fine pass that composites in the MLP kernel reduces them in its epilogue;
+ * otherwise ns_argmax_gather runs on the fine arrays (weights into weights_dev, or into the workspace).         */
 typedef struct ns_hier_args {
   const ns_weights* coarse;
   const ns_weights* fine; /* NULL: the coarse network is used for both passes */
@@ -281,7 +286,7 @@ typedef struct ns_hier_args {
   float near_, far_;
   const float* t_rand_dev;
   const float* u_dev;
-  void* workspace_dev; /* ns_hier_workspace_bytes(R, Nc, Nf) bytes, 256-byte aligned */
+  void* workspace_dev; /* ns_hier_workspace_bytes(R, Nc, Nf) bytes (ns_hier_max_workspace_bytes with max_*), 256-byte aligned */
   float* rgb_dev;
   float* disp_dev;
   float* z_dev;
@@ -293,8 +298,13 @@ typedef struct ns_hier_args {
   int64_t disp_stride;
   void* ev_coarse_begin; /* optional hipEvent_t pair around the COARSE-pass MLP kernel */
   void* ev_coarse_end;
+  float* max_z_dev;   /* [R,1] or NULL: the max-weight fine sample (see above) */
+  float* max_w_dev;   /* [R,1] or NULL */
+  float* max_rgb_dev; /* [R,3] or NULL */
 } ns_hier_args;
 int64_t ns_hier_workspace_bytes(int64_t R, int Nc, int Nf);
+/* the workspace of a call with the max-weight sample: ns_hier_workspace_bytes plus one [R, Nc+Nf] fp32 slice (256-aligned) */
+int64_t ns_hier_max_workspace_bytes(int64_t R, int Nc, int Nf);
 int ns_render_rays_hierarchical(const ns_hier_args* args, void* stream);
 
 /* ---- training step of the DepthNet (Trainer.core_optimization_loop, Trainer.py:506-544) -------------

@@ -72,6 +72,7 @@ class HierArgs(C.Structure):
         ("ev_mlp_begin", _p), ("ev_mlp_end", _p),
         ("rgb_stride", _i64), ("disp_stride", _i64),
         ("ev_coarse_begin", _p), ("ev_coarse_end", _p),
+        ("max_z_dev", _p), ("max_w_dev", _p), ("max_rgb_dev", _p),
     ]
 
 
@@ -112,6 +113,7 @@ SIGNATURES = {
     "ns_render_fused_workspace_bytes": (_i64, [_i64]),
     "ns_render_rays_fused": (_i, [C.POINTER(RenderArgs), _p]),
     "ns_hier_workspace_bytes": (_i64, [_i64, _i, _i]),
+    "ns_hier_max_workspace_bytes": (_i64, [_i64, _i, _i]),
     "ns_render_rays_hierarchical": (_i, [C.POINTER(HierArgs), _p]),
     "ns_gemm_strided": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "ns_gemm_fused": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _p, _i64, _p, _p]),

@@ -3,7 +3,7 @@
 // this code with their own group shape.  A group is NWAVES x T tiles of 16 samples = T chunks of 64 consecutive samples; wave w
 // holds samples w * 16 T .. (w + 1) * 16 T - 1 of it, so with T != 4 a chunk straddles waves.
 //
-// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. fix_rec under the same names.
+// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. max_rgb under the same names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +36,12 @@ __device__ __forceinline__ int opaque_lane() {
 // The compositing records in LDS, from byte address `base` on (kBytes): sample i (0 .. GS - 1) of the open group
 //   raw float4 per sample | {z, dist * |d|} float2 per sample, two group parities | sigma of a ray's last sample from the guard
 //   pass, one float per ray of the group, two parities | 128 chunk scalars
+// The chunk scalars, as float offsets:
+//   kCP + c            chunk c's transmittance factor
+//   kCS + 8 c + 0..4   chunk c's five sums;  + 5..7 its max-weight sample (Args::max_w != NULL): weight, z, sigmoid(raw r)
+//   kOPEN + 8 p + 0..5 the open ray's {carry, r, g, b, depth, acc}, parity p;  + 6..7 its max-weight sample so far: weight, z
+//   kMGB + 2 c + 0..1  chunk c's max-weight sample: sigmoid(raw g, b)
+//   kMOPEN + 3 p + 0..2  the open ray's max-weight sample so far: sigmoid(raw r, g, b), parity p
 template <int T, int NWAVES>
 struct Records {
   static constexpr int GS = NWAVES * T * 16;
@@ -43,7 +49,9 @@ struct Records {
   // rays of several chunks: per chunk of the group its transmittance factor (kCP) and its five sums (kCS); the ray that is open
   // at the group's end: {carry, r, g, b, depth, acc}, two parities (kOPEN + 8 par is read, kOPEN + 8 (par ^ 1) written)
   static constexpr int kCP = 0, kCS = 8, kOPEN = 8 + 8 * 8;          // float offsets inside the 128-float scalar block
+  static constexpr int kMGB = kOPEN + 16, kMOPEN = kMGB + 16;
   static_assert(T <= 8, "eight chunks per group at most");
+  static_assert(kMOPEN + 2 * 3 <= 128, "the max-weight sample's slots end inside the 128-float scalar block (kBytes unchanged)");
   uint32_t base;
   __device__ __forceinline__ CrawPtr raw(int i) const { return reinterpret_cast<CrawPtr>(static_cast<uintptr_t>(base + static_cast<uint32_t>(i) * 16u)); }
   __device__ __forceinline__ CzdPtr zd(uint32_t par, int i) const {
@@ -118,6 +126,8 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
                                                 uint32_t par, int wave, int le) {
   constexpr int GS = Records<T, NWAVES>::GS;
   constexpr int kCP = Records<T, NWAVES>::kCP, kCS = Records<T, NWAVES>::kCS, kOPEN = Records<T, NWAVES>::kOPEN;
+  constexpr int kMGB = Records<T, NWAVES>::kMGB, kMOPEN = Records<T, NWAVES>::kMOPEN;
+  const bool amax = a.max_w != nullptr;   // the max-weight sample of every ray (wave-uniform: a kernel argument)
   if (comp && a.m_chunks) {
     // Rays of m = N / 64 chunks (N = 128, 192, ...): a ray's chunks sit on different waves, possibly in different groups
     // of the workgroup's run.  Three phases around two s_barriers, the arithmetic of raw2outputs_kernel's multi-chunk
@@ -179,6 +189,17 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
           *rec.scal(kCS + 8 * c + 0) = A.r; *rec.scal(kCS + 8 * c + 1) = A.g; *rec.scal(kCS + 8 * c + 2) = A.b;
           *rec.scal(kCS + 8 * c + 3) = A.depth; *rec.scal(kCS + 8 * c + 4) = A.acc;
         }
+        if (__builtin_expect(amax, 0)) {   // the chunk's max-weight sample (a ray's chunks are combined in order in phase 3)
+          float best = w;
+          int bi = okc[ci] ? le : nscomp::kNoSample;
+          nscomp::argmax_segment(best, bi, 64);
+          if (bi == le) {   // its own lane records it (the raw record is this group's until the barrier below)
+            const v4f qv = *rec.raw(c * 64 + le);
+            *rec.scal(kCS + 8 * c + 5) = w; *rec.scal(kCS + 8 * c + 6) = zc[ci];
+            *rec.scal(kCS + 8 * c + 7) = nscomp::sigmoid_ieee(qv.x);
+            *rec.scal(kMGB + 2 * c) = nscomp::sigmoid_ieee(qv.y); *rec.scal(kMGB + 2 * c + 1) = nscomp::sigmoid_ieee(qv.z);
+          }
+        }
       }
     });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -198,6 +219,22 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
           tot.r = tot.r + *rec.scal(kCS + 8 * cc); tot.g = tot.g + *rec.scal(kCS + 8 * cc + 1); tot.b = tot.b + *rec.scal(kCS + 8 * cc + 2);
           tot.depth = tot.depth + *rec.scal(kCS + 8 * cc + 3); tot.acc = tot.acc + *rec.scal(kCS + 8 * cc + 4);
         }
+        // the ray's max-weight sample: the open ray's so far, then its chunks of this group in order (a later chunk's samples
+        // have larger indices: it wins only where nscomp::beats says so without the index -- a larger weight, or the first NaN)
+        float mw = 0.0f, mz = 0.0f, mr = 0.0f, mg = 0.0f, mb = 0.0f;
+        if (__builtin_expect(amax, 0)) {
+          if (first < 0) {
+            mw = *rec.scal(kOPEN + 8 * par + 6); mz = *rec.scal(kOPEN + 8 * par + 7);
+            mr = *rec.scal(kMOPEN + 3 * par); mg = *rec.scal(kMOPEN + 3 * par + 1); mb = *rec.scal(kMOPEN + 3 * par + 2);
+          }
+          for (int cc = first < 0 ? 0 : first; cc <= c; ++cc) {
+            const float v = *rec.scal(kCS + 8 * cc + 5);
+            if (cc == first || (v != v ? mw == mw : v > mw)) {
+              mw = v; mz = *rec.scal(kCS + 8 * cc + 6); mr = *rec.scal(kCS + 8 * cc + 7);
+              mg = *rec.scal(kMGB + 2 * cc); mb = *rec.scal(kMGB + 2 * cc + 1);
+            }
+          }
+        }
         if (ends) {
           const int64_t r = (C0 + c) / m;
           if (r * a.N < a.S) {
@@ -206,11 +243,19 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
             float* prgb = a.rgb + r * a.rgb_stride;
             prgb[0] = tot.r; prgb[1] = tot.g; prgb[2] = tot.b;
             a.disp[r * a.disp_stride] = disp;
+            if (amax) {
+              a.max_w[r] = mw; a.max_z[r] = mz;
+              a.max_rgb[r * 3] = mr; a.max_rgb[r * 3 + 1] = mg; a.max_rgb[r * 3 + 2] = mb;
+            }
           }
         } else {                                     // the ray goes on in the workgroup's next group
           const uint32_t np = par ^ 1u;
           *rec.scal(kOPEN + 8 * np) = tot.carry; *rec.scal(kOPEN + 8 * np + 1) = tot.r; *rec.scal(kOPEN + 8 * np + 2) = tot.g;
           *rec.scal(kOPEN + 8 * np + 3) = tot.b; *rec.scal(kOPEN + 8 * np + 4) = tot.depth; *rec.scal(kOPEN + 8 * np + 5) = tot.acc;
+          if (amax) {
+            *rec.scal(kOPEN + 8 * np + 6) = mw; *rec.scal(kOPEN + 8 * np + 7) = mz;
+            *rec.scal(kMOPEN + 3 * np) = mr; *rec.scal(kMOPEN + 3 * np + 1) = mg; *rec.scal(kMOPEN + 3 * np + 2) = mb;
+          }
         }
       }
     }
@@ -222,6 +267,11 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
     // waves, one s_barrier (all four waves reach it: the group loop is workgroup-uniform).
     if constexpr (T == 4) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
     else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // (amax) the lane's sample for the ray's argmax below the switch -- one copy of that code for the six segment widths: its
+    // weight, its index in the ray (kNoSample past the end), depth and raw
+    float mx_w = 0.0f, mx_z = 0.0f;
+    int mx_i = nscomp::kNoSample;
+    float4 mx_q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     auto composite = [&](auto sw_, int c) {
       constexpr int SW = decltype(sw_)::value;
       const int i = c * 64 + le;
@@ -236,6 +286,7 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
       const int sub = le & (SW - 1);
       nscomp::composite_chunk<SW>(A, ok, sub, q, zd.x, zd.y, 1.0f, 0.0f, false, alpha, w, &Tr);
       if (ok && a.weights) a.weights[s] = w;
+      if (__builtin_expect(amax, 0)) { mx_w = w; mx_i = ok ? sub : nscomp::kNoSample; mx_z = zd.x; mx_q = q; }
       nscomp::composite_finish<SW>(A, a.white_bkgd, disp, sub, &tree);
       if (ok && sub == SW - 1) {
         const int64_t r = s / SW;      // N == SW
@@ -260,6 +311,17 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         case 4: composite(std::integral_constant<int, 4>{}, c); break;
         default: composite(std::integral_constant<int, 2>{}, c); break;
       }
+      if (__builtin_expect(amax, 0)) {     // the ray's max-weight sample over its N-lane segment; its own lane writes it
+        float best = mx_w;
+        int bi = mx_i;
+        nscomp::argmax_segment(best, bi, a.N);
+        if (mx_i != nscomp::kNoSample && bi == mx_i) {   // (a segment past the end has no sample: nothing is written)
+          const int64_t r = (grp * GS + c * 64 + le) / a.N;
+          a.max_w[r] = mx_w; a.max_z[r] = mx_z;
+          float* prgb = a.max_rgb + r * 3;
+          prgb[0] = nscomp::sigmoid_ieee(mx_q.x); prgb[1] = nscomp::sigmoid_ieee(mx_q.y); prgb[2] = nscomp::sigmoid_ieee(mx_q.z);
+        }
+      }
     }
   }
 }
@@ -277,6 +339,7 @@ inline void set_comp_args(Args& a, const ns_composite_args* comp, int N) {
   a.rgb = comp->rgb_dev; a.rgb_stride = comp->rgb_stride; a.disp = comp->disp_dev; a.disp_stride = comp->disp_stride;
   a.weights = comp->weights_dev; a.z_out = comp->z_out_dev; a.pts_out = comp->pts_out_dev;
   a.sig_last = comp->sigma_last_dev;
+  a.max_z = comp->max_z_dev; a.max_w = comp->max_w_dev; a.max_rgb = comp->max_rgb_dev;
 }
 // runs of lcm(group samples, N) / group samples consecutive groups (whole rays per run) when rays span several chunks, else 1
 inline int run_groups(int group_samples, int m_chunks, int N) {

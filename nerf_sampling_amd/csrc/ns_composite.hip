@@ -349,17 +349,7 @@ importance_z_wave_kernel(const float* __restrict__ z, const float* __restrict__ 
   }
 }
 
-// nerf_utils.py:813-819: argmax over samples (first index on ties, NaN counts as largest)
-__device__ __forceinline__ bool beats(float v, int i, float bv, int bi) {
-  if (i == 0x7fffffff) return false;
-  if (bi == 0x7fffffff) return true;
-  const bool vn = v != v, bn = bv != bv;
-  if (vn != bn) return vn;
-  if (vn) return i < bi;
-  if (v != bv) return v > bv;
-  return i < bi;
-}
-
+// nerf_utils.py:813-819: argmax over samples in the order of nscomp::beats (first index on ties, NaN counts as largest)
 __global__ void __launch_bounds__(256)
 argmax_gather_kernel(const float* __restrict__ w, const float* __restrict__ z, const float4* __restrict__ raw,
                      int64_t R, int N, float* __restrict__ max_z, float* __restrict__ max_w,
@@ -369,25 +359,20 @@ argmax_gather_kernel(const float* __restrict__ w, const float* __restrict__ z, c
   const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
   for (int64_t r = wave; r < R; r += nwaves) {
     float best = 0.f;
-    int bi = 0x7fffffff;
+    int bi = nscomp::kNoSample;
     for (int i = lane; i < N; i += 64) {
       const float v = w[r * N + i];
-      if (beats(v, i, best, bi)) { best = v; bi = i; }
+      if (nscomp::beats(v, i, best, bi)) { best = v; bi = i; }
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-      const float ov = __shfl_xor(best, m, 64);
-      const int oi = __shfl_xor(bi, m, 64);
-      if (beats(ov, oi, best, bi)) { best = ov; bi = oi; }
-    }
+    nscomp::argmax_segment(best, bi, 64);
     if (lane == 0) {
       if (max_w) max_w[r] = best;
       if (max_z) max_z[r] = z[r * N + bi];
       if (max_rgb) {
         const float4 q = raw[r * N + bi];
-        max_rgb[r * 3] = 1.0f / (1.0f + expf(-q.x));
-        max_rgb[r * 3 + 1] = 1.0f / (1.0f + expf(-q.y));
-        max_rgb[r * 3 + 2] = 1.0f / (1.0f + expf(-q.z));
+        max_rgb[r * 3] = nscomp::sigmoid_ieee(q.x);
+        max_rgb[r * 3 + 1] = nscomp::sigmoid_ieee(q.y);
+        max_rgb[r * 3 + 2] = nscomp::sigmoid_ieee(q.z);
       }
     }
   }

@@ -213,6 +213,35 @@ __device__ __forceinline__ void recomposite_last(RayAccum& A /* in: tree sums, o
   w_out = w;
 }
 
+// ---- the max-weight sample of a ray (nerf_utils.py:813-819: top_indices = weights.argmax(1), then z / weight / sigmoid(raw rgb)
+// at that index): argmax_gather_kernel (ns_composite.hip) and the compositing epilogue (ns_comp_epilogue.h) share these.
+// The order of argmax: first index on ties, NaN counts as the largest value (the first NaN wins); index kNoSample is never
+// chosen.  A total order, so any reduction tree gives the same result.
+constexpr int kNoSample = 0x7fffffff;
+__device__ __forceinline__ bool beats(float v, int i, float bv, int bi) {
+  if (i == kNoSample) return false;
+  if (bi == kNoSample) return true;
+  const bool vn = v != v, bn = bv != bv;
+  if (vn != bn) return vn;
+  if (vn) return i < bi;
+  if (v != bv) return v > bv;
+  return i < bi;
+}
+// (best, bi) of every lane -> the best of its sw-lane segment (sw a power of two <= 64, wave-uniform), on every lane of it
+// (butterfly on ds_bpermute; all 64 lanes active)
+__device__ __forceinline__ void argmax_segment(float& best, int& bi, int sw) {
+  const int lane = static_cast<int>(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+  for (int m = 1; m < sw; m <<= 1) {
+    const int src = (lane ^ m) << 2;
+    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, best)));
+    const int oi = __builtin_amdgcn_ds_bpermute(src, bi);
+    if (beats(ov, oi, best, bi)) { best = ov; bi = oi; }
+  }
+}
+// the colour of the max-weight sample as torch.sigmoid gives it: expf and an IEEE divide (not sample_colour's transcendental-unit
+// form), so that both producers of max_rgb agree bit for bit
+__device__ __forceinline__ float sigmoid_ieee(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // A ray of SEVERAL 64-sample chunks (N > 64): every chunk's sums are reduced on their own and the chunk totals are added in
 // chunk order -- so the chunks of a ray can be evaluated by different waves (the one-kernel renderer) or one after the other
 // (raw2outputs_kernel) and give the same bits.  `tot` (wave-uniform) += the totals of the chunk whose lane shares are in A.

@@ -58,6 +58,11 @@ struct Nerf16Args {
   float fix_thr;
   uint32_t* fix_count;
   float* fix_rec;
+  // the max-weight sample of every ray (nerf_utils.py:813-819), all three or none: max_z, max_w [R] and max_rgb [R,3] get the z,
+  // the weight and sigmoid(raw rgb) of the sample argmax(weights) picks (ns_comp_epilogue.h)
+  float* max_z;
+  float* max_w;
+  float* max_rgb;
 };
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
@@ -573,8 +578,9 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
   if (comp) {
     nsepi::set_comp_args(a, comp, N);
     if (comp->fix_rec_dev) {
-      if (N > 64 || comp->sigma_last_dev) {
-        ns::set_error("the selective guard serves rays of one chunk (N <= 64) and excludes the every-ray guard's sigma array");
+      if (N > 64 || comp->sigma_last_dev || comp->max_w_dev) {
+        ns::set_error("the selective guard serves rays of one chunk (N <= 64) and excludes the every-ray guard's sigma array and "
+                      "the max-weight sample");
         return NS_E_INVALID;
       }
       a.fix_thr = comp->fix_thr; a.fix_count = comp->fix_count_dev; a.fix_rec = comp->fix_rec_dev;

@@ -54,12 +54,15 @@ FusedLayout fused_layout(Carve& ws, int64_t R) {
   return l;
 }
 
-struct HierLayout { RaySlices rays; float *z_c, *raw_c, *w_c, *z_f, *raw_f; };
-HierLayout hier_layout(Carve& ws, int64_t R, int Nc, int Nt) {
+// max_slice: the call produces the max-weight sample -- one more slice at the end, the fine weights of the chain's argmax when
+// the caller takes none (every slice before it stays where it is)
+struct HierLayout { RaySlices rays; float *z_c, *raw_c, *w_c, *z_f, *raw_f, *w_f; };
+HierLayout hier_layout(Carve& ws, int64_t R, int Nc, int Nt, bool max_slice) {
   HierLayout l;
   l.rays = take_rays(ws, R);
   l.z_c = ws.take(R * Nc * 4); l.raw_c = ws.take(R * Nc * 16); l.w_c = ws.take(R * Nc * 4);
   l.z_f = ws.take(R * Nt * 4); l.raw_f = ws.take(R * Nt * 16);
+  l.w_f = max_slice ? ws.take(R * Nt * 4) : nullptr;
   return l;
 }
 
@@ -249,7 +252,14 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
 int64_t ns_hier_workspace_bytes(int64_t R, int Nc, int Nf) {
   if (R < 0 || Nc < 3 || Nf < 0) return 0;
   Carve ws;
-  hier_layout(ws, R, Nc, Nc + Nf);
+  hier_layout(ws, R, Nc, Nc + Nf, false);
+  return ws.total;
+}
+
+int64_t ns_hier_max_workspace_bytes(int64_t R, int Nc, int Nf) {
+  if (R < 0 || Nc < 3 || Nf < 0) return 0;
+  Carve ws;
+  hier_layout(ws, R, Nc, Nc + Nf, true);
   return ws.total;
 }
 
@@ -258,10 +268,13 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   NS_REQUIRE(a->coarse->out_ch == 4 && a->coarse->use_viewdirs && (!a->fine || (a->fine->out_ch == 4 && a->fine->use_viewdirs)),
              "the one-call path composites raw [R,N,4] of networks with view directions");
   NS_REQUIRE(a->Nc >= 3 && a->Nf >= 0, "needs at least 3 coarse samples");
+  const bool max_sample = a->max_z_dev || a->max_w_dev || a->max_rgb_dev;
+  NS_REQUIRE(!max_sample || (a->max_z_dev && a->max_w_dev && a->max_rgb_dev), "max_z, max_w and max_rgb go together");
+  NS_REQUIRE(!max_sample || a->Nf > 0, "the max-weight sample is one of the fine pass: needs n_importance > 0");
   const int Nc = a->Nc, Nt = a->Nc + a->Nf;
   HierLayout l;
   Rays r;
-  int rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = hier_layout(ws, R, Nc, Nt); return l.rays; }, &r, stream);
+  int rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = hier_layout(ws, R, Nc, Nt, max_sample); return l.rays; }, &r, stream);
   if (rc != NS_OK || r.R == 0) return rc;
   const int64_t R = r.R;
   const Outputs out = outputs(a);
@@ -303,6 +316,7 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
     c.white_bkgd = a->white_bkgd;
     c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
     c.weights_dev = out.weights;
+    c.max_z_dev = a->max_z_dev; c.max_w_dev = a->max_w_dev; c.max_rgb_dev = a->max_rgb_dev;   // (epilogue argmax)
     rc = ns_nerf_forward_ob16(fine, nullptr, r.o, r.d, z_f, r.view, nullptr, R * Nt, Nt, a->raw_dev, ns::as_stream(stream), &c);
     if (rc != NS_OK) return rc;
     return record(a->ev_mlp_end, stream);
@@ -310,7 +324,11 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   rc = ns_nerf_forward(fine, nullptr, r.o, r.d, z_f, r.view, R, Nt, raw_f, stream);
   if (rc != NS_OK) return rc;
   if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
-  return composite(out, raw_f, z_f, r.d, R, Nt, a->white_bkgd, stream);
+  Outputs fo = out;
+  if (max_sample && !fo.weights) fo.weights = l.w_f;
+  rc = composite(fo, raw_f, z_f, r.d, R, Nt, a->white_bkgd, stream);
+  if (rc != NS_OK || !max_sample) return rc;
+  return ns_argmax_gather(fo.weights, z_f, raw_f, R, Nt, a->max_z_dev, a->max_w_dev, a->max_rgb_dev, stream);
 }
 
 int ns_event_create(void** ev) {

@@ -40,6 +40,10 @@ struct ns_composite_args {
   float fix_thr;
   uint32_t* fix_count_dev;
   float* fix_rec_dev;
+  // the max-weight sample of every ray (ns_hier_args::max_z_dev ..): all three or none (NULL: not produced)
+  float* max_z_dev;        // [R]
+  float* max_w_dev;        // [R]
+  float* max_rgb_dev;      // [R,3]
 };
 // the selective guard's two small kernels (ns_composite.hip): compact inputs of the flagged rays' last samples for the fp32-grade
 // network; then the flagged pixels from the records and the re-evaluated sigma (raw_c [.,4], element 3)

@@ -242,6 +242,10 @@ def prepare_rays(c2w, c2w_staticcam, use_viewdirs, ndc, H, W, K, near, far, rays
 def _render(batch_fn, H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, **kwargs):
     rays, rays_o, rays_d, sh = prepare_rays(c2w=c2w, c2w_staticcam=c2w_staticcam, use_viewdirs=use_viewdirs,
                                             ndc=ndc, H=H, W=W, K=K, near=near, far=far, rays=rays)
+    if batch_fn is batchify_rays_test:
+        # internal: the scalar bounds every row of the batch carries, for the one-call vanilla pass of render_rays_test (which
+        # then need not read the batch's near / far columns back from the device)
+        kwargs["_near_far"] = (float(near), float(far))
     all_returned = batch_fn(rays, chunk, **kwargs)
     for key in all_returned:
         all_returned[key] = torch.reshape(all_returned[key], list(sh[:-1]) + list(all_returned[key].shape[1:]))
@@ -475,6 +479,39 @@ def _one_call_eligible(depth_network, net, network_query_fn, trainer, viewdirs) 
             and not (torch.is_grad_enabled() and any(p.requires_grad for p in depth_network.parameters())))
 
 
+def _hier_one_call_eligible(network_fn, network_fine, network_query_fn, trainer, viewdirs, N_samples, raw_noise_std,
+                            pytest) -> bool:
+    """sample_as_in_NeRF + argmax_gather of render_rays_test as ONE ns_render_rays_hierarchical call: the standard query function,
+    this package's NeRF modules with view directions, the trainer's own operators, a fine pass, no noise, no gradient."""
+    from .trainers import DepthNetTrainer
+
+    nets = [network_fn] + ([network_fine] if network_fine is not None else [])
+    return (viewdirs is not None and getattr(network_query_fn, "_ns_standard_query", False)
+            and all(isinstance(n, run_nerf_helpers.NeRF) and n.use_viewdirs for n in nets)
+            and all(getattr(type(trainer), f, None) is getattr(DepthNetTrainer, f)
+                    for f in ("raw2outputs", "sample_coarse_points", "sample_fine_points", "run_network"))
+            and int(trainer.N_importance) > 0 and int(N_samples) >= 3 and raw_noise_std == 0 and not pytest
+            and not (torch.is_grad_enabled() and any(p.requires_grad for n in nets for p in n.parameters())))
+
+
+def _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samples, trainer, perturb, lindisp, white_bkgd,
+                      near_far, full):
+    """The fine pass's max-weight sample (and with ``full`` its z / weights / pts / rgb / disp) through one
+    ns_render_rays_hierarchical call: the values sample_as_in_NeRF + argmax_gather give, bit for bit."""
+    R, dev = rays_o.shape[0], rays_o.device
+    # the chain's random draws, in its order: stratified jitter (sample_coarse_points), then the inverse-CDF draws
+    t_rand = torch.rand([R, N_samples], device=dev) if perturb > 0.0 else None
+    u = torch.rand([R, trainer.N_importance], device=dev) if perturb != 0.0 else None
+    out = ops.render_rays_hierarchical(network_fn.packed(), network_fine.packed() if network_fine is not None else None,
+                                       rays=(rays_o, rays_d, viewdirs), n_coarse=int(N_samples),
+                                       n_importance=int(trainer.N_importance), lindisp=bool(lindisp),
+                                       white_bkgd=bool(white_bkgd), near=near_far[0], far=near_far[1], t_rand=t_rand, u=u,
+                                       extras=("z", "weights") if full else False, device=dev, max_sample=True)
+    if full:
+        out["pts"] = ops.points_along_rays(rays_o, rays_d, out["z"])
+    return out
+
+
 def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer, retraw=True, lindisp=False,
                      perturb=0.0, N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0.0,
                      verbose=False, pytest=False, **kwargs):
@@ -488,11 +525,22 @@ def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer
     released_early = False
     to_host = (lambda key, t: sink.put(key, t)) if sink is not None else (lambda key, t: t.cpu())
     if trainer.compare_nerf or trainer.use_nerf_max_pts or trainer.use_full_nerf:
-        (_dens, fine_z, fine_pts, fine_rgb, fine_w, _al, fine_disp, fine_raw) = sample_as_in_NeRF(
-            ray_batch=ray_batch, N_samples=N_samples, network_fn=network_fn, network_fine=network_fine,
-            network_query_fn=network_query_fn, trainer=trainer, perturb=perturb, raw_noise_std=raw_noise_std,
-            lindisp=lindisp, white_bkgd=white_bkgd, pytest=pytest, kwargs=kwargs)
-        max_z_vals, max_weights, max_rgb_map = ops.argmax_gather(fine_w, fine_z, fine_raw)
+        near_far = kwargs.get("_near_far")
+        if near_far is not None and _hier_one_call_eligible(network_fn, network_fine, network_query_fn, trainer, viewdirs,
+                                                            N_samples, raw_noise_std, pytest):
+            # coarse pass, importance sampling, fine pass and the argmax as one C call: no per-sample array of the coarse pass
+            # in HBM, and on 16-bit fields none of the fine pass either (the argmax runs in the MLP kernel's epilogue)
+            v = _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samples, trainer, perturb, lindisp,
+                                  white_bkgd, near_far, trainer.use_full_nerf and not trainer.use_nerf_max_pts)
+            max_z_vals, max_weights, max_rgb_map = v["max_z"], v["max_weights"], v["max_rgb"]
+            fine_rgb, fine_disp = v["rgb"], v["disp"]
+            fine_w, fine_z, fine_pts = v.get("weights"), v.get("z"), v.get("pts")
+        else:
+            (_dens, fine_z, fine_pts, fine_rgb, fine_w, _al, fine_disp, fine_raw) = sample_as_in_NeRF(
+                ray_batch=ray_batch, N_samples=N_samples, network_fn=network_fn, network_fine=network_fine,
+                network_query_fn=network_query_fn, trainer=trainer, perturb=perturb, raw_noise_std=raw_noise_std,
+                lindisp=lindisp, white_bkgd=white_bkgd, pytest=pytest, kwargs=kwargs)
+            max_z_vals, max_weights, max_rgb_map = ops.argmax_gather(fine_w, fine_z, fine_raw)
         max_pts = ops.points_along_rays(rays_o, rays_d, max_z_vals)
         ret["max_z_vals"], ret["max_pts"] = to_host("max_z_vals", max_z_vals), to_host("max_pts", max_pts)
         ret["max_weights"] = to_host("max_weights", max_weights)

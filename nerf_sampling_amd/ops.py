@@ -560,12 +560,20 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
 def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights], *, rays=None, camera=None,
                              n_coarse: int = 64, n_importance: int = 128, lindisp: bool = True,
                              white_bkgd: bool = True, near: float = 2.0, far: float = 6.0,
-                             t_rand: Optional[Tensor] = None, u: Optional[Tensor] = None, extras: bool = False,
+                             t_rand: Optional[Tensor] = None, u: Optional[Tensor] = None, extras=False,
                              workspace: Optional[RenderWorkspace] = None, device="cuda", mlp_events=None,
-                             shard: Optional[Tensor] = None, coarse_events=None):
+                             shard: Optional[Tensor] = None, coarse_events=None, max_sample: bool = False):
     """Vanilla coarse + fine pass (sample_as_in_NeRF) as one C call; returns the FINE pass outputs.
+    ``extras``: True = z / weights [R,Nc+Nf] and raw [R,Nc+Nf,4] too; or a tuple naming the ones wanted, e.g. ("z", "weights").
+    ``max_sample``: also the max-weight fine sample of every ray (nerf_utils.py:813-819), max_z / max_weights [R,1] and
+    max_rgb [R,3], bit-identical to argmax_gather(weights, z, raw) of the same call; needs n_importance > 0.
     ``shard``: as in render_rays_depthnet.  ``mlp_events`` / ``coarse_events``: (begin, end) ops.Event pairs recorded around
     the fine-pass / coarse-pass MLP kernel."""
+    if max_sample and int(n_importance) <= 0:
+        raise ValueError("max_sample: the max-weight sample is one of the fine pass, n_importance must be > 0")
+    names = ("z", "weights", "raw") if extras is True else tuple(extras or ())
+    if not set(names) <= {"z", "weights", "raw"}:
+        raise ValueError(f"extras: True, False or a tuple of 'z', 'weights', 'raw', got {extras!r}")
     lib = _lib.load()
     a = _lib.HierArgs()
     a.coarse = coarse.handle
@@ -578,14 +586,19 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
             t = _dev(t, name)
             keep.append(t)
             setattr(a, name, t.data_ptr())
-    _set_workspace(a, workspace, int(lib.ns_hier_workspace_bytes(R, a.Nc, a.Nf)), device)
+    size_fn = lib.ns_hier_max_workspace_bytes if max_sample else lib.ns_hier_workspace_bytes
+    _set_workspace(a, workspace, int(size_fn(R, a.Nc, a.Nf)), device)
     Nt = a.Nc + a.Nf
     out = _rgb_disp_outputs(a, R, device, shard)
-    if extras:
-        out["z"] = torch.empty((R, Nt), dtype=torch.float32, device=device)
-        out["weights"] = torch.empty((R, Nt), dtype=torch.float32, device=device)
-        out["raw"] = torch.empty((R, Nt, 4), dtype=torch.float32, device=device)
-        a.z_dev, a.weights_dev, a.raw_dev = out["z"].data_ptr(), out["weights"].data_ptr(), out["raw"].data_ptr()
+    for name, shape in (("z", (R, Nt)), ("weights", (R, Nt)), ("raw", (R, Nt, 4))):
+        if name in names:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=device)
+            setattr(a, name + "_dev", out[name].data_ptr())
+    if max_sample:
+        for name, field, shape in (("max_z", "max_z_dev", (R, 1)), ("max_weights", "max_w_dev", (R, 1)),
+                                   ("max_rgb", "max_rgb_dev", (R, 3))):
+            out[name] = torch.empty(shape, dtype=torch.float32, device=device)
+            setattr(a, field, out[name].data_ptr())
     if mlp_events is not None:
         a.ev_mlp_begin, a.ev_mlp_end = mlp_events[0].handle, mlp_events[1].handle
     if coarse_events is not None:
