@@ -171,6 +171,24 @@ int ns_raw2outputs_strided(const float* raw_dev, const float* z_dev, const float
                            int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* acc_dev,
                            float* depth_dev, float* alphas_dev, float* weights_dev, void* stream);
 
+/* Backward of ns_raw2outputs: what torch autograd gives for DepthNetTrainer.raw2outputs (sampling_trainer.py:153-230,
+ * raw2alpha nerf_utils.py:27-42) from the forward's INPUTS -- raw [R,N,4], z [R,N], rays_d [R,3], noise [R,N] or NULL,
+ * white_bkgd, as ns_raw2outputs took them; the forward is re-run inside, nothing of it is saved.  Upstream gradients, any
+ * NULL (that output takes no part in the loss): g_rgb [R,3], g_disp / g_acc / g_depth [R], g_alphas / g_weights [R,N]
+ * (ignored for N == 1, where those outputs are [R,0]).  Outputs, each NULL when not wanted: d_raw [R,N,4] (rgb and sigma
+ * channels; the noise is a constant), d_z [R,N] (through the distances and depth_map), d_rays_d [R,3] (through |d|).
+ * torch's conventions where it has one: relu's subgradient at 0 is 0, torch.maximum splits the gradient in half on a tie
+ * (the disp floor), NaN propagates as through torch's own backward formulas.  N <= 4096.                                 */
+int ns_raw2outputs_backward(const float* raw_dev, const float* z_dev, const float* rays_d_dev, const float* noise_dev,
+                            int64_t R, int N, int white_bkgd, const float* g_rgb_dev, const float* g_disp_dev,
+                            const float* g_acc_dev, const float* g_depth_dev, const float* g_alphas_dev,
+                            const float* g_weights_dev, float* d_raw_dev, float* d_z_dev, float* d_rays_d_dev, void* stream);
+/* Backward of ns_place_samples w.r.t. the mean: d_z [R,N] -> d_mean [R].  Every sample is the mean plus a constant and the
+ * sort only permutes them, so d_mean is the sum of d_z over the ray (the merged mean included); UNIFORM masks the samples
+ * torch.clamp(., 2, 6) clipped (inclusive bounds, and a NaN mean gets 0 there, as torch's clamp backward gives).       */
+int ns_place_samples_backward(int mode, const float* mean_dev, int64_t R, int N, float std_, const float* d_z_dev,
+                              float* d_mean_dev, void* stream);
+
 /* ---- a11 vanilla hierarchical pieces (Trainer.py:579-710, run_nerf_helpers.py:250-293) ------ */
 /* stratified coarse depths: near/far [R]; t_rand [R,N] uniform draws or NULL (perturb==0)    */
 int ns_coarse_z(const float* near_dev, const float* far_dev, int64_t R, int N, int lindisp,

@@ -101,6 +101,8 @@ SIGNATURES = {
     "ns_nerf_forward_embedded": (_i, [_p, _p, _i64, _p, _p]),
     "ns_raw2outputs": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "ns_raw2outputs_strided": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "ns_raw2outputs_backward": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ns_place_samples_backward": (_i, [_i, _p, _i64, _i, _f, _p, _p, _p]),
     "ns_coarse_z": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     "ns_sample_pdf": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     "ns_importance_z": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),

@@ -5,10 +5,12 @@ What needs gradients in the reference's training step (`train_depth_net_only`, r
   * the frozen NeRF: only w.r.t. its input point (one sample per ray at the predicted depth,
     nerf_utils.py:692-715) -- its weights are frozen (Trainer.py:724-728)
   * pts = o + d*z, and the single-sample compositing (rgb = sigmoid(raw rgb), see ns_raw2outputs N == 1)
+Beyond the training step, compositing at any N (Composite: ns_raw2outputs_backward) and sample placement (PlaceSamples:
+ns_place_samples_backward) make the DepthNet branch of render_rays_test differentiable end to end.
 The vanilla coarse+fine pass that produces the target depth runs without gradients on the fused path.
 
 Each torch.autograd.Function below runs its arithmetic in libnerf_sampling_hip.so (ns_gemm_strided,
-ns_act_*, ns_posenc[_backward], ns_points_backward); torch is used for tensor storage and `cat`/slicing.
+ns_act_*, ns_posenc[_backward], ns_points_backward, ns_raw2outputs_backward, ns_place_samples_backward); torch is used for tensor storage and `cat`/slicing.
 Training batches are N_rand = 1024 rays: launch-bound, so layers are individual fp32 GEMMs here rather than
 the fused inference kernels.
 """
@@ -147,6 +149,59 @@ class SingleSampleComposite(torch.autograd.Function):
         draw = torch.zeros((rgb.shape[0], 1, 4), dtype=torch.float32, device=rgb.device)
         draw[:, 0, :3] = g
         return draw, None, None, None
+
+
+# ---- compositing at any N, with or without noise (sampling_trainer.py:153-230) ------------------------------------
+class Composite(torch.autograd.Function):
+    """forward: ns_raw2outputs; backward: ns_raw2outputs_backward, which re-runs the forward from the saved INPUTS (raw, z,
+    rays_d, noise) and returns the gradients of raw, z and rays_d (the noise is a constant).  An output that takes no part in
+    the loss sends no gradient (NULL), not zeros: a zero times an inf of the forward would be a NaN torch does not produce."""
+
+    @staticmethod
+    def forward(ctx, raw: Tensor, z: Tensor, rays_d: Tensor, noise: Optional[Tensor], white_bkgd: bool):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw, z, rays_d, noise)
+        ctx.white_bkgd = bool(white_bkgd)
+        out = ops.raw2outputs(raw, z, rays_d, noise, white_bkgd)
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raw, z, rays_d, noise = ctx.saved_tensors
+        want = ctx.needs_input_grad[:3]
+        if not any(want) or all(g is None for g in grads):
+            return None, None, None, None, None
+        d_raw, d_z, d_d = ops.raw2outputs_backward(raw, z, rays_d, noise, ctx.white_bkgd, grads, want)
+        return d_raw, d_z, d_d, None, None
+
+
+def composite(raw: Tensor, z: Tensor, rays_d: Tensor, noise: Optional[Tensor], white_bkgd: bool):
+    """raw2outputs' six maps (rgb, disp, acc, depth, alphas, weights), differentiable in raw, z and rays_d"""
+    return Composite.apply(raw, z, rays_d, noise, bool(white_bkgd))
+
+
+# ---- sample placement around the predicted depth (utils.py:220-244) --------------------------------------------------
+class PlaceSamples(torch.autograd.Function):
+    """z [R,N] from mean [R] (ns_place_samples, its own draws for the gaussian mode); backward: ns_place_samples_backward."""
+
+    @staticmethod
+    def forward(ctx, mean: Tensor, o: Tensor, d: Tensor, n_samples: int, mode: str, std: float):
+        _, z = ops.place_samples(o, d, mean, n_samples, mode, std, want_pts=False)
+        ctx.save_for_backward(mean)
+        ctx.mode, ctx.std = mode, float(std)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz: Tensor):
+        (mean,) = ctx.saved_tensors
+        return ops.place_samples_backward(mean, dz, ctx.mode, ctx.std), None, None, None, None, None
+
+
+def place_samples(o: Tensor, d: Tensor, mean: Tensor, n_samples: int, mode: str, std: float):
+    """pts [R,N,3], z [R,N] of sample_points_around_mean, differentiable in mean: mean -> z (PlaceSamples) -> pts
+    (PointsAlongRays).  The same kernels as ops.place_samples, so the same values."""
+    z = PlaceSamples.apply(mean.reshape(-1), o, d, n_samples, mode, std)
+    return PointsAlongRays.apply(o, d, z), z
 
 
 # ---- frozen NeRF, gradient w.r.t. the input points -------------------------------------------------------

@@ -252,4 +252,53 @@ __device__ __forceinline__ void add_chunk_totals(RayAccum& tot, RayAccum A) {
   tot.depth = tot.depth + last(A.depth); tot.acc = tot.acc + last(A.acc);
 }
 
+// ---- the backward of compositing (raw2outputs_backward_kernel, ns_composite_bwd.hip)
+// Reverse inclusive scan of affine maps f_i(x) = a_i x + b_i over segments of SW consecutive lanes (SW a power of two <= 64,
+// segments aligned): lane i ends with f_i o f_{i+1} o ... o f_{last lane of its segment} as (a, b).  Lanes past the samples
+// hold the identity (1, 0).  Kogge-Stone toward lower lanes inside the 16-lane rows (row_shl 1, 2, 4, 8: a lane whose source
+// lies past its row keeps the identity), then the row totals: the first lane of every odd row into the even row before it
+// (32-lane segments done), then lane 32 into the lower half.  Those two steps read another row, which row_shl cannot:
+// ds_bpermute.
+constexpr int kRowShl1 = 0x101, kRowShl2 = 0x102, kRowShl4 = 0x104, kRowShl8 = 0x108, kWaveShl1 = 0x130;
+template <int SW>
+__device__ __forceinline__ void seg_scan_affine_rev(float& a, float& b, int lane) {
+  const int sub = lane & (SW - 1);
+  auto compose = [&](float ua, float ub) { b = a * ub + b; a = a * ua; };   // (a, b) o (ua, ub): the later map applied first
+  auto step = [&](auto ctrl_, int dlt) {
+    const float ua = dpp<decltype(ctrl_)::value>(1.0f, a), ub = dpp<decltype(ctrl_)::value>(0.0f, b);
+    if (SW >= 16 || sub + dlt < SW) compose(ua, ub);
+  };
+  if constexpr (SW >= 2) step(std::integral_constant<int, kRowShl1>{}, 1);
+  if constexpr (SW >= 4) step(std::integral_constant<int, kRowShl2>{}, 2);
+  if constexpr (SW >= 8) step(std::integral_constant<int, kRowShl4>{}, 4);
+  if constexpr (SW >= 16) step(std::integral_constant<int, kRowShl8>{}, 8);
+  auto from = [&](int src) {
+    const float ua = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, a)));
+    const float ub = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, b)));
+    return make_float2(ua, ub);
+  };
+  if constexpr (SW >= 32) {
+    const float2 u = from((lane | 15) + 1);
+    if (((lane >> 4) & 1) == 0) compose(u.x, u.y);
+  }
+  if constexpr (SW >= 64) {
+    const float2 u = from(32);
+    if (lane < 32) compose(u.x, u.y);
+  }
+}
+// x of lane i + 1 (lane 63: `old`), and of lane i - 1 (lane 0: `old`)
+__device__ __forceinline__ float from_next_lane(float old, float x) { return dpp<kWaveShl1>(old, x); }
+__device__ __forceinline__ float from_prev_lane(float old, float x) { return dpp<kWaveShr1>(old, x); }
+// x of the last lane of the lane's SW-lane segment, and the sum of x over the segment on every lane of it (butterfly)
+template <int SW>
+__device__ __forceinline__ float seg_last(float x, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((lane | (SW - 1))) << 2, __builtin_bit_cast(int, x)));
+}
+template <int SW>
+__device__ __forceinline__ float seg_sum(float x, int lane) {
+  for (int m = 1; m < SW; m <<= 1)
+    x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ m) << 2, __builtin_bit_cast(int, x)));
+  return x;
+}
+
 }  // namespace nscomp

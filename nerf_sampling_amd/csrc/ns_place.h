@@ -23,11 +23,11 @@ __host__ inline float linspace_step_of(float start, float end, int steps) {
   return steps <= 1 ? 0.0f : (end - start) / static_cast<float>(steps - 1);
 }
 
-// z[j], j = 0 .. steps, of  clip(sort(cat[m + linspace(-std, std, steps), m]), 2, 6)  (steps = n_samples - 1 >= 1).
+// z[j], j = 0 .. steps, of  sort(cat[m + linspace(-std, std, steps), m])  (steps = n_samples - 1 >= 1), before the clip.
 // The grid a_i = m + g_i is non-decreasing, so the mean is merged at its rank p = #{i : a_i < m} instead of sorting:
 // z[j] = a_j for j < p, m for j == p, a_{j-1} for j > p.  "j < p" <=> a_j < m and "j > p" <=> !(a_{j-1} < m), so no rank
-// search is needed.  A NaN mean gives NaN everywhere (the clip would turn it into 2).
-__device__ __forceinline__ float uniform_z(float m, float std_, float step, int steps, int j) {
+// search is needed.
+__device__ __forceinline__ float uniform_z_unclipped(float m, float std_, float step, int steps, int j) {
   float v = m;
   if (j < steps) {
     const float b = m + linspace_step(-std_, std_, step, steps, j);
@@ -37,6 +37,11 @@ __device__ __forceinline__ float uniform_z(float m, float std_, float step, int 
     const float a = m + linspace_step(-std_, std_, step, steps, j - 1);
     if (!(a < m)) v = a;
   }
+  return v;
+}
+// ... and clipped: the sample depths of the uniform mode.  A NaN mean gives NaN everywhere (the clip would turn it into 2).
+__device__ __forceinline__ float uniform_z(float m, float std_, float step, int steps, int j) {
+  float v = uniform_z_unclipped(m, std_, step, steps, j);
   v = fminf(fmaxf(v, 2.0f), 6.0f);  // hard-coded clip, utils.py:240
   return (m != m) ? m : v;
 }

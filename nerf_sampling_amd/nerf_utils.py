@@ -173,10 +173,13 @@ def _batchify(render_fn, rays_flat, chunk, **kwargs):
                 and _one_call_eligible(kwargs.get("depth_network"), net, kwargs.get("network_query_fn"), tr, True)):
             per_ray = 20 * (1 if tr.sampling_mode == "depth_only" else int(tr.n_depth_samples))
             chunk = max(chunk, min(rays_flat.shape[0], _WHOLE_FRAME_BYTES // per_ray))
+    # A frame is rendered for its values: render_rays_test's maps carry a graph back to a trainable DepthNet (call it on a ray
+    # batch for gradients), the frame's chunks are detached so that each chunk's graph is freed with the chunk.
+    frame = render_fn is render_rays_test
     for i in range(0, rays_flat.shape[0], chunk):
         returned = render_fn(rays_flat[i : i + chunk], **kwargs)
         for key in returned:
-            all_returned.setdefault(key, []).append(returned[key])
+            all_returned.setdefault(key, []).append(returned[key].detach() if frame else returned[key])
         if sink is not None:
             sink.advance(min(chunk, rays_flat.shape[0] - i))
     _last_sink = sink if defer else None
@@ -523,7 +526,7 @@ def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer
     # they go asynchronously into the frame's pinned buffers (_HostSink)
     sink = kwargs.get("_host_sink")
     released_early = False
-    to_host = (lambda key, t: sink.put(key, t)) if sink is not None else (lambda key, t: t.cpu())
+    to_host = (lambda key, t: sink.put(key, t.detach())) if sink is not None else (lambda key, t: t.cpu())
     if trainer.compare_nerf or trainer.use_nerf_max_pts or trainer.use_full_nerf:
         near_far = kwargs.get("_near_far")
         if near_far is not None and _hier_one_call_eligible(network_fn, network_fine, network_query_fn, trainer, viewdirs,

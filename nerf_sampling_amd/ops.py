@@ -368,6 +368,42 @@ def raw2outputs(raw: Tensor, z: Tensor, rays_d: Tensor, noise: Optional[Tensor] 
     return rgb, disp, acc, depth, alphas, weights
 
 
+def raw2outputs_backward(raw: Tensor, z: Tensor, rays_d: Tensor, noise: Optional[Tensor], white_bkgd: bool,
+                         grads: Sequence[Optional[Tensor]], want: Sequence[bool] = (True, True, True)):
+    """Backward of raw2outputs from its inputs (ns_raw2outputs_backward re-runs the forward).  grads: the upstream gradients of
+    (rgb, disp, acc, depth, alphas, weights), None where an output takes no part.  want: which of (d_raw, d_z, d_rays_d) to
+    compute.  -> (d_raw [R,N,C] | None, d_z [R,N] | None, d_rays_d [R,3] | None); channels past the fourth get zeros."""
+    lib = _lib.load()
+    C_ = raw.shape[-1]
+    raw4 = raw[..., :4] if C_ > 4 else raw
+    raw4, z, rays_d = _dev(raw4, "raw"), _dev(z, "z_vals"), _dev(rays_d, "rays_d")
+    R, N = z.shape
+    dev = raw4.device
+    g = [None if t is None or t.numel() == 0 else _dev(t, "grad") for t in grads]
+    if noise is not None:
+        noise = _dev(noise, "noise")
+    d_raw = torch.empty((R, N, 4), dtype=torch.float32, device=dev) if want[0] else None
+    d_z = torch.empty((R, N), dtype=torch.float32, device=dev) if want[1] else None
+    d_d = torch.empty((R, 3), dtype=torch.float32, device=dev) if want[2] else None
+    check(lib.ns_raw2outputs_backward(_ptr(raw4), _ptr(z), _ptr(rays_d), _ptr(noise), R, N, int(bool(white_bkgd)),
+                                      *[_ptr(t) for t in g], _ptr(d_raw), _ptr(d_z), _ptr(d_d), _stream(dev)),
+          "ns_raw2outputs_backward")
+    if d_raw is not None and C_ > 4:
+        d_raw = torch.cat([d_raw, torch.zeros((R, N, C_ - 4), dtype=torch.float32, device=dev)], -1)
+    return d_raw, d_z, d_d
+
+
+def place_samples_backward(mean: Tensor, d_z: Tensor, mode: str, std: float) -> Tensor:
+    """d mean [R] of place_samples from d z [R,N] (ns_place_samples_backward)"""
+    lib = _lib.load()
+    mean, d_z = _dev(mean.reshape(-1), "mean"), _dev(d_z, "d_z")
+    R, N = d_z.shape
+    d_mean = torch.empty((R,), dtype=torch.float32, device=mean.device)
+    check(lib.ns_place_samples_backward(_MODES[mode], _ptr(mean), R, N, float(std), _ptr(d_z), _ptr(d_mean),
+                                        _stream(mean.device)), "ns_place_samples_backward")
+    return d_mean
+
+
 # ---- a11 ------------------------------------------------------------------------------------------
 def coarse_z(near: Tensor, far: Tensor, n_samples: int, lindisp: bool, t_rand: Optional[Tensor] = None) -> Tensor:
     lib = _lib.load()

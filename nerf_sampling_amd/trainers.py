@@ -432,14 +432,16 @@ class DepthNetTrainer(BlenderTrainer):
             zeros = torch.zeros((R,), device=raw.device)
             return (torch.zeros((R, 3), device=raw.device), torch.full((R,), 1e10, device=raw.device), zeros,
                     zeros.clone(), density, raw[..., 3].clone(), raw[..., 3].clone())
-        if torch.is_grad_enabled() and raw.requires_grad:
-            if z_vals.shape[-1] != 1 or noise is not None:
-                raise NotImplementedError("autograd through compositing is implemented for the single-sample "
-                                          "training path only (nerf_utils.py:692-715)")
-            from .autograd import SingleSampleComposite
+        if torch.is_grad_enabled() and (raw.requires_grad or z_vals.requires_grad or rays_d.requires_grad):
+            if z_vals.shape[-1] == 1 and noise is None:      # the training step's operator (nerf_utils.py:692-715)
+                from .autograd import SingleSampleComposite
 
-            rgb_map, disp_map, acc_map, depth_map, alphas, weights = SingleSampleComposite.apply(
-                raw, z_vals, rays_d, bool(white_bkgd))
+                rgb_map, disp_map, acc_map, depth_map, alphas, weights = SingleSampleComposite.apply(
+                    raw, z_vals, rays_d, bool(white_bkgd))
+            else:                                            # any N, with or without noise: ns_raw2outputs_backward
+                from .autograd import composite
+
+                rgb_map, disp_map, acc_map, depth_map, alphas, weights = composite(raw, z_vals, rays_d, noise, white_bkgd)
             return rgb_map, disp_map, acc_map, depth_map, density, alphas, weights
         rgb_map, disp_map, acc_map, depth_map, alphas, weights = ops.raw2outputs(raw, z_vals, rays_d, noise, white_bkgd)
         return rgb_map, disp_map, acc_map, depth_map, density, alphas, weights

@@ -86,5 +86,13 @@ def find_intersection_points_with_sphere(origin, direction, sphere_radius):
 
 
 def sample_points_around_mean(rays_o, rays_d, mean, n_samples=32, mode="gaussian", std=0.1):
-    """pts [R,N,3], z_vals [R,N] (utils.py:220-244)."""
+    """pts [R,N,3], z_vals [R,N] (utils.py:220-244).  Under autograd both are differentiable in ``mean``; the rays are not."""
+    if torch.is_grad_enabled():
+        if rays_o.requires_grad or rays_d.requires_grad:
+            raise NotImplementedError("sample_points_around_mean is differentiable in `mean` only: detach rays_o / rays_d "
+                                      "(no gradient reaches the rays on this path)")
+        if mean.requires_grad:
+            from .autograd import place_samples
+
+            return place_samples(rays_o, rays_d, mean, n_samples, mode, std)
     return ops.place_samples(rays_o, rays_d, mean.reshape(-1), n_samples, mode, std)
