@@ -214,7 +214,11 @@ int ns_argmax_gather(const float* weights_dev, const float* z_dev, const float* 
  * rays come either from (o,d,viewdirs) device arrays or, if o_dev is NULL, are generated in
  * place from the camera (rows [row0,row1) of an HxW image).  Runs DepthNet -> placement ->
  * NeRF MLP -> compositing on `stream` with intermediates in the caller-provided workspace.
- * Outputs rgb [R,3], disp [R] always; z/weights/pts (per-sample extras) only if non-NULL.   */
+ * Outputs rgb [R,3], disp [R] always; z/weights/pts (per-sample extras) only if non-NULL.
+ * depth_dev / acc_dev [R] (packed, NULL = not produced): the expected depth sum_i w_i z_i and the opacity sum_i w_i of every
+ * ray, exactly what ns_raw2outputs writes to its depth_dev / acc_dev for the call's own raw, z and rays_d -- acc before the
+ * white-background add, from the guard's sigma under a guard, 0 for N == 1 (depth_only), NaN for a ray that misses the
+ * sphere.  Both renderers produce them; the workspace sizes do not change.                                                */
 typedef struct ns_render_args {
   const ns_weights* depthnet;
   const ns_weights* nerf;
@@ -263,6 +267,8 @@ typedef struct ns_render_args {
    * for bit what the every-ray guard gives wherever |sigma16 - sigma32| < guard_threshold.  The five-launch chain
    * (ns_render_rays_depthnet), and the one-kernel renderer on an F16X3 field, ignore it and guard every ray.              */
   float guard_threshold;
+  float* depth_dev; /* [R] or NULL: expected depth sum_i w_i z_i (see above) */
+  float* acc_dev;   /* [R] or NULL: opacity sum_i w_i, before the white-background add */
 } ns_render_args;
 int64_t ns_render_workspace_bytes(int64_t R, int N);
 int ns_render_rays_depthnet(const ns_render_args* args, void* stream);
@@ -288,7 +294,10 @@ int ns_render_rays_fused(const ns_render_args* args, void* stream);
  * max_z [R,1], max_w [R,1] and max_rgb [R,3] (sigmoid of the sample's raw rgb), all three or none, bit-identical to
  * ns_argmax_gather on the call's own weights / z / raw; they need Nf > 0 and a workspace of
  * ns_hier_max_workspace_bytes(R, Nc, Nf) bytes.  A fine pass that composites in the MLP kernel reduces them in its epilogue;
- * otherwise ns_argmax_gather runs on the fine arrays (weights into weights_dev, or into the workspace).         */
+ * otherwise ns_argmax_gather runs on the fine arrays (weights into weights_dev, or into the workspace).
+ * depth_dev / acc_dev [R] (packed, NULL = not produced): the expected-depth and opacity maps of the FINE pass (of the coarse
+ * pass when Nf == 0), exactly what ns_raw2outputs writes to its depth_dev / acc_dev for that pass's z and raw (acc before the
+ * white-background add).  The workspace sizes do not change.                                                              */
 typedef struct ns_hier_args {
   const ns_weights* coarse;
   const ns_weights* fine; /* NULL: the coarse network is used for both passes */
@@ -316,6 +325,8 @@ typedef struct ns_hier_args {
   int64_t disp_stride;
   void* ev_coarse_begin; /* optional hipEvent_t pair around the COARSE-pass MLP kernel */
   void* ev_coarse_end;
+  float* depth_dev;   /* [R] or NULL: expected depth of the fine pass (see above) */
+  float* acc_dev;     /* [R] or NULL: its opacity */
   float* max_z_dev;   /* [R,1] or NULL: the max-weight fine sample (see above) */
   float* max_w_dev;   /* [R,1] or NULL */
   float* max_rgb_dev; /* [R,3] or NULL */

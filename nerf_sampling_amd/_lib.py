@@ -39,6 +39,7 @@ class RenderArgs(C.Structure):
         ("ev_mlp_begin", _p), ("ev_mlp_end", _p),
         ("rgb_stride", _i64), ("disp_stride", _i64),
         ("nerf_guard", _p), ("guard_threshold", _f),
+        ("depth_dev", _p), ("acc_dev", _p),
     ]
 
 
@@ -72,6 +73,7 @@ class HierArgs(C.Structure):
         ("ev_mlp_begin", _p), ("ev_mlp_end", _p),
         ("rgb_stride", _i64), ("disp_stride", _i64),
         ("ev_coarse_begin", _p), ("ev_coarse_end", _p),
+        ("depth_dev", _p), ("acc_dev", _p),
         ("max_z_dev", _p), ("max_w_dev", _p), ("max_rgb_dev", _p),
     ]
 

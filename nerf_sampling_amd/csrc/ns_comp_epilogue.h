@@ -3,7 +3,7 @@
 // this code with their own group shape.  A group is NWAVES x T tiles of 16 samples = T chunks of 64 consecutive samples; wave w
 // holds samples w * 16 T .. (w + 1) * 16 T - 1 of it, so with T != 4 a chunk straddles waves.
 //
-// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. max_rgb under the same names.
+// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. acc under the same names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -243,6 +243,8 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
             float* prgb = a.rgb + r * a.rgb_stride;
             prgb[0] = tot.r; prgb[1] = tot.g; prgb[2] = tot.b;
             a.disp[r * a.disp_stride] = disp;
+            if (a.depth) a.depth[r] = tot.depth;      // (wave-uniform tests: kernel arguments)
+            if (a.acc) a.acc[r] = tot.acc;            // (finish_totals adds the white background to rgb only)
             if (amax) {
               a.max_w[r] = mw; a.max_z[r] = mz;
               a.max_rgb[r * 3] = mr; a.max_rgb[r * 3 + 1] = mg; a.max_rgb[r * 3 + 2] = mb;
@@ -293,6 +295,8 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         float* prgb = a.rgb + r * a.rgb_stride;
         prgb[0] = A.r; prgb[1] = A.g; prgb[2] = A.b;
         a.disp[r * a.disp_stride] = disp;
+        if (a.depth) a.depth[r] = A.depth;
+        if (a.acc) a.acc[r] = A.acc;
         if (a.fix_rec && __builtin_fabsf(q.w) < a.fix_thr) {      // (a NaN sigma compares false: a NaN ray stays NaN)
           float* rec16 = a.fix_rec + static_cast<size_t>(atomicAdd(a.fix_count, 1u)) * 16;
           reinterpret_cast<float4*>(rec16)[0] = make_float4(tree.r, tree.g, tree.b, tree.depth);
@@ -340,6 +344,7 @@ inline void set_comp_args(Args& a, const ns_composite_args* comp, int N) {
   a.weights = comp->weights_dev; a.z_out = comp->z_out_dev; a.pts_out = comp->pts_out_dev;
   a.sig_last = comp->sigma_last_dev;
   a.max_z = comp->max_z_dev; a.max_w = comp->max_w_dev; a.max_rgb = comp->max_rgb_dev;
+  a.depth = comp->depth_dev; a.acc = comp->acc_dev;
 }
 // runs of lcm(group samples, N) / group samples consecutive groups (whole rays per run) when rays span several chunks, else 1
 inline int run_groups(int group_samples, int m_chunks, int N) {

@@ -520,11 +520,13 @@ fix_gather_kernel(const float* __restrict__ rec, const uint32_t* __restrict__ co
   }
 }
 // the flagged pixels again: tree sums + the last sample's share with the re-evaluated sigma (nscomp::recomposite_last: the very
-// additions composite_finish makes, so a ray whose sigma keeps its sign comes out bit-identical to the every-ray guard)
+// additions composite_finish makes, so a ray whose sigma keeps its sign comes out bit-identical to the every-ray guard); the
+// depth / acc maps, when asked for, are rewritten from the same totals
 __global__ void __launch_bounds__(256)
 fix_last_sample_kernel(const float* __restrict__ rec, const uint32_t* __restrict__ count, int64_t cap, const float4* __restrict__ raw_c,
                        int N, int white_bkgd, float* __restrict__ rgb, int64_t rgb_stride, float* __restrict__ disp_out,
-                       int64_t disp_stride, float* __restrict__ weights) {
+                       int64_t disp_stride, float* __restrict__ weights, float* __restrict__ depth_out,
+                       float* __restrict__ acc_out) {
   int64_t n = static_cast<int64_t>(*count);
   if (n > cap) n = cap;
   for (int64_t s = blockIdx.x * static_cast<int64_t>(256) + threadIdx.x; s < n; s += static_cast<int64_t>(gridDim.x) * 256) {
@@ -537,6 +539,8 @@ fix_last_sample_kernel(const float* __restrict__ rec, const uint32_t* __restrict
     float* p = rgb + r * rgb_stride;
     p[0] = A.r; p[1] = A.g; p[2] = A.b;
     disp_out[r * disp_stride] = disp;
+    if (depth_out) depth_out[r] = A.depth;
+    if (acc_out) acc_out[r] = A.acc;
     if (weights) weights[r * N + (N - 1)] = w;
   }
 }
@@ -552,12 +556,13 @@ int ns_fix_gather(const float* rec_dev, const uint32_t* count_dev, int64_t cap, 
 }
 
 int ns_fix_last_sample(const float* rec_dev, const uint32_t* count_dev, int64_t cap, const float* raw_c, int N, int white_bkgd,
-                       float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev, void* stream) {
+                       float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev,
+                       float* depth_dev, float* acc_dev, void* stream) {
   NS_REQUIRE(rec_dev && count_dev && cap >= 0 && raw_c && N >= 2 && rgb_dev && disp_dev, "bad arguments");
   if (cap == 0) return NS_OK;
   fix_last_sample_kernel<<<ns::ew_grid(cap, 256), 256, 0, ns::as_stream(stream)>>>(
       rec_dev, count_dev, cap, reinterpret_cast<const float4*>(raw_c), N, white_bkgd, rgb_dev, rgb_stride, disp_dev, disp_stride,
-      weights_dev);
+      weights_dev, depth_dev, acc_dev);
   NS_LAUNCH_CHECK();
   return NS_OK;
 }

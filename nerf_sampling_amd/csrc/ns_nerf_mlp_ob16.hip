@@ -63,6 +63,9 @@ struct Nerf16Args {
   float* max_z;
   float* max_w;
   float* max_rgb;
+  // the per-ray expected depth and opacity sums (ns_composite_args::depth_dev / acc_dev): [R] each, or NULL
+  float* depth;
+  float* acc;
 };
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);

@@ -76,7 +76,7 @@ struct NerfX3Args {
                                // launches for its capacity and the device knows how many rays were flagged)
 };
 // ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): the fields of
-// Nerf16Args::comp .. max_rgb (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
+// Nerf16Args::comp .. acc (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
 // that form serves 16-bit fields only.
 struct NerfX3CompArgs : NerfX3Args {
   int comp;
@@ -97,6 +97,8 @@ struct NerfX3CompArgs : NerfX3Args {
   float* max_z;
   float* max_w;
   float* max_rgb;
+  float* depth;
+  float* acc;
 };
 
 // PROD: the production network (8 x 256, skips = [4], view directions) as straight-line code over the generated layer

@@ -90,17 +90,23 @@ int resolve_rays(const Args* a, CarveLayout carve_layout, Rays* r, void* stream)
 }
 
 // The caller's per-ray outputs, strides resolved (0 = packed: 3 / 1).
-struct Outputs { float* rgb; int64_t rgb_stride; float* disp; int64_t disp_stride; float* weights; };
+struct Outputs { float* rgb; int64_t rgb_stride; float* disp; int64_t disp_stride; float* weights; float* depth; float* acc; };
 template <class Args>
 Outputs outputs(const Args* a) {
-  return {a->rgb_dev, a->rgb_stride ? a->rgb_stride : 3, a->disp_dev, a->disp_stride ? a->disp_stride : 1, a->weights_dev};
+  return {a->rgb_dev, a->rgb_stride ? a->rgb_stride : 3, a->disp_dev, a->disp_stride ? a->disp_stride : 1, a->weights_dev,
+          a->depth_dev, a->acc_dev};
 }
 
-// raw [R,N,4] composited into the caller's rgb / disp (/ weights)
+// raw [R,N,4] composited into the caller's rgb / disp (/ weights, depth, acc)
 int composite(const Outputs& out, const float* raw, const float* z, const float* d, int64_t R, int N, int white_bkgd,
               void* stream) {
   return ns_raw2outputs_strided(raw, z, d, nullptr, R, N, white_bkgd, out.rgb, out.rgb_stride, out.disp, out.disp_stride,
-                                nullptr, nullptr, nullptr, out.weights, stream);
+                                out.acc, out.depth, nullptr, out.weights, stream);
+}
+// the per-ray outputs of a pass that composites in the MLP kernel's epilogue
+void set_outputs(ns_composite_args& c, const Outputs& out) {
+  c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
+  c.weights_dev = out.weights; c.depth_dev = out.depth; c.acc_dev = out.acc;
 }
 
 // an optional event (NULL = none) recorded on the stream
@@ -214,8 +220,8 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   const Outputs out = outputs(a);
   ns_composite_args c{};
   c.mean_dev = l.mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
-  c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
-  c.weights_dev = out.weights; c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
+  set_outputs(c, out);
+  c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
   // (the fix-up launches the split-operand MLP kernel with a device-side count: another packing of the guard handle, e.g. fp32,
   // takes the every-ray pass through the generic dispatch.  An f16x3 field is fp32-grade itself: its guard is the every-ray one)
   const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && a->N <= 64 && a->nerf_guard->dtype == NS_DTYPE_F16X3 &&
@@ -246,7 +252,7 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
                           ns::as_stream(stream), l.fix_count, nullptr);
   if (rc != NS_OK) return rc;
   return ns_fix_last_sample(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride, out.disp,
-                            out.disp_stride, out.weights, stream);
+                            out.disp_stride, out.weights, out.depth, out.acc, stream);
 }
 
 int64_t ns_hier_workspace_bytes(int64_t R, int Nc, int Nf) {
@@ -314,8 +320,7 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   if (!chain && ns_nerf_can_composite(fine, Nt)) {
     ns_composite_args c{};
     c.white_bkgd = a->white_bkgd;
-    c.rgb_dev = out.rgb; c.rgb_stride = out.rgb_stride; c.disp_dev = out.disp; c.disp_stride = out.disp_stride;
-    c.weights_dev = out.weights;
+    set_outputs(c, out);
     c.max_z_dev = a->max_z_dev; c.max_w_dev = a->max_w_dev; c.max_rgb_dev = a->max_rgb_dev;   // (epilogue argmax)
     rc = ns_nerf_forward_ob16(fine, nullptr, r.o, r.d, z_f, r.view, nullptr, R * Nt, Nt, a->raw_dev, ns::as_stream(stream), &c);
     if (rc != NS_OK) return rc;

@@ -44,13 +44,17 @@ struct ns_composite_args {
   float* max_z_dev;        // [R]
   float* max_w_dev;        // [R]
   float* max_rgb_dev;      // [R,3]
+  // the per-ray expected depth sum_i w_i z_i and opacity sum_i w_i (ns_render_args::depth_dev / acc_dev), each NULL when not wanted
+  float* depth_dev;        // [R]
+  float* acc_dev;          // [R]
 };
 // the selective guard's two small kernels (ns_composite.hip): compact inputs of the flagged rays' last samples for the fp32-grade
 // network; then the flagged pixels from the records and the re-evaluated sigma (raw_c [.,4], element 3)
 int ns_fix_gather(const float* rec_dev, const uint32_t* count_dev, int64_t cap, const float* o_dev, const float* d_dev,
                   const float* view_dev, float* o_c, float* d_c, float* view_c, float* z_c, void* stream);
 int ns_fix_last_sample(const float* rec_dev, const uint32_t* count_dev, int64_t cap, const float* raw_c, int N, int white_bkgd,
-                       float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev, void* stream);
+                       float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev,
+                       float* depth_dev, float* acc_dev, void* stream);
 // internal helpers of the guard pass (ns_rays.hip, ns_composite.hip)
 int ns_place_last_sample(const float* mean_dev, int64_t R, int N, float std_, float* z_last_dev, void* stream);
 int ns_patch_sigma_last(float* raw_dev, const float* raw_last_dev, int64_t R, int N, void* stream);

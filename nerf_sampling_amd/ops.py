@@ -520,10 +520,30 @@ def _rgb_disp_outputs(a, R: int, device, shard: Optional[Tensor]):
     return {"rgb": shard[:R, :3], "disp": shard[:R, 3]}
 
 
+def _extras_names(extras, per_sample: Tuple[str, ...]) -> Tuple[str, ...]:
+    """``extras`` of a one-call renderer -> the names asked for: True = its per-sample arrays, False / None = none, or a tuple
+    drawn from those and the per-ray maps "depth" / "acc"."""
+    if isinstance(extras, (bool, int, np.bool_)):
+        return per_sample if extras else ()
+    names = tuple(extras or ())
+    allowed = per_sample + ("depth", "acc")
+    if not set(names) <= set(allowed):
+        raise ValueError(f"extras: True, False or a tuple of {', '.join(repr(n) for n in allowed)}, got {extras!r}")
+    return names
+
+
+def _per_ray_maps(a, names, R: int, device, out: dict) -> None:
+    """The expected-depth and opacity maps [R] asked for in ``names`` (RenderArgs / HierArgs depth_dev / acc_dev)."""
+    for name in ("depth", "acc"):
+        if name in names:
+            out[name] = torch.empty((R,), dtype=torch.float32, device=device)
+            setattr(a, name + "_dev", out[name].data_ptr())
+
+
 def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=None, camera=None,
                          n_samples: int, mode: str, std: float, noise: Optional[Tensor] = None,
                          near: float = 2.0, far: float = 6.0, sphere_radius: float = 2.0,
-                         white_bkgd: bool = True, extras: bool = False, workspace: Optional[RenderWorkspace] = None,
+                         white_bkgd: bool = True, extras=False, workspace: Optional[RenderWorkspace] = None,
                          device="cuda", mlp_events=None, shard: Optional[Tensor] = None,
                          one_kernel: Optional[bool] = None, guard: Optional[PackedWeights] = None,
                          guard_threshold: Optional[float] = None):
@@ -531,6 +551,9 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
 
     rays = (o, d, viewdirs) device tensors, or camera = (H, W, K, c2w, row0, row1) to generate
     the rays on the device.  Returns dict(rgb [R,3], disp [R], and with extras z/weights/pts).
+    ``extras``: True = z [R,N], weights [R,N] and pts [R,N,3]; or a tuple naming the ones wanted from "z", "weights", "pts",
+    "depth", "acc" -- depth / acc [R] are the expected-depth and opacity maps (acc before the white background), bit for bit
+    what raw2outputs returns for the call's own raw and z; per-ray, so they cost no per-sample traffic.
     ``shard``: a contiguous fp32 [>= R, 4] device tensor; the compositing kernel then writes (r, g, b, disp) of ray i
     straight into shard[i] (the unit parallel.FrameRenderer all-gathers) and rgb / disp are returned as views of it.
     ``one_kernel``: None (default) = ns_render_rays_fused -- placement, MLP and compositing in ONE persistent kernel, per-sample
@@ -546,15 +569,17 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     rays whose own sigma of the last sample lies within it of zero are re-evaluated, after the kernel, on a compacted list
     (the same bits as the every-ray guard wherever |sigma16 - sigma32| stays below it); 0 = every ray, before the kernel.
     """
+    names = _extras_names(extras, ("z", "weights", "pts"))
     lib = _lib.load()
     a = _lib.RenderArgs()
     a.depthnet, a.nerf = depthnet.handle, nerf.handle
     if rays is not None and rays[0].shape[0] == 0:     # empty batch: nothing to launch
         dev0, n0 = rays[0].device, (1 if mode == "depth_only" else int(n_samples))
         out = {"rgb": torch.empty((0, 3), device=dev0), "disp": torch.empty((0,), device=dev0)}
-        if extras:
-            out.update(z=torch.empty((0, n0), device=dev0), weights=torch.empty((0, 0 if n0 == 1 else n0), device=dev0),
-                       pts=torch.empty((0, n0, 3), device=dev0))
+        empty = dict(z=torch.empty((0, n0), device=dev0), weights=torch.empty((0, 0 if n0 == 1 else n0), device=dev0),
+                     pts=torch.empty((0, n0, 3), device=dev0), depth=torch.empty((0,), device=dev0),
+                     acc=torch.empty((0,), device=dev0))
+        out.update((k, empty[k]) for k in names)
         return out
     R, device, keep = _set_ray_source(a, rays, camera, device)
     N = 1 if mode == "depth_only" else int(n_samples)
@@ -574,13 +599,13 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     nbytes = int(lib.ns_render_fused_workspace_bytes(R) if use_fused else lib.ns_render_workspace_bytes(R, N))
     _set_workspace(a, workspace, nbytes, device)
     out = _rgb_disp_outputs(a, R, device, shard)
-    if extras:
-        out["z"] = torch.empty((R, N), dtype=torch.float32, device=device)
-        # one sample: the reference's weights are [R, 0] (its dists are empty) and ns_raw2outputs writes none
-        out["weights"] = torch.empty((R, 0 if N == 1 else N), dtype=torch.float32, device=device)
-        out["pts"] = torch.empty((R, N, 3), dtype=torch.float32, device=device)
-        a.z_dev, a.pts_dev = out["z"].data_ptr(), out["pts"].data_ptr()
-        a.weights_dev = out["weights"].data_ptr() if N > 1 else None
+    # one sample: the reference's weights are [R, 0] (its dists are empty) and ns_raw2outputs writes none
+    for name, shape in (("z", (R, N)), ("weights", (R, 0 if N == 1 else N)), ("pts", (R, N, 3))):
+        if name in names:
+            out[name] = torch.empty(shape, dtype=torch.float32, device=device)
+            if out[name].numel():
+                setattr(a, name + "_dev", out[name].data_ptr())
+    _per_ray_maps(a, names, R, device, out)
     if mlp_events is not None:
         a.ev_mlp_begin, a.ev_mlp_end = mlp_events[0].handle, mlp_events[1].handle
     if guard is not None:
@@ -600,16 +625,16 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
                              workspace: Optional[RenderWorkspace] = None, device="cuda", mlp_events=None,
                              shard: Optional[Tensor] = None, coarse_events=None, max_sample: bool = False):
     """Vanilla coarse + fine pass (sample_as_in_NeRF) as one C call; returns the FINE pass outputs.
-    ``extras``: True = z / weights [R,Nc+Nf] and raw [R,Nc+Nf,4] too; or a tuple naming the ones wanted, e.g. ("z", "weights").
+    ``extras``: True = z / weights [R,Nc+Nf] and raw [R,Nc+Nf,4] too; or a tuple naming the ones wanted, e.g. ("z", "weights"),
+    from those and "depth" / "acc": the fine pass's (the coarse pass's when n_importance == 0) expected-depth and opacity maps
+    [R], bit for bit what raw2outputs returns for that pass's z and raw.
     ``max_sample``: also the max-weight fine sample of every ray (nerf_utils.py:813-819), max_z / max_weights [R,1] and
     max_rgb [R,3], bit-identical to argmax_gather(weights, z, raw) of the same call; needs n_importance > 0.
     ``shard``: as in render_rays_depthnet.  ``mlp_events`` / ``coarse_events``: (begin, end) ops.Event pairs recorded around
     the fine-pass / coarse-pass MLP kernel."""
     if max_sample and int(n_importance) <= 0:
         raise ValueError("max_sample: the max-weight sample is one of the fine pass, n_importance must be > 0")
-    names = ("z", "weights", "raw") if extras is True else tuple(extras or ())
-    if not set(names) <= {"z", "weights", "raw"}:
-        raise ValueError(f"extras: True, False or a tuple of 'z', 'weights', 'raw', got {extras!r}")
+    names = _extras_names(extras, ("z", "weights", "raw"))
     lib = _lib.load()
     a = _lib.HierArgs()
     a.coarse = coarse.handle
@@ -630,6 +655,7 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
         if name in names:
             out[name] = torch.empty(shape, dtype=torch.float32, device=device)
             setattr(a, name + "_dev", out[name].data_ptr())
+    _per_ray_maps(a, names, R, device, out)
     if max_sample:
         for name, field, shape in (("max_z", "max_z_dev", (R, 1)), ("max_weights", "max_w_dev", (R, 1)),
                                    ("max_rgb", "max_rgb_dev", (R, 3))):
