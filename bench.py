@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N rank processes, one per GPU)
     python bench.py ... --dump-outputs DIR                 (also writes the last timed frame: DIR/rgb.npy, DIR/disp.npy)
+    python bench.py ... --full                             (also the legs below that run outside the timed steps)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one full 800x800 frame of the reference's spiral render path (pose k of 40): ray generation,
@@ -15,12 +16,13 @@ ground-truth scene of nerf_sampling_amd/analytic_scene.py (tools/fit_scene.py; w
 the realistic case, the only one a scene PSNR exists for; "lego_synth" = seeded random weights (a conditioning stress
 test: its density crosses zero on a fifth of the rays).  The timed arithmetic is identical for both.
 
-Rank 0 prints ONE JSON line.  Beside the contract's fields it carries: `roofline` (dominant kernel, HIP events inside the
-timed region), `cpu_baseline` (the oracle on the host cores over a band of the same frame), the accuracy of the timed
-dtype against that same oracle pass (all rays first; then diagnostics that isolate the reference's last-sample step rule),
-`scene_psnr` (oracle vs build against the analytic ground truth: north_star's 0.05 dB bar), `other_configs` (the
-parity-grade dtypes and the other BASELINE shapes, a few steps each) and `api_path` (the mirrored reference API with its
-host copies).  None of those legs runs inside the timed region.
+Rank 0 prints ONE JSON line.  Beside the contract's fields it carries `roofline` (dominant kernel, HIP events inside the
+timed region).  A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  With --full
+(N = 1, depthnet mode) the line also carries `cpu_baseline` (the oracle on the host cores over a band of the same frame),
+the accuracy of the timed dtype against that same oracle pass (all rays first; then diagnostics that isolate the
+reference's last-sample step rule), `scene_psnr` (oracle vs build against the analytic ground truth: north_star's 0.05 dB
+bar), `other_configs` (the parity-grade dtypes and the other BASELINE shapes, a few steps each) and `api_path` (the
+mirrored reference API with its host copies).  None of those legs runs inside the timed region.
 """
 
 import argparse
@@ -46,15 +48,19 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--scene", default="shapes_fit", choices=["shapes_fit", "lego_synth"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-rows", type=int, default=50, help="rows of the frame timed on the CPU (x 800 rays)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline, the accuracy and scene-PSNR checks, the other "
+                         "configs and the API path (N = 1, depthnet mode); without it the run stops at the JSON line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and every leg after it")
+    ap.add_argument("--cpu-rows", type=int, default=50, help="rows of the frame timed on the CPU (x 800 rays), with --full")
     ap.add_argument("--mode", default="depthnet", choices=["depthnet", "full_nerf"],
                     help="depthnet = BASELINE configs[1] (headline); full_nerf = configs[2], vanilla 64+128 coarse+fine")
     ap.add_argument("--api-path", dest="api_path", action="store_true", default=True,
-                    help="also time nerf_utils.render_test (the mirrored reference API with per-chunk host copies)")
+                    help="with --full, also time nerf_utils.render_test (the mirrored reference API with per-chunk host copies)")
     ap.add_argument("--no-api-path", dest="api_path", action="store_false")
     ap.add_argument("--other-configs", dest="other_configs", action="store_true", default=True,
-                    help="also run f16x3 / f32 at the headline shape, configs[2] (vanilla 64+128) and the configs[4] shape")
+                    help="with --full, also run f16x3 / f32 at the headline shape, configs[2] (vanilla 64+128) and the "
+                         "configs[4] shape")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false")
     ap.add_argument("--chain", action="store_true", help="render with the five-launch chain (ns_render_rays_depthnet) instead of "
                     "the one-kernel renderer (ns_render_rays_fused): same bits, for A/B timing")
@@ -739,7 +745,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline and args.mode == "depthnet":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "depthnet":
             mid = H // 2
             rows = (max(0, mid - args.cpu_rows // 2), min(H, mid - args.cpu_rows // 2 + args.cpu_rows))
             pose_k = args.warmup % 40

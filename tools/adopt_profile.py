@@ -1,11 +1,12 @@
 """Copy the summaries of one tools/profile_round.sh run into profiles/ under a prefix (the judged, committed copies):
-    python tools/adopt_profile.py r03u r03c"""
+    python tools/adopt_profile.py r03u r03c          (reads $PROFILE_OUT/r03u, default build/profiles/r03u)"""
 import glob
+import os
 import shutil
 import sys
 
 tag, pre = sys.argv[1:3]
-src, dst = f"gpurun_out/{tag}", "profiles"
+src, dst = os.path.join(os.environ.get("PROFILE_OUT", "build/profiles"), tag), "profiles"
 one = lambda pat: sorted(glob.glob(f"{src}/{pat}"))[0]  # noqa: E731
 shutil.copy(f"{src}/traffic_nerf_mlp.json", f"{dst}/{pre}_traffic_nerf_mlp.json")
 shutil.copy(f"{src}/per_launch_means.json", f"{dst}/{pre}_pmc_per_launch_means.json")
