@@ -284,6 +284,27 @@ int ns_render_rays_depthnet(const ns_render_args* args, void* stream);
 int ns_render_fused_supported(const ns_weights* nerf, int mode, int N);
 int64_t ns_render_fused_workspace_bytes(int64_t R);
 int ns_render_rays_fused(const ns_render_args* args, void* stream);
+/* The one-kernel renderer with forward-mode tangents in the DepthNet depth m of every ray.  In uniform placement every sample
+ * depth is m + a constant, clipped to [2, 6], so a ray's composited outputs depend on m alone and their Jacobian is six numbers
+ * per ray, carried through placement, encoding, field and compositing in the same kernel: nothing per sample is stored, and the
+ * gradient of a loss in rgb / disp / depth / acc w.r.t. m is sum_k g_k J_k per ray.  The conventions are those of torch
+ * autograd through ns_place_samples -> the NeRF -> ns_raw2outputs (ns_place_samples_backward's clip mask, relu'(0) = 0, half of
+ * torch.maximum's tangent on a tie); a zero tangent contributes exactly 0, so a ray without a depth tangent (a NaN mean, every
+ * sample clipped) has J = 0.  rgb / disp / depth / acc are bit-identical to ns_render_rays_fused on the same handle and mean.
+ * Supported (ns_render_tangent_supported != 0): NS_MODE_UNIFORM, an F16X3 NeRF handle with view directions, N as in
+ * ns_render_fused_supported; both ray sources, the rgb / disp strides, depth_dev / acc_dev.  Not supported (NS_E_UNSUPPORTED
+ * or NS_E_INVALID before any launch): nerf_guard, z_dev / weights_dev / pts_dev, noise, a 16-bit field.  Workspace:
+ * ns_render_tangent_workspace_bytes(R) bytes, 256-byte aligned.                                                         */
+typedef struct ns_tangent_args {
+  const float* mean_dev; /* [R] DepthNet depth supplied by the caller, or NULL: run args->depthnet as ns_render_rays_fused does */
+  float* d_rgb_dev;      /* [R,3] d rgb / d mean, or NULL */
+  float* d_disp_dev;     /* [R] */
+  float* d_depth_dev;    /* [R] */
+  float* d_acc_dev;      /* [R] */
+} ns_tangent_args;
+int ns_render_tangent_supported(const ns_weights* nerf, int mode, int N);
+int64_t ns_render_tangent_workspace_bytes(int64_t R);
+int ns_render_rays_fused_tangent(const ns_render_args* args, const ns_tangent_args* tangent, void* stream);
 
 /* ---- a11 as one call: sample_as_in_NeRF (nerf_utils.py:497-611) = coarse pass, inverse-CDF importance
  * sampling, sorted merge, fine pass.  Rays explicit or generated from the camera (o_dev == NULL).

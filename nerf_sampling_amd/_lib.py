@@ -43,6 +43,15 @@ class RenderArgs(C.Structure):
     ]
 
 
+class TangentArgs(C.Structure):
+    """struct ns_tangent_args"""
+
+    _fields_ = [
+        ("mean_dev", _p),
+        ("d_rgb_dev", _p), ("d_disp_dev", _p), ("d_depth_dev", _p), ("d_acc_dev", _p),
+    ]
+
+
 class GemmProblem(C.Structure):
     """struct ns_gemm_problem"""
 
@@ -116,6 +125,9 @@ SIGNATURES = {
     "ns_render_fused_supported": (_i, [_p, _i, _i]),
     "ns_render_fused_workspace_bytes": (_i64, [_i64]),
     "ns_render_rays_fused": (_i, [C.POINTER(RenderArgs), _p]),
+    "ns_render_tangent_supported": (_i, [_p, _i, _i]),
+    "ns_render_tangent_workspace_bytes": (_i64, [_i64]),
+    "ns_render_rays_fused_tangent": (_i, [C.POINTER(RenderArgs), C.POINTER(TangentArgs), _p]),
     "ns_hier_workspace_bytes": (_i64, [_i64, _i, _i]),
     "ns_hier_max_workspace_bytes": (_i64, [_i64, _i, _i]),
     "ns_render_rays_hierarchical": (_i, [C.POINTER(HierArgs), _p]),

@@ -388,13 +388,20 @@ class DepthNetFunction(torch.autograd.Function):
         return (None, None, None, None, None, None, *grads)
 
 
-def depthnet_forward_train(net, o: Tensor, d: Tensor) -> Tensor:
-    n, _width = net._train_shape()
+def depthnet_params(net) -> List[Tensor]:
+    """The DepthNet's parameters in DepthNetFunction's order: [w, b] of the origin, direction and intersection branches, the
+    trunk, the head."""
     mods = (list(net.origin_layers) + list(net.direction_layers) + list(net.intersection_layers)
             + [m for m in net.cat_layers if isinstance(m, torch.nn.Linear)] + [net.to_depth[0]])
     params = []
     for m in mods:
         params += [m.weight, m.bias]
+    return params
+
+
+def depthnet_forward_train(net, o: Tensor, d: Tensor) -> Tensor:
+    n, _width = net._train_shape()
+    params = depthnet_params(net)
     return DepthNetFunction.apply(_dev(o, "rays_o"), _dev(d, "rays_d"), float(net.near), float(net.far),
                                   float(net.sphere_radius.reshape(-1)[0]), n, *params)
 
@@ -547,3 +554,79 @@ class HipAdam(torch.optim.Adam):
                                        float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                        int(st["step"].item()), _stream(p.device)), "ns_adam_step")
         return None
+
+
+# ---- the one-kernel renderer, differentiable in the DepthNet's depth (ns_render_rays_fused_tangent) ------------------------
+class DepthNetTangentRender(torch.autograd.Function):
+    """rgb, disp, depth, acc of rays through DepthNet -> uniform placement -> a frozen f16x3 field -> compositing, rendered in
+    chunks by the tangent kernel; differentiable in the DepthNet's parameters.  The kernel returns each ray's Jacobian
+    J = d{rgb, disp, depth, acc} / d mean beside its outputs, so the backward is d mean = sum_k g_k J_k per ray, then the DepthNet
+    is run again chunk by chunk through DepthNetFunction and its gradients summed: what is held between forward and backward is
+    J (six floats per ray); in the backward, one chunk's DepthNet activations."""
+
+    @staticmethod
+    def forward(ctx, o: Tensor, d: Tensor, viewdirs: Tensor, cfg: dict, *params: Tensor):
+        net, nerf, chunk = cfg["depth_net"], cfg["nerf"], cfg["chunk"]
+        outs = {k: [] for k in ("rgb", "disp", "depth", "acc")}
+        jac = {k: [] for k in outs}
+        for s in range(0, o.shape[0], chunk):
+            sl = slice(s, s + chunk)
+            mean = depthnet_forward_train(net, o[sl], d[sl]).reshape(-1)
+            out, J = ops.render_rays_depthnet_tangent(mean, nerf, rays=(o[sl], d[sl], viewdirs[sl]), n_samples=cfg["n_samples"],
+                                                      std=cfg["std"], extras=("depth", "acc"), white_bkgd=cfg["white_bkgd"])
+            for k in outs:
+                outs[k].append(out[k])
+                jac[k].append(J[k])
+        ctx.cfg, ctx.n_params = cfg, len(params)
+        ctx.jac = {k: torch.cat(v) for k, v in jac.items()}
+        ctx.save_for_backward(o, d, *params)
+        return tuple(torch.cat(outs[k]) for k in ("rgb", "disp", "depth", "acc"))
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_depth, g_acc):
+        o, d, *params = ctx.saved_tensors
+        J = ctx.jac
+        d_mean = torch.zeros((o.shape[0],), dtype=torch.float32, device=o.device)
+        if g_rgb is not None:
+            d_mean += (g_rgb * J["rgb"]).sum(-1)
+        for g, k in ((g_disp, "disp"), (g_depth, "depth"), (g_acc, "acc")):
+            if g is not None:
+                d_mean += g.reshape(-1) * J[k]
+        net, chunk = ctx.cfg["depth_net"], ctx.cfg["chunk"]
+        grads = [torch.zeros_like(p) for p in params]
+        for s in range(0, o.shape[0], chunk):
+            sl = slice(s, s + chunk)
+            with torch.enable_grad():
+                mean = depthnet_forward_train(net, o[sl], d[sl]).reshape(-1)
+                gs = torch.autograd.grad(mean, params, d_mean[sl], allow_unused=True)
+            for acc, g in zip(grads, gs):
+                if g is not None:
+                    acc += g
+        return (None, None, None, None, *grads)
+
+
+def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n_samples: int, std: float, chunk: int = 65536,
+                                   white_bkgd: bool = True):
+    """DepthNet -> sample_points_around_mean("uniform") -> frozen NeRF -> raw2outputs on the one-kernel renderer, differentiable
+    in ``depth_net``'s parameters: dict(rgb [R,3], disp, depth, acc [R]) with a grad_fn (DepthNetTangentRender).  ``nerf``: an
+    "f16x3" NeRF handle; ``rays`` = (o, d, viewdirs) device tensors or ``camera`` = (H, W, K, c2w, row0, row1); ``chunk`` rays
+    per DepthNet pass.  The depth is DepthNetFunction's (the training step's), so the gradients are those of the autograd chain
+    PlaceSamples -> NerfInputGrad -> Composite, without its per-sample arrays."""
+    if getattr(nerf, "dtype", None) != "f16x3":
+        raise NotImplementedError(f"the differentiable renderer needs an f16x3 NeRF handle, got {getattr(nerf, 'dtype', None)}")
+    if not ops._tangent_samples_ok(int(n_samples)):
+        raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {n_samples}")
+    if (rays is None) == (camera is None):
+        raise ValueError("exactly one of rays= and camera= is required")
+    if int(chunk) < 1:
+        raise ValueError("chunk must be >= 1")
+    if rays is None:
+        H, W, K, c2w, row0, row1 = camera
+        rays = ops.get_rays(H, W, K, c2w, row0, row1)
+    o, d, v = (_dev(t, n) for t, n in zip(rays, ("rays_o", "rays_d", "viewdirs")))
+    depth_net._train_shape()          # (raises for shapes the layer-by-layer path does not cover)
+    params = depthnet_params(depth_net)
+    cfg = dict(depth_net=depth_net, nerf=nerf, chunk=int(chunk), n_samples=int(n_samples), std=float(std),
+               white_bkgd=bool(white_bkgd))
+    rgb, disp, depth, acc = DepthNetTangentRender.apply(o, d, v, cfg, *params)
+    return {"rgb": rgb, "disp": disp, "depth": depth, "acc": acc}

@@ -9,6 +9,9 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
 int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
                        const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
                        float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
+int ns_nerf_forward_x3_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev, int64_t R,
+                               int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth, float* d_acc,
+                               hipStream_t stream);
 
 namespace {
 
@@ -51,6 +54,14 @@ FusedLayout fused_layout(Carve& ws, int64_t R) {
   l.fix_count = reinterpret_cast<uint32_t*>(ws.take(256));   // the selective guard: counter, 64-byte records, compacted rays
   l.fix_rec = ws.take(R * 64);
   l.fix_rays = take_rays(ws, R);
+  return l;
+}
+
+struct TangentLayout { RaySlices rays; float* mean; };
+TangentLayout tangent_layout(Carve& ws, int64_t R) {
+  TangentLayout l;
+  l.rays = take_rays(ws, R);
+  l.mean = ws.take(R * 4);            // the DepthNet depth, when the caller supplies none
   return l;
 }
 
@@ -253,6 +264,53 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   if (rc != NS_OK) return rc;
   return ns_fix_last_sample(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride, out.disp,
                             out.disp_stride, out.weights, out.depth, out.acc, stream);
+}
+
+// ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_nerf_mlp_x3_tan.hip): the rays' Jacobians
+// d {rgb, disp, depth, acc} / d mean beside the forward's outputs
+int ns_render_tangent_supported(const ns_weights* nerf, int mode, int N) {
+  return nerf && nerf->dtype == NS_DTYPE_F16X3 && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
+}
+
+int64_t ns_render_tangent_workspace_bytes(int64_t R) {
+  if (R < 0) return 0;
+  Carve ws;
+  tangent_layout(ws, R);
+  return ws.total;
+}
+
+int ns_render_rays_fused_tangent(const ns_render_args* a, const ns_tangent_args* t, void* stream) {
+  NS_REQUIRE(a && t, "null args");
+  NS_REQUIRE(a->nerf, "the NeRF handle is required");
+  NS_REQUIRE(t->mean_dev || a->depthnet, "a DepthNet handle or the caller's mean is required");
+  if (!ns_render_tangent_supported(a->nerf, a->mode, a->N)) {
+    ns::set_error("ns_render_rays_fused_tangent: uniform placement, an f16x3 NeRF handle with view directions and n_samples a "
+                  "power of two in [2, 64] or a multiple of 64 up to 512 are required (mode %d, N %d)", a->mode, a->N);
+    return NS_E_UNSUPPORTED;
+  }
+  NS_REQUIRE(!a->noise_dev, "uniform placement takes no noise");
+  if (a->nerf_guard || a->z_dev || a->weights_dev || a->pts_dev) {
+    ns::set_error("ns_render_rays_fused_tangent: no guard pass and no per-sample outputs (z, weights, pts)");
+    return NS_E_UNSUPPORTED;
+  }
+  TangentLayout l;
+  Rays r;
+  int rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = tangent_layout(ws, R); return l.rays; }, &r, stream);
+  if (rc != NS_OK || r.R == 0) return rc;
+  const float* mean = t->mean_dev;
+  if (!mean) {
+    rc = ns_depthnet_forward(a->depthnet, r.o, r.d, r.R, a->near_, a->far_, a->sphere_radius, l.mean, stream);
+    if (rc != NS_OK) return rc;
+    mean = l.mean;
+  }
+  ns_composite_args c{};
+  c.mean_dev = mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
+  set_outputs(c, outputs(a));
+  if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
+  rc = ns_nerf_forward_x3_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
+                                  t->d_acc_dev, ns::as_stream(stream));
+  if (rc != NS_OK) return rc;
+  return record(a->ev_mlp_end, stream);
 }
 
 int64_t ns_hier_workspace_bytes(int64_t R, int Nc, int Nf) {

@@ -618,6 +618,67 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     return out
 
 
+def _tangent_samples_ok(n: int) -> bool:
+    return (2 <= n <= 64 and n & (n - 1) == 0) or (64 < n <= 512 and n % 64 == 0)
+
+
+def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=None, camera=None, n_samples: int,
+                                 std: float, extras=(), near: float = 2.0, far: float = 6.0, sphere_radius: float = 2.0,
+                                 white_bkgd: bool = True, workspace: Optional[RenderWorkspace] = None, device="cuda",
+                                 mlp_events=None):
+    """The one-kernel renderer with forward-mode tangents in every ray's DepthNet depth (ns_render_rays_fused_tangent).
+
+    ``depthnet_or_mean``: a packed DepthNet (its depth is computed as render_rays_depthnet does) or a device tensor [R] of
+    depths.  ``nerf``: an "f16x3" NeRF handle.  Uniform placement, n_samples a power of two in [2, 64] or a multiple of 64
+    up to 512.  Returns (out, J): out = dict(rgb [R,3], disp [R], and "depth" / "acc" [R] if named in ``extras``), bit for bit
+    those of render_rays_depthnet(one_kernel=True) on the same handle and depth; J = dict(rgb [R,3], disp, depth, acc [R]), the
+    derivatives of those maps w.r.t. the depth of their ray -- what torch autograd of place_samples -> the field ->
+    raw2outputs gives, per ray."""
+    names = _extras_names(extras, ())
+    if not isinstance(nerf, PackedWeights) or nerf.dtype != "f16x3":
+        raise NotImplementedError(f"tangents need an f16x3 NeRF handle, got {getattr(nerf, 'dtype', type(nerf).__name__)}")
+    N = int(n_samples)
+    if not _tangent_samples_ok(N):
+        raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {N}")
+    if (rays is None) == (camera is None):
+        raise ValueError("exactly one of rays= and camera= is required")
+    if isinstance(depthnet_or_mean, PackedWeights):
+        if depthnet_or_mean.kind != "depthnet":
+            raise TypeError("depthnet_or_mean: a packed DepthNet or a depth tensor [R]")
+        mean = None
+    elif isinstance(depthnet_or_mean, Tensor):
+        mean = _dev(depthnet_or_mean.detach().reshape(-1), "mean")
+        R_ = rays[0].shape[0] if rays is not None else (camera[5] - camera[4]) * camera[1]
+        if mean.shape[0] != R_:
+            raise ValueError(f"mean has {mean.shape[0]} depths for {R_} rays")
+    else:
+        raise TypeError("depthnet_or_mean: a packed DepthNet or a depth tensor [R]")
+    lib = _lib.load()
+    a = _lib.RenderArgs()
+    t = _lib.TangentArgs()
+    a.nerf = nerf.handle
+    if mean is None:
+        a.depthnet = depthnet_or_mean.handle
+    R, device, _keep = _set_ray_source(a, rays, camera, device)
+    if mean is not None:
+        t.mean_dev = mean.data_ptr()
+    a.mode, a.N, a.std_ = _lib.MODE_UNIFORM, N, float(std)
+    a.near_, a.far_, a.sphere_radius, a.white_bkgd = float(near), float(far), float(sphere_radius), int(bool(white_bkgd))
+    out = {"rgb": torch.empty((R, 3), dtype=torch.float32, device=device), "disp": torch.empty((R,), dtype=torch.float32, device=device)}
+    J = {"rgb": torch.empty((R, 3), dtype=torch.float32, device=device)}
+    J.update((k, torch.empty((R,), dtype=torch.float32, device=device)) for k in ("disp", "depth", "acc"))
+    _per_ray_maps(a, names, R, device, out)
+    if R == 0:
+        return out, J
+    a.rgb_dev, a.disp_dev = out["rgb"].data_ptr(), out["disp"].data_ptr()
+    t.d_rgb_dev, t.d_disp_dev, t.d_depth_dev, t.d_acc_dev = (J[k].data_ptr() for k in ("rgb", "disp", "depth", "acc"))
+    _set_workspace(a, workspace, int(lib.ns_render_tangent_workspace_bytes(R)), device)
+    if mlp_events is not None:
+        a.ev_mlp_begin, a.ev_mlp_end = mlp_events[0].handle, mlp_events[1].handle
+    check(lib.ns_render_rays_fused_tangent(C.byref(a), C.byref(t), _stream(device)), "ns_render_rays_fused_tangent")
+    return out, J
+
+
 def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights], *, rays=None, camera=None,
                              n_coarse: int = 64, n_importance: int = 128, lindisp: bool = True,
                              white_bkgd: bool = True, near: float = 2.0, far: float = 6.0,
