@@ -291,9 +291,13 @@ int ns_render_rays_fused(const ns_render_args* args, void* stream);
  * autograd through ns_place_samples -> the NeRF -> ns_raw2outputs (ns_place_samples_backward's clip mask, relu'(0) = 0, half of
  * torch.maximum's tangent on a tie); a zero tangent contributes exactly 0, so a ray without a depth tangent (a NaN mean, every
  * sample clipped) has J = 0.  rgb / disp / depth / acc are bit-identical to ns_render_rays_fused on the same handle and mean.
- * Supported (ns_render_tangent_supported != 0): NS_MODE_UNIFORM, an F16X3 NeRF handle with view directions, N as in
+ * What J means depends on the field.  On an F16X3 handle it is the fp32-grade Jacobian of that chain.  On an F16 handle it is
+ * the derivative carried through that field's 16-bit arithmetic: the field's weights and activations are fp16 and so is the
+ * tangent of every layer (relu' taken from the fp32 pre-activation), so J is the Jacobian of the f16 field, which differs from the
+ * fp32-grade one where the field's rounding moves a kink.
+ * Supported (ns_render_tangent_supported != 0): NS_MODE_UNIFORM, an F16X3 or F16 NeRF handle with view directions, N as in
  * ns_render_fused_supported; both ray sources, the rgb / disp strides, depth_dev / acc_dev.  Not supported (NS_E_UNSUPPORTED
- * or NS_E_INVALID before any launch): nerf_guard, z_dev / weights_dev / pts_dev, noise, a 16-bit field.  Workspace:
+ * or NS_E_INVALID before any launch): nerf_guard, z_dev / weights_dev / pts_dev, noise, a BF16 or F32 field.  Workspace:
  * ns_render_tangent_workspace_bytes(R) bytes, 256-byte aligned.                                                         */
 typedef struct ns_tangent_args {
   const float* mean_dev; /* [R] DepthNet depth supplied by the caller, or NULL: run args->depthnet as ns_render_rays_fused does */

@@ -558,7 +558,7 @@ class HipAdam(torch.optim.Adam):
 
 # ---- the one-kernel renderer, differentiable in the DepthNet's depth (ns_render_rays_fused_tangent) ------------------------
 class DepthNetTangentRender(torch.autograd.Function):
-    """rgb, disp, depth, acc of rays through DepthNet -> uniform placement -> a frozen f16x3 field -> compositing, rendered in
+    """rgb, disp, depth, acc of rays through DepthNet -> uniform placement -> a frozen f16x3 (or f16) field -> compositing, rendered in
     chunks by the tangent kernel; differentiable in the DepthNet's parameters.  The kernel returns each ray's Jacobian
     J = d{rgb, disp, depth, acc} / d mean beside its outputs, so the backward is d mean = sum_k g_k J_k per ray, then the DepthNet
     is run again chunk by chunk through DepthNetFunction and its gradients summed: what is held between forward and backward is
@@ -573,7 +573,8 @@ class DepthNetTangentRender(torch.autograd.Function):
             sl = slice(s, s + chunk)
             mean = depthnet_forward_train(net, o[sl], d[sl]).reshape(-1)
             out, J = ops.render_rays_depthnet_tangent(mean, nerf, rays=(o[sl], d[sl], viewdirs[sl]), n_samples=cfg["n_samples"],
-                                                      std=cfg["std"], extras=("depth", "acc"), white_bkgd=cfg["white_bkgd"])
+                                                      std=cfg["std"], extras=("depth", "acc"), white_bkgd=cfg["white_bkgd"],
+                                                      approximate=cfg["approximate"])
             for k in outs:
                 outs[k].append(out[k])
                 jac[k].append(J[k])
@@ -606,13 +607,23 @@ class DepthNetTangentRender(torch.autograd.Function):
 
 
 def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n_samples: int, std: float, chunk: int = 65536,
-                                   white_bkgd: bool = True):
+                                   white_bkgd: bool = True, approximate: bool = False):
     """DepthNet -> sample_points_around_mean("uniform") -> frozen NeRF -> raw2outputs on the one-kernel renderer, differentiable
     in ``depth_net``'s parameters: dict(rgb [R,3], disp, depth, acc [R]) with a grad_fn (DepthNetTangentRender).  ``nerf``: an
     "f16x3" NeRF handle; ``rays`` = (o, d, viewdirs) device tensors or ``camera`` = (H, W, K, c2w, row0, row1); ``chunk`` rays
     per DepthNet pass.  The depth is DepthNetFunction's (the training step's), so the gradients are those of the autograd chain
-    PlaceSamples -> NerfInputGrad -> Composite, without its per-sample arrays."""
-    if getattr(nerf, "dtype", None) != "f16x3":
+    PlaceSamples -> NerfInputGrad -> Composite, without its per-sample arrays.
+
+    ``approximate=True`` (keyword only) also accepts an "f16" NeRF handle.  The Jacobian is then the derivative carried through
+    the field's 16-bit arithmetic (ops.render_rays_depthnet_tangent): the maps are the f16 one-kernel forward's, and the DepthNet
+    gradients are those of the f16 field -- measured, a cosine of at least 0.9989 with autograd through a model of that field, and
+    of 0.979 .. 0.99996 with the f16x3 path's on lego_synth and a fitted-scene band, as close as the f16 field itself comes
+    (tests/test_gpu_render_tangent16.py).  bf16 and f32 handles are refused either way."""
+    dtypes = ("f16x3", "f16") if approximate else ("f16x3",)
+    if getattr(nerf, "dtype", None) not in dtypes:
+        if approximate:
+            raise NotImplementedError("the differentiable renderer needs an f16x3 or f16 NeRF handle, got "
+                                      f"{getattr(nerf, 'dtype', None)}")
         raise NotImplementedError(f"the differentiable renderer needs an f16x3 NeRF handle, got {getattr(nerf, 'dtype', None)}")
     if not ops._tangent_samples_ok(int(n_samples)):
         raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {n_samples}")
@@ -627,6 +638,6 @@ def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n
     depth_net._train_shape()          # (raises for shapes the layer-by-layer path does not cover)
     params = depthnet_params(depth_net)
     cfg = dict(depth_net=depth_net, nerf=nerf, chunk=int(chunk), n_samples=int(n_samples), std=float(std),
-               white_bkgd=bool(white_bkgd))
+               white_bkgd=bool(white_bkgd), approximate=bool(approximate))
     rgb, disp, depth, acc = DepthNetTangentRender.apply(o, d, v, cfg, *params)
     return {"rgb": rgb, "disp": disp, "depth": depth, "acc": acc}

@@ -12,6 +12,9 @@ int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float*
 int ns_nerf_forward_x3_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev, int64_t R,
                                int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth, float* d_acc,
                                hipStream_t stream);
+int ns_nerf_forward_ob16_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev,
+                                 int64_t R, int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth,
+                                 float* d_acc, hipStream_t stream);
 
 namespace {
 
@@ -266,10 +269,10 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
                             out.disp_stride, out.weights, out.depth, out.acc, stream);
 }
 
-// ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_nerf_mlp_x3_tan.hip): the rays' Jacobians
-// d {rgb, disp, depth, acc} / d mean beside the forward's outputs
+// ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_nerf_mlp_x3_tan.hip for an f16x3 field,
+// ns_nerf_mlp_ob16_tan.hip for an f16 one): the rays' Jacobians d {rgb, disp, depth, acc} / d mean beside the forward's outputs
 int ns_render_tangent_supported(const ns_weights* nerf, int mode, int N) {
-  return nerf && nerf->dtype == NS_DTYPE_F16X3 && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
+  return nerf && (nerf->dtype == NS_DTYPE_F16X3 || nerf->dtype == NS_DTYPE_F16) && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
 }
 
 int64_t ns_render_tangent_workspace_bytes(int64_t R) {
@@ -284,7 +287,7 @@ int ns_render_rays_fused_tangent(const ns_render_args* a, const ns_tangent_args*
   NS_REQUIRE(a->nerf, "the NeRF handle is required");
   NS_REQUIRE(t->mean_dev || a->depthnet, "a DepthNet handle or the caller's mean is required");
   if (!ns_render_tangent_supported(a->nerf, a->mode, a->N)) {
-    ns::set_error("ns_render_rays_fused_tangent: uniform placement, an f16x3 NeRF handle with view directions and n_samples a "
+    ns::set_error("ns_render_rays_fused_tangent: uniform placement, an f16x3 or f16 NeRF handle with view directions and n_samples a "
                   "power of two in [2, 64] or a multiple of 64 up to 512 are required (mode %d, N %d)", a->mode, a->N);
     return NS_E_UNSUPPORTED;
   }
@@ -307,8 +310,12 @@ int ns_render_rays_fused_tangent(const ns_render_args* a, const ns_tangent_args*
   c.mean_dev = mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
   set_outputs(c, outputs(a));
   if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
-  rc = ns_nerf_forward_x3_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
-                                  t->d_acc_dev, ns::as_stream(stream));
+  if (a->nerf->dtype == NS_DTYPE_F16X3)
+    rc = ns_nerf_forward_x3_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
+                                    t->d_acc_dev, ns::as_stream(stream));
+  else
+    rc = ns_nerf_forward_ob16_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
+                                      t->d_acc_dev, ns::as_stream(stream));
   if (rc != NS_OK) return rc;
   return record(a->ev_mlp_end, stream);
 }

@@ -625,7 +625,7 @@ def _tangent_samples_ok(n: int) -> bool:
 def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=None, camera=None, n_samples: int,
                                  std: float, extras=(), near: float = 2.0, far: float = 6.0, sphere_radius: float = 2.0,
                                  white_bkgd: bool = True, workspace: Optional[RenderWorkspace] = None, device="cuda",
-                                 mlp_events=None):
+                                 mlp_events=None, approximate: bool = False):
     """The one-kernel renderer with forward-mode tangents in every ray's DepthNet depth (ns_render_rays_fused_tangent).
 
     ``depthnet_or_mean``: a packed DepthNet (its depth is computed as render_rays_depthnet does) or a device tensor [R] of
@@ -633,10 +633,23 @@ def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=
     up to 512.  Returns (out, J): out = dict(rgb [R,3], disp [R], and "depth" / "acc" [R] if named in ``extras``), bit for bit
     those of render_rays_depthnet(one_kernel=True) on the same handle and depth; J = dict(rgb [R,3], disp, depth, acc [R]), the
     derivatives of those maps w.r.t. the depth of their ray -- what torch autograd of place_samples -> the field ->
-    raw2outputs gives, per ray."""
+    raw2outputs gives, per ray.
+
+    ``approximate=True`` (keyword only) also accepts an "f16" NeRF handle, one of the renderer's production fields.  J is then
+    the derivative carried through that field's 16-bit arithmetic: the field's weights and activations are fp16, and so is the
+    tangent of every layer, so J is the Jacobian of the f16 field, not the fp32-grade Jacobian of the chain.  Against autograd
+    of a model of the same f16 field the error of J is ~1e-3 of its column's RMS at the median or below; against the f16x3 kernel
+    it is 10 .. 100 x larger, because the f16 field's rounding moves ReLU and opacity kinks.  The DepthNet gradients of
+    autograd.render_depthnet_differentiable keep a cosine of at least 0.9989 with the same f16 field's and of 0.979 .. 0.99996
+    with the f16x3 path's, as the f16 field itself does (tests/test_gpu_render_tangent16.py).  The outputs
+    are those of the f16 one-kernel forward bit for bit.  bf16 and f32 handles are refused either way."""
     names = _extras_names(extras, ())
-    if not isinstance(nerf, PackedWeights) or nerf.dtype != "f16x3":
-        raise NotImplementedError(f"tangents need an f16x3 NeRF handle, got {getattr(nerf, 'dtype', type(nerf).__name__)}")
+    ok_dtypes = ("f16x3", "f16") if approximate else ("f16x3",)
+    if not isinstance(nerf, PackedWeights) or nerf.dtype not in ok_dtypes:
+        got = getattr(nerf, "dtype", type(nerf).__name__)
+        if approximate:
+            raise NotImplementedError(f"tangents need an f16x3 or f16 NeRF handle, got {got}")
+        raise NotImplementedError(f"tangents need an f16x3 NeRF handle, got {got}")
     N = int(n_samples)
     if not _tangent_samples_ok(N):
         raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {N}")
