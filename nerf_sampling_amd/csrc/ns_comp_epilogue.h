@@ -3,7 +3,7 @@
 // this code with their own group shape.  A group is NWAVES x T tiles of 16 samples = T chunks of 64 consecutive samples; wave w
 // holds samples w * 16 T .. (w + 1) * 16 T - 1 of it, so with T != 4 a chunk straddles waves.
 //
-// Args (Nerf16Args, NerfX3CompArgs) carries the fields of Nerf16Args::comp .. acc under the same names.
+// Args (Nerf16Args, NerfX3CompArgs, nstan::TanArgs) carries the fields of nsepi::CompFields under the same names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,31 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 typedef v4f __attribute__((address_space(3))) * CrawPtr;
 typedef v2f __attribute__((address_space(3))) * CzdPtr;
 typedef float __attribute__((address_space(3))) * CsigPtr;
+
+// The compositing fields of a kernel's argument struct, which place_wave / composite_group / set_comp_args read by name
+// (Nerf16Args, ns_nerf_mlp_ob16.hip, spells them out among its own fields and documents each)
+struct CompFields {
+  int comp;
+  int n_shift;
+  const float* mean;
+  float std_, lin_step;
+  int white_bkgd;
+  float* rgb; int64_t rgb_stride;
+  float* disp; int64_t disp_stride;
+  float* weights;
+  float* z_out;
+  float* pts_out;
+  const float* sig_last;
+  int m_chunks, sg_groups;
+  float fix_thr;
+  uint32_t* fix_count;
+  float* fix_rec;
+  float* max_z;
+  float* max_w;
+  float* max_rgb;
+  float* depth;
+  float* acc;
+};
 
 // The lane id as a value the compiler cannot hoist: everything the compositing code derives from the lane (LDS record
 // addresses per tile, the scan's lane predicates for six segment widths) would otherwise be computed ONCE before the

@@ -75,31 +75,10 @@ struct NerfX3Args {
   const uint32_t* count_dev;   // NULL, or the number of samples to evaluate, read by the kernel (<= S: the selective guard pass
                                // launches for its capacity and the device knows how many rays were flagged)
 };
-// ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): the fields of
-// Nerf16Args::comp .. acc (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
+// ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): nsepi::CompFields, the fields
+// of Nerf16Args::comp .. acc (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
 // that form serves 16-bit fields only.
-struct NerfX3CompArgs : NerfX3Args {
-  int comp;
-  int n_shift;
-  const float* mean;
-  float std_, lin_step;
-  int white_bkgd;
-  float* rgb; int64_t rgb_stride;
-  float* disp; int64_t disp_stride;
-  float* weights;
-  float* z_out;
-  float* pts_out;
-  const float* sig_last;
-  int m_chunks, sg_groups;
-  float fix_thr;
-  uint32_t* fix_count;
-  float* fix_rec;
-  float* max_z;
-  float* max_w;
-  float* max_rgb;
-  float* depth;
-  float* acc;
-};
+struct NerfX3CompArgs : NerfX3Args, nsepi::CompFields {};
 
 // PROD: the production network (8 x 256, skips = [4], view directions) as straight-line code over the generated layer
 // statements, as in ns_nerf_mlp_ob16.hip.  COMP (Args = NerfX3CompArgs, rays (o, d) in): the samples are placed and composited

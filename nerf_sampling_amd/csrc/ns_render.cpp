@@ -269,8 +269,9 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
                             out.disp_stride, out.weights, out.depth, out.acc, stream);
 }
 
-// ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_nerf_mlp_x3_tan.hip for an f16x3 field,
-// ns_nerf_mlp_ob16_tan.hip for an f16 one): the rays' Jacobians d {rgb, disp, depth, acc} / d mean beside the forward's outputs
+// ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_tangent.h, instantiated by
+// ns_nerf_mlp_x3_tan.hip for an f16x3 field and by ns_nerf_mlp_ob16_tan.hip for an f16 one): the rays' Jacobians
+// d {rgb, disp, depth, acc} / d mean beside the forward's outputs
 int ns_render_tangent_supported(const ns_weights* nerf, int mode, int N) {
   return nerf && (nerf->dtype == NS_DTYPE_F16X3 || nerf->dtype == NS_DTYPE_F16) && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
 }

@@ -1,6 +1,7 @@
 """Host side of the one-kernel renderer's depth tangents (ns_render_rays_fused_tangent), no GPU needed: ns_tangent_args as the
-header lays it out against its ctypes mirror, the new symbols in the binding table, the tangent kernel's code objects (no scratch,
-no spill, registers within a gfx950 SIMD, LDS within a CU), and the Python argument checks, which raise before the library is touched."""
+header lays it out against its ctypes mirror, the new symbols in the binding table, the code objects of the tangent kernel on
+f16x3 and on f16 fields (no scratch, no spill, registers within a gfx950 SIMD, LDS within a CU), and the Python argument checks,
+which raise before the library is touched."""
 
 import ctypes
 import os
@@ -38,45 +39,69 @@ def test_tangent_symbols_are_bound():
     assert args[1]._type_ is _lib.TangentArgs
 
 
-def test_tangent_kernel_keeps_no_scratch_and_fits_the_cu():
+# the two instantiations of the tangent renderer (ns_tangent.h): kernel name, mangled template arguments of its instances by
+# width (NKB = W / 32; bf16 is not instantiated: refused), bytes of one block in the embedding stash,
+# samples per group
+KERNELS = {
+    "f16x3": ("nerf_mlp_x3_tan_kernel", {256: "ILi8E", 128: "ILi4E"}, 2048, 64),
+    "f16": ("nerf_tan16_kernel", {256: "Mma16F16ELi8E", 128: "Mma16F16ELi4E"}, 1024, 128),
+}
+
+
+def _blocks(kernel):
+    out = []
+    for dis, notes in _notes_and_isa(kernel.encode()):
+        fns = _functions(dis)
+        for name, blk in _kernel_notes(notes).items():
+            if kernel in name and not name.endswith(".kd"):
+                out.append((name, blk, fns.get(name, [])))
+    return out
+
+
+@pytest.mark.parametrize("field", list(KERNELS))
+def test_tangent_kernel_keeps_no_scratch_and_fits_the_cu(field):
     """Both widths of the tangent kernel (W = 256 and W = 128): no private segment, no spilled VGPR, VGPRs + AGPRs within the
     512 of a gfx950 SIMD lane, no scratch instruction, no more full DMA waits than the forward kernels are allowed."""
+    kernel, instances, _stash, _gs = KERNELS[field]
     seen = set()
-    for dis, notes in _notes_and_isa(b"nerf_mlp_x3_tan_kernel"):
-        blocks = {k: v for k, v in _kernel_notes(notes).items() if "nerf_mlp_x3_tan_kernel" in k and not k.endswith(".kd")}
-        fns = _functions(dis)
-        for name, blk in blocks.items():
-            seen.add(name)
-            assert _field(blk, "private_segment_fixed_size") == 0, name
-            assert _field(blk, "vgpr_spill_count") == 0, name
-            assert _field(blk, "vgpr_count") <= 512, name
-            ins = fns.get(name, [])
-            assert ins, name
-            assert not any(i.startswith("scratch_") for i in ins), name
-            full_waits = sum(bool(re.search(r"s_waitcnt vmcnt\(0\)(?! *lgkmcnt)|s_waitcnt vmcnt\(0\)$", i)) for i in ins)
-            assert full_waits <= 10, (name, full_waits)
-    assert len(seen) == 2, sorted(seen)
+    for name, blk, ins in _blocks(kernel):
+        key = [w for w, tag in instances.items() if tag in name]
+        assert len(key) == 1, name
+        seen.add(key[0])
+        assert _field(blk, "private_segment_fixed_size") == 0, name
+        assert _field(blk, "vgpr_spill_count") == 0, name
+        assert _field(blk, "vgpr_count") <= 512, name
+        assert ins, name
+        assert not any(i.startswith("scratch_") for i in ins), name
+        full_waits = sum(bool(re.search(r"s_waitcnt vmcnt\(0\)(?! *lgkmcnt)|s_waitcnt vmcnt\(0\)$", i)) for i in ins)
+        assert full_waits <= 10, (name, full_waits)
+    assert seen == set(instances), sorted(seen)
 
 
-# dynamic LDS of the tangent launch: these constants MIRROR tan_lds_bytes (ns_nerf_mlp_x3_tan.hip) -- the library exposes it
-# nowhere, so a change there must be repeated here; launch_tan refuses at run time what exceeds 160 KiB.  Weight ring (4 slabs x
-# 16 KiB) | bias image | embedding stash (4 waves x 2 register tiles x 3 blocks x hi / lo 1 KiB) | input staging (4 waves x 11
-# slots x 256 B) | compositing records of a 64-sample group (64 x 36 B + 512 B, ns_comp_epilogue.h) | tangent records (64 x
-# 16 B of d raw, two parities of 64 x 8 B of {dz, d dist}, 64 B of walk state)
-RING, STASH, STAGING, RECORDS, TAN_RECORDS = 4 * 16384, 4 * 2 * 3 * 2048, 4 * 11 * 256, 64 * 36 + 512, 64 * 16 + 2 * 64 * 8 + 64
+# dynamic LDS of the tangent launch: this MIRRORS tan_lds_bytes (ns_tangent.h) -- the library exposes it nowhere, so a change
+# there must be repeated here; launch_tan refuses at run time what exceeds 160 KiB.  For a group of gs samples (gs / 64 primal
+# tiles per wave and as many tangent tiles): weight ring (4 slabs x 16 KiB) | bias image | embedding stash (4 waves x 2 gs / 64
+# register tiles x 3 blocks of `stash` bytes) | input staging (4 waves x 11 slots x 256 B) | compositing records of the group
+# (gs x 36 B + 512 B, ns_comp_epilogue.h) | tangent records (gs x 16 B of d raw, two parities of gs x 8 B of {dz, d dist}, 64 B
+# of walk state)
+def _dynamic_lds(bias_floats, stash, gs):
+    ring, staging = 4 * 16384, 4 * 11 * 256
+    return (ring + (bias_floats * 4 + 15) // 16 * 16 + 4 * (2 * gs // 64) * 3 * stash + staging + (gs * 36 + 512) +
+            (gs * 16 + 2 * gs * 8 + 64))
 
 
 @pytest.mark.parametrize("W,D", [(256, 8), (128, 8), (128, 4)])
-def test_tangent_kernel_fits_the_cu_lds(W, D):
+@pytest.mark.parametrize("field", list(KERNELS))
+def test_tangent_kernel_fits_the_cu_lds(field, W, D):
+    kernel, instances, stash, gs = KERNELS[field]
     bias_floats = D * W + (W // 2 + 16) + 16     # D hidden layers, the view layer + sigma sub-block, the rgb sub-block
-    dynamic = RING + (bias_floats * 4 + 15) // 16 * 16 + STASH + STAGING + RECORDS + TAN_RECORDS
+    dynamic = _dynamic_lds(bias_floats, stash, gs)
     checked = 0
-    for _dis, notes in _notes_and_isa(b"nerf_mlp_x3_tan_kernel"):
-        for name, blk in _kernel_notes(notes).items():
-            if "nerf_mlp_x3_tan_kernel" not in name or name.endswith(".kd") or ("ILi8E" in name) != (W == 256):
-                continue
-            checked += 1
-            assert _field(blk, "group_segment_fixed_size") + dynamic <= 160 * 1024, (name, dynamic)
+    for name, blk, _ins in _blocks(kernel):
+        if instances[W] not in name:
+            continue
+        checked += 1
+        assert _field(blk, "group_segment_fixed_size") + dynamic <= 160 * 1024, (name, dynamic)
     assert checked == 1
 
 
