@@ -295,10 +295,18 @@ int ns_render_rays_fused(const ns_render_args* args, void* stream);
  * the derivative carried through that field's 16-bit arithmetic: the field's weights and activations are fp16 and so is the
  * tangent of every layer (relu' taken from the fp32 pre-activation), so J is the Jacobian of the f16 field, which differs from the
  * fp32-grade one where the field's rounding moves a kink.
- * Supported (ns_render_tangent_supported != 0): NS_MODE_UNIFORM, an F16X3 or F16 NeRF handle with view directions, N as in
- * ns_render_fused_supported; both ray sources, the rgb / disp strides, depth_dev / acc_dev.  Not supported (NS_E_UNSUPPORTED
- * or NS_E_INVALID before any launch): nerf_guard, z_dev / weights_dev / pts_dev, noise, a BF16 or F32 field.  Workspace:
- * ns_render_tangent_workspace_bytes(R) bytes, 256-byte aligned.                                                         */
+ * NS_MODE_DEPTH_ONLY (the DepthNet branch of the training operator, nerf_utils.py:692-715): a ray is ONE sample at z = m, not
+ * clipped (utils.py:220-244), its tangent 1; args->N is ignored and treated as 1, as ns_place_samples does, and std_ is ignored.
+ * The outputs are what ns_raw2outputs documents for N == 1 -- rgb = sigmoid(raw rgb) whatever white_bkgd says, disp = 1e10,
+ * depth = acc = 0 -- bit-identical to ns_render_rays_depthnet in this mode on the same handle and mean.  The Jacobian is
+ * d rgb = rgb (1 - rgb) d raw rgb / d m (relu' conventions as above; a plain product, as torch's sigmoid backward: a NaN mean
+ * gives a NaN rgb and a NaN d rgb for that ray only) and d disp = d depth = d acc = 0 exactly; sigma takes no part.  A group of
+ * 64 samples is 64 rays, each finished by the lanes that hold it; F16X3 handles only (training wants the fp32-grade Jacobian).
+ * Supported (ns_render_tangent_supported != 0): NS_MODE_UNIFORM with an F16X3 or F16 NeRF handle with view directions and N as in
+ * ns_render_fused_supported; NS_MODE_DEPTH_ONLY with an F16X3 NeRF handle with view directions, at any N (ns_render_fused_supported
+ * stays 0 for this mode); both ray sources, both mean sources, the rgb / disp strides, depth_dev / acc_dev.  Not supported
+ * (NS_E_UNSUPPORTED or NS_E_INVALID before any launch): nerf_guard, z_dev / weights_dev / pts_dev, noise, a BF16 or F32 field,
+ * an F16 field in NS_MODE_DEPTH_ONLY, NS_MODE_GAUSSIAN.  Workspace: ns_render_tangent_workspace_bytes(R) bytes, 256-byte aligned.  */
 typedef struct ns_tangent_args {
   const float* mean_dev; /* [R] DepthNet depth supplied by the caller, or NULL: run args->depthnet as ns_render_rays_fused does */
   float* d_rgb_dev;      /* [R,3] d rgb / d mean, or NULL */

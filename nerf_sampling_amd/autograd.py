@@ -574,7 +574,7 @@ class DepthNetTangentRender(torch.autograd.Function):
             mean = depthnet_forward_train(net, o[sl], d[sl]).reshape(-1)
             out, J = ops.render_rays_depthnet_tangent(mean, nerf, rays=(o[sl], d[sl], viewdirs[sl]), n_samples=cfg["n_samples"],
                                                       std=cfg["std"], extras=("depth", "acc"), white_bkgd=cfg["white_bkgd"],
-                                                      approximate=cfg["approximate"])
+                                                      approximate=cfg["approximate"], mode=cfg["mode"])
             for k in outs:
                 outs[k].append(out[k])
                 jac[k].append(J[k])
@@ -606,8 +606,39 @@ class DepthNetTangentRender(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+class SingleSampleTangentRender(torch.autograd.Function):
+    """The DepthNet branch of the training operator (render_rays, nerf_utils.py:692-715) as ONE kernel: rgb_map [R,3] and disp_map
+    [R] of one sample per ray at ``depth`` [R,1] (DepthNetFunction's output) through a frozen f16x3 field and raw2outputs'
+    single-sample rule -- points_along_rays -> NerfInputGrad -> SingleSampleComposite, forward and derivative together
+    (ns_render_rays_fused_tangent, NS_MODE_DEPTH_ONLY).  The forward saves J = d rgb / d depth [R,3]; the backward is
+    d depth = sum_c g_rgb[:, c] J[:, c].  disp is the constant 1e10 and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth: Tensor, o: Tensor, d: Tensor, viewdirs: Tensor, nerf, workspace):
+        out, J = ops.render_rays_depthnet_tangent(depth.reshape(-1), nerf, rays=(o, d, viewdirs), n_samples=1, std=0.0,
+                                                  mode="depth_only", workspace=workspace, device=depth.device)
+        ctx.save_for_backward(J["rgb"])
+        ctx.depth_shape = depth.shape
+        ctx.mark_non_differentiable(out["disp"])
+        return out["rgb"], out["disp"]
+
+    @staticmethod
+    def backward(ctx, g_rgb, _g_disp):
+        (J,) = ctx.saved_tensors
+        return (g_rgb * J).sum(-1).reshape(ctx.depth_shape), None, None, None, None, None
+
+
+def render_single_sample(depth: Tensor, o: Tensor, d: Tensor, viewdirs: Tensor, nerf, workspace=None):
+    """(rgb_map [R,3], disp_map [R]) of one sample per ray at ``depth`` [R,1] or [R], differentiable in ``depth``
+    (SingleSampleTangentRender); ``nerf``: an "f16x3" NeRF handle."""
+    if getattr(nerf, "dtype", None) != "f16x3":
+        raise NotImplementedError(f"the one-sample render needs an f16x3 NeRF handle, got {getattr(nerf, 'dtype', None)}")
+    o, d, viewdirs = (_dev(t, n) for t, n in zip((o, d, viewdirs), ("rays_o", "rays_d", "viewdirs")))
+    return SingleSampleTangentRender.apply(depth, o, d, viewdirs, nerf, workspace)
+
+
 def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n_samples: int, std: float, chunk: int = 65536,
-                                   white_bkgd: bool = True, approximate: bool = False):
+                                   white_bkgd: bool = True, approximate: bool = False, mode: str = "uniform"):
     """DepthNet -> sample_points_around_mean("uniform") -> frozen NeRF -> raw2outputs on the one-kernel renderer, differentiable
     in ``depth_net``'s parameters: dict(rgb [R,3], disp, depth, acc [R]) with a grad_fn (DepthNetTangentRender).  ``nerf``: an
     "f16x3" NeRF handle; ``rays`` = (o, d, viewdirs) device tensors or ``camera`` = (H, W, K, c2w, row0, row1); ``chunk`` rays
@@ -618,14 +649,23 @@ def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n
     the field's 16-bit arithmetic (ops.render_rays_depthnet_tangent): the maps are the f16 one-kernel forward's, and the DepthNet
     gradients are those of the f16 field -- measured, a cosine of at least 0.9989 with autograd through a model of that field, and
     of 0.979 .. 0.99996 with the f16x3 path's on lego_synth and a fitted-scene band, as close as the f16 field itself comes
-    (tests/test_gpu_render_tangent16.py).  bf16 and f32 handles are refused either way."""
-    dtypes = ("f16x3", "f16") if approximate else ("f16x3",)
+    (tests/test_gpu_render_tangent16.py).  bf16 and f32 handles are refused either way.
+
+    ``mode="depth_only"`` (keyword only): one sample per ray at the DepthNet's depth, the training operator's DepthNet branch;
+    ``n_samples`` and ``std`` are ignored, "f16x3" handles only (ops.render_rays_depthnet_tangent): rgb = sigmoid(raw rgb),
+    disp = 1e10, depth = acc = 0, and only rgb carries a gradient."""
+    if mode not in ("uniform", "depth_only"):
+        raise ValueError(f"mode: 'uniform' or 'depth_only', got {mode!r}")
+    single = mode == "depth_only"
+    dtypes = ("f16x3", "f16") if approximate and not single else ("f16x3",)
     if getattr(nerf, "dtype", None) not in dtypes:
+        if single:
+            raise NotImplementedError(f"the depth_only differentiable renderer needs an f16x3 NeRF handle, got {getattr(nerf, 'dtype', None)}")
         if approximate:
             raise NotImplementedError("the differentiable renderer needs an f16x3 or f16 NeRF handle, got "
                                       f"{getattr(nerf, 'dtype', None)}")
         raise NotImplementedError(f"the differentiable renderer needs an f16x3 NeRF handle, got {getattr(nerf, 'dtype', None)}")
-    if not ops._tangent_samples_ok(int(n_samples)):
+    if not single and not ops._tangent_samples_ok(int(n_samples)):
         raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {n_samples}")
     if (rays is None) == (camera is None):
         raise ValueError("exactly one of rays= and camera= is required")
@@ -638,6 +678,6 @@ def render_depthnet_differentiable(depth_net, nerf, *, rays=None, camera=None, n
     depth_net._train_shape()          # (raises for shapes the layer-by-layer path does not cover)
     params = depthnet_params(depth_net)
     cfg = dict(depth_net=depth_net, nerf=nerf, chunk=int(chunk), n_samples=int(n_samples), std=float(std),
-               white_bkgd=bool(white_bkgd), approximate=bool(approximate))
+               white_bkgd=bool(white_bkgd), approximate=bool(approximate), mode=mode)
     rgb, disp, depth, acc = DepthNetTangentRender.apply(o, d, v, cfg, *params)
     return {"rgb": rgb, "disp": disp, "depth": depth, "acc": acc}

@@ -273,7 +273,12 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
 // ns_nerf_mlp_x3_tan.hip for an f16x3 field and by ns_nerf_mlp_ob16_tan.hip for an f16 one): the rays' Jacobians
 // d {rgb, disp, depth, acc} / d mean beside the forward's outputs
 int ns_render_tangent_supported(const ns_weights* nerf, int mode, int N) {
-  return nerf && (nerf->dtype == NS_DTYPE_F16X3 || nerf->dtype == NS_DTYPE_F16) && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
+  if (!nerf) return 0;
+  // one sample per ray at the DepthNet depth: the f16x3 instance only (training wants the fp32-grade Jacobian), at any N
+  if (mode == NS_MODE_DEPTH_ONLY)
+    return nerf->kind == NS_KIND_NERF && nerf->layout == 16 && nerf->dtype == NS_DTYPE_F16X3 && nerf->use_viewdirs &&
+           nerf->out_ch == 4 ? 1 : 0;
+  return (nerf->dtype == NS_DTYPE_F16X3 || nerf->dtype == NS_DTYPE_F16) && ns_render_fused_supported(nerf, mode, N) ? 1 : 0;
 }
 
 int64_t ns_render_tangent_workspace_bytes(int64_t R) {
@@ -287,12 +292,14 @@ int ns_render_rays_fused_tangent(const ns_render_args* a, const ns_tangent_args*
   NS_REQUIRE(a && t, "null args");
   NS_REQUIRE(a->nerf, "the NeRF handle is required");
   NS_REQUIRE(t->mean_dev || a->depthnet, "a DepthNet handle or the caller's mean is required");
+  const int N = a->mode == NS_MODE_DEPTH_ONLY ? 1 : a->N;     // one sample per ray: N and std_ are ignored (ns_place_samples)
   if (!ns_render_tangent_supported(a->nerf, a->mode, a->N)) {
-    ns::set_error("ns_render_rays_fused_tangent: uniform placement, an f16x3 or f16 NeRF handle with view directions and n_samples a "
-                  "power of two in [2, 64] or a multiple of 64 up to 512 are required (mode %d, N %d)", a->mode, a->N);
+    ns::set_error("ns_render_rays_fused_tangent: uniform placement with an f16x3 or f16 NeRF handle with view directions and n_samples "
+                  "a power of two in [2, 64] or a multiple of 64 up to 512, or depth_only placement with an f16x3 one, are "
+                  "required (mode %d, N %d, dtype %d)", a->mode, a->N, a->nerf->dtype);
     return NS_E_UNSUPPORTED;
   }
-  NS_REQUIRE(!a->noise_dev, "uniform placement takes no noise");
+  NS_REQUIRE(!a->noise_dev, "uniform and depth_only placement take no noise");
   if (a->nerf_guard || a->z_dev || a->weights_dev || a->pts_dev) {
     ns::set_error("ns_render_rays_fused_tangent: no guard pass and no per-sample outputs (z, weights, pts)");
     return NS_E_UNSUPPORTED;
@@ -312,7 +319,7 @@ int ns_render_rays_fused_tangent(const ns_render_args* a, const ns_tangent_args*
   set_outputs(c, outputs(a));
   if ((rc = record(a->ev_mlp_begin, stream)) != NS_OK) return rc;
   if (a->nerf->dtype == NS_DTYPE_F16X3)
-    rc = ns_nerf_forward_x3_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
+    rc = ns_nerf_forward_x3_tangent(a->nerf, r.o, r.d, r.view, r.R, N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,
                                     t->d_acc_dev, ns::as_stream(stream));
   else
     rc = ns_nerf_forward_ob16_tangent(a->nerf, r.o, r.d, r.view, r.R, a->N, &c, t->d_rgb_dev, t->d_disp_dev, t->d_depth_dev,

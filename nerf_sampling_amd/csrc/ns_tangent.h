@@ -22,6 +22,13 @@
 //               division); a ray of several 64-sample chunks carries its walk state from group to group in LDS.
 // A product of a value and a tangent is a SELECT on the tangent (tmul): a zero tangent contributes exactly 0, so a ray whose
 // samples have no depth tangent (a NaN mean, every sample clipped) has a Jacobian of 0, whatever NaN or inf its forward holds.
+//
+// ONE SAMPLE PER RAY (tangent_body<M, NKB, true>, NS_MODE_DEPTH_ONLY: the training operator's DepthNet branch): the sample sits at
+// z = m, unclipped, with dz = 1, and is composited by raw2outputs' N == 1 rule (ns_composite.hip: rgb = sigmoid(raw rgb),
+// disp = 1 / 1e-10, depth = acc = 0; sigma takes no part, nor does the background).  A group of 64 samples is 64 rays: the lanes
+// that hold a sample's raw and d raw accumulators finish it and write its outputs -- no placement pass, no compositing records,
+// no barrier, no walk, nothing carried from group to group.  d rgb = rgb (1 - rgb) d raw, a plain product as in torch's sigmoid
+// backward: a NaN mean gives a NaN rgb and a NaN d rgb for its ray.  d disp = d depth = d acc = 0.
 #pragma once
 #include "ns_common.h"
 #include "ns_comp_epilogue.h"
@@ -406,8 +413,27 @@ __device__ __forceinline__ void walk_group(const TanArgs& a, const RecOf<GS>& re
   }
 }
 
-// The kernel: NKB = W / 32 K-blocks of a hidden layer
-template <class M, int NKB>
+// One sample per ray (ONE): ray r from its sample's raw rgb and their tangents -- raw2outputs_single_kernel (ns_composite.hip)
+// and its derivative
+__device__ __forceinline__ void finish_single(const TanArgs& a, int64_t r, const f32x4a& raw, const f32x4a& draw) {
+  const float c0 = nscomp::sigmoid_ieee(raw[0]), c1 = nscomp::sigmoid_ieee(raw[1]), c2 = nscomp::sigmoid_ieee(raw[2]);
+  float* prgb = a.rgb + r * a.rgb_stride;
+  prgb[0] = c0; prgb[1] = c1; prgb[2] = c2;
+  a.disp[r * a.disp_stride] = 1.0f / 1e-10f;
+  if (a.depth) a.depth[r] = 0.0f;
+  if (a.acc) a.acc[r] = 0.0f;
+  if (a.d_rgb) {
+    a.d_rgb[r * 3] = (c0 * (1.0f - c0)) * draw[0];
+    a.d_rgb[r * 3 + 1] = (c1 * (1.0f - c1)) * draw[1];
+    a.d_rgb[r * 3 + 2] = (c2 * (1.0f - c2)) * draw[2];
+  }
+  if (a.d_disp) a.d_disp[r] = 0.0f;
+  if (a.d_depth) a.d_depth[r] = 0.0f;
+  if (a.d_acc) a.d_acc[r] = 0.0f;
+}
+
+// The kernel: NKB = W / 32 K-blocks of a hidden layer; ONE: one sample per ray at z = m (see the head of this file; a.N == 1)
+template <class M, int NKB, bool ONE = false>
 __device__ __forceinline__ void tangent_body(const TanArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Ops = TanOps<M>;
@@ -482,10 +508,23 @@ __device__ __forceinline__ void tangent_body(const TanArgs& a) {
     Block xe[kRT][2];   // embedded points (tiles 0 .. kTiles - 1) and their tangents
     uint32_t bad = 0;   // tiles with non-finite inputs (kMarkBad)
     asm volatile("" ::: "memory");
-    nsepi::place_wave(a, rec, staged_at, grp, gi, par, wave);
+    if constexpr (!ONE) nsepi::place_wave(a, rec, staged_at, grp, gi, par, wave);
     {
-      const int jg0 = a.m_chunks ? (gi * kGS) % a.N : 0;
       float P[kTiles][3], PD[kTiles][3], V[kTiles][3], ZD[kTiles];
+      if constexpr (ONE) {
+        static_for<kTiles>([&](auto t_) {
+          constexpr int t = decltype(t_)::value;
+          const float zz = staged_at(6, t * 16 + n);                  // z = m, no clip (utils.py:220-244), dz = 1
+          ZD[t] = 1.0f;
+          static_for<3>([&](auto c_) {
+            constexpr int c = decltype(c_)::value;
+            P[t][c] = staged_at(c, t * 16 + n) + staged_at(3 + c, t * 16 + n) * zz;
+            PD[t][c] = staged_at(3 + c, t * 16 + n);
+            V[t][c] = staged_at(7 + c, t * 16 + n);
+          });
+        });
+      } else {
+      const int jg0 = a.m_chunks ? (gi * kGS) % a.N : 0;
       static_for<kTiles>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
         const int ig = (wave * kTiles + t) * 16 + n;                // the sample in its group, j: in its ray
@@ -506,6 +545,7 @@ __device__ __forceinline__ void tangent_body(const TanArgs& a) {
           *tr.dz(par, ig) = nsepi::v2f{ZD[t], j < a.N - 1 ? tmul(nrm, zd1 - ZD[t]) : 0.0f};
         }
       });
+      }
       asm volatile("" ::: "memory");   // the staged reads above, then the stash writes (two LDS regions)
       static_for<kTiles>([&](auto t_) {
         constexpr int t = decltype(t_)::value;
@@ -580,6 +620,18 @@ __device__ __forceinline__ void tangent_body(const TanArgs& a) {
     layer_tan<M, 1, NKB / 2, kNone>(ring, bias, g, hA, last, in_B);
 
     const int le = nsepi::opaque_lane();
+    if constexpr (ONE) {
+      if (le < 16) {                           // lane group g == 0 holds the sample's raw rgb and d raw rgb: it finishes the ray
+        static_for<kTiles>([&](auto t_) {
+          constexpr int t = decltype(t_)::value;
+          const int64_t r = grp * kGS + (wave * kTiles + t) * 16 + le;
+          f32x4a q = last[t];
+          if (Ops::kMarkBad && ((bad >> t) & 1u)) { const float nan = __builtin_nanf(""); q = f32x4a{nan, nan, nan, nan}; }
+          if (r < S_) finish_single(a, r, q, last[kTiles + t]);
+        });
+      }
+      continue;
+    }
     if (le < 16) {
       static_for<kTiles>([&](auto t_) {
         constexpr int t = decltype(t_)::value;

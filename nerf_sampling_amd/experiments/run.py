@@ -31,6 +31,9 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--iters", default=100_000, show_default=True, help="Training iterations (EPOCHS in the reference).")
 @click.option("--dtype", default="f32", type=click.Choice(["bf16", "f16", "f32", "f16x3"]), show_default=True,
               help="MFMA operand precision of the frozen-NeRF forward kernels (not in the reference).")
+@click.option("--fused-step", "fused_step", is_flag=True, default=False,
+              help="Run the DepthNet branch of the training step as one kernel and the target pass as one call (not in the "
+                   "reference; DepthNetTrainer(fused_step=True)).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -52,6 +55,8 @@ def main(**kw):
     set_global_device(k["device"])
     ops.set_compute_dtype(kw["dtype"])
     k.update(ft_path=ft_path, depth_net_path=None, datadir=datadir, basedir=f"{root}/logs")
+    if kw["fused_step"]:
+        k["fused_step"] = True
     trainer = load_obj_from_config(cfg=config)
     trainer.train(N_iters=kw["iters"] + 1)
 

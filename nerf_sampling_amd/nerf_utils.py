@@ -245,9 +245,9 @@ def prepare_rays(c2w, c2w_staticcam, use_viewdirs, ndc, H, W, K, near, far, rays
 def _render(batch_fn, H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, **kwargs):
     rays, rays_o, rays_d, sh = prepare_rays(c2w=c2w, c2w_staticcam=c2w_staticcam, use_viewdirs=use_viewdirs,
                                             ndc=ndc, H=H, W=W, K=K, near=near, far=far, rays=rays)
-    if batch_fn is batchify_rays_test:
-        # internal: the scalar bounds every row of the batch carries, for the one-call vanilla pass of render_rays_test (which
-        # then need not read the batch's near / far columns back from the device)
+    if batch_fn is batchify_rays_test or kwargs.get("fused_step", False):
+        # internal: the scalar bounds every row of the batch carries, for the one-call vanilla pass of render_rays_test and of
+        # render_rays under fused_step (which then need not read the batch's near / far columns back from the device)
         kwargs["_near_far"] = (float(near), float(far))
     all_returned = batch_fn(rays, chunk, **kwargs)
     for key in all_returned:
@@ -429,12 +429,81 @@ def sample_as_in_NeRF(ray_batch, network_fn, network_fine, network_query_fn, N_s
     return f_density, f_z, f_pts, f_rgb, f_w, f_alphas, f_disp, f_raw
 
 
+_fused_step_warned = False
+
+
+def _fused_step_field(net, network_query_fn, trainer, viewdirs):
+    """The f16x3 handle of the frozen field when render_rays' DepthNet branch may run as one kernel (``fused_step``): the
+    standard query function, this package's NeRF with view directions, the trainer's own raw2outputs / run_network, and a field
+    that packs as f16x3.  None otherwise; a field that does not pack warns once and takes the layer-by-layer path."""
+    global _fused_step_warned
+    from .trainers import DepthNetTrainer
+
+    if not (viewdirs is not None and getattr(network_query_fn, "_ns_standard_query", False)
+            and isinstance(net, run_nerf_helpers.NeRF) and net.use_viewdirs
+            and type(trainer).raw2outputs is DepthNetTrainer.raw2outputs
+            and type(trainer).run_network is DepthNetTrainer.run_network):
+        return None
+    try:
+        return net.packed("f16x3")
+    except (NotImplementedError, RuntimeError, ValueError) as e:
+        if not _fused_step_warned:
+            import warnings
+
+            warnings.warn(f"fused_step: the field does not pack as f16x3 ({e}); render_rays takes the layer-by-layer path")
+            _fused_step_warned = True
+        return None
+
+
+def _render_rays_fused_step(ray_batch, rays_o, rays_d, viewdirs, field, network_fn, network_query_fn, N_samples, trainer,
+                            lindisp, perturb, network_fine, white_bkgd, raw_noise_std, pytest, kwargs):
+    """render_rays with ``fused_step``: the target pass as one ns_render_rays_hierarchical call where it is eligible (the values of
+    sample_as_in_NeRF + argmax_gather bit for bit, random draws in the same order), the DepthNet branch as one
+    ns_render_rays_fused_tangent call (autograd.SingleSampleTangentRender).  The same keys as render_rays except ``raw``, which
+    stays in the CU."""
+    from .autograd import render_single_sample
+
+    ws = kwargs.get("_workspaces") or {}
+    with torch.no_grad():
+        near_far = kwargs.get("_near_far")
+        if near_far is not None and _hier_one_call_eligible(network_fn, network_fine, network_query_fn, trainer, viewdirs,
+                                                            N_samples, raw_noise_std, pytest):
+            max_z_vals = _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samples, trainer, perturb,
+                                           lindisp, white_bkgd, near_far, False, workspace=ws.get("vanilla"))["max_z"]
+        else:
+            (_dens, fine_z, _pts, _rgb, fine_w, _al, _disp, _raw) = sample_as_in_NeRF(
+                ray_batch=ray_batch, N_samples=N_samples, network_fn=network_fn, network_fine=network_fine,
+                network_query_fn=network_query_fn, trainer=trainer, perturb=perturb, raw_noise_std=raw_noise_std,
+                lindisp=lindisp, white_bkgd=white_bkgd, pytest=pytest, kwargs=kwargs)
+            max_z_vals, _, _ = ops.argmax_gather(fine_w, fine_z)
+        max_pts = ops.points_along_rays(rays_o, rays_d, max_z_vals)
+    depth_net_z_vals = kwargs["depth_network"](rays_o, rays_d)
+    rgb_map, disp_map = render_single_sample(depth_net_z_vals, rays_o, rays_d, viewdirs, field, ws.get("tangent"))
+    with torch.no_grad():
+        depth_net_pts = ops.points_along_rays(rays_o, rays_d, depth_net_z_vals.detach())
+    to_host = (lambda t: t) if kwargs.get("_skip_host_copies", False) else (lambda t: t.cpu())
+    return {"depth_net_rgb_map": rgb_map, "depth_net_disp_map": disp_map, "depth_net_z_vals": depth_net_z_vals,
+            "max_z_vals": max_z_vals, "depth_net_pts": to_host(depth_net_pts), "max_pts": to_host(max_pts)}
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, trainer, retraw=True, lindisp=False,
                 perturb=0.0, N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0.0,
                 verbose=False, pytest=False, **kwargs):
-    """Training operator, forward (nerf_utils.py:614-733); same keys / host copies as the reference."""
+    """Training operator, forward (nerf_utils.py:614-733); same keys / host copies as the reference.
+
+    ``fused_step`` (render kwarg, not in the reference; default off): with the standard configuration (see _fused_step_field)
+    the DepthNet branch -- points, the frozen field, single-sample compositing and, in the backward, the field's input-gradient
+    chain -- runs as ONE kernel on the field's f16x3 packing, which returns d rgb / d depth beside rgb, and the target pass as one
+    hierarchical-renderer call.  ``raw`` is then omitted from the returned keys (it never leaves the CU; nothing in the trainer
+    reads it); max_z_vals and depth_net_z_vals are the default path's bits, depth_net_rgb_map is the f16x3 field's (fp32-grade)
+    instead of the exact-fp32 kernel's."""
     rays_o, rays_d = ray_batch[:, 0:3].contiguous(), ray_batch[:, 3:6].contiguous()
     viewdirs = ray_batch[:, -3:].contiguous() if ray_batch.shape[-1] > 8 else None
+    if kwargs.get("fused_step", False):
+        field = _fused_step_field(network_fine if network_fine is not None else network_fn, network_query_fn, trainer, viewdirs)
+        if field is not None:
+            return _render_rays_fused_step(ray_batch, rays_o, rays_d, viewdirs, field, network_fn, network_query_fn, N_samples,
+                                           trainer, lindisp, perturb, network_fine, white_bkgd, raw_noise_std, pytest, kwargs)
     # the vanilla pass only provides the regression target max_z: frozen networks, detached samples
     # (Trainer.py:569) -- no gradient reaches the DepthNet through it
     with torch.no_grad():
@@ -498,7 +567,7 @@ def _hier_one_call_eligible(network_fn, network_fine, network_query_fn, trainer,
 
 
 def _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samples, trainer, perturb, lindisp, white_bkgd,
-                      near_far, full):
+                      near_far, full, workspace=None):
     """The fine pass's max-weight sample (and with ``full`` its z / weights / pts / rgb / disp) through one
     ns_render_rays_hierarchical call: the values sample_as_in_NeRF + argmax_gather give, bit for bit."""
     R, dev = rays_o.shape[0], rays_o.device
@@ -509,7 +578,8 @@ def _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samp
                                        rays=(rays_o, rays_d, viewdirs), n_coarse=int(N_samples),
                                        n_importance=int(trainer.N_importance), lindisp=bool(lindisp),
                                        white_bkgd=bool(white_bkgd), near=near_far[0], far=near_far[1], t_rand=t_rand, u=u,
-                                       extras=("z", "weights") if full else False, device=dev, max_sample=True)
+                                       extras=("z", "weights") if full else False, device=dev, max_sample=True,
+                                       workspace=workspace)
     if full:
         out["pts"] = ops.points_along_rays(rays_o, rays_d, out["z"])
     return out

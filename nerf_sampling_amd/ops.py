@@ -625,7 +625,7 @@ def _tangent_samples_ok(n: int) -> bool:
 def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=None, camera=None, n_samples: int,
                                  std: float, extras=(), near: float = 2.0, far: float = 6.0, sphere_radius: float = 2.0,
                                  white_bkgd: bool = True, workspace: Optional[RenderWorkspace] = None, device="cuda",
-                                 mlp_events=None, approximate: bool = False):
+                                 mlp_events=None, approximate: bool = False, mode: str = "uniform"):
     """The one-kernel renderer with forward-mode tangents in every ray's DepthNet depth (ns_render_rays_fused_tangent).
 
     ``depthnet_or_mean``: a packed DepthNet (its depth is computed as render_rays_depthnet does) or a device tensor [R] of
@@ -642,16 +642,28 @@ def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=
     it is 10 .. 100 x larger, because the f16 field's rounding moves ReLU and opacity kinks.  The DepthNet gradients of
     autograd.render_depthnet_differentiable keep a cosine of at least 0.9989 with the same f16 field's and of 0.979 .. 0.99996
     with the f16x3 path's, as the f16 field itself does (tests/test_gpu_render_tangent16.py).  The outputs
-    are those of the f16 one-kernel forward bit for bit.  bf16 and f32 handles are refused either way."""
+    are those of the f16 one-kernel forward bit for bit.  bf16 and f32 handles are refused either way.
+
+    ``mode="depth_only"`` (keyword only; default "uniform"): one sample per ray at the depth itself, unclipped -- the DepthNet
+    branch of the training operator (render_rays).  ``n_samples`` and ``std`` are ignored.  out is raw2outputs' single-sample
+    rule, bit for bit render_rays_depthnet(mode="depth_only") on the same handles: rgb = sigmoid(raw rgb) whatever the
+    background, disp = 1e10, depth = acc = 0; J["rgb"] = rgb (1 - rgb) d raw rgb / d depth, J["disp"] = J["depth"] =
+    J["acc"] = 0.  A NaN depth gives a NaN rgb and a NaN J["rgb"] for its ray, as torch autograd of the chain does.  An "f16x3"
+    handle only: ``approximate=True`` with an "f16" handle raises NotImplementedError."""
     names = _extras_names(extras, ())
-    ok_dtypes = ("f16x3", "f16") if approximate else ("f16x3",)
+    if mode not in ("uniform", "depth_only"):
+        raise ValueError(f"mode: 'uniform' or 'depth_only', got {mode!r}")
+    single = mode == "depth_only"
+    ok_dtypes = ("f16x3", "f16") if approximate and not single else ("f16x3",)
     if not isinstance(nerf, PackedWeights) or nerf.dtype not in ok_dtypes:
         got = getattr(nerf, "dtype", type(nerf).__name__)
+        if single:
+            raise NotImplementedError(f"depth_only tangents need an f16x3 NeRF handle, got {got}")
         if approximate:
             raise NotImplementedError(f"tangents need an f16x3 or f16 NeRF handle, got {got}")
         raise NotImplementedError(f"tangents need an f16x3 NeRF handle, got {got}")
-    N = int(n_samples)
-    if not _tangent_samples_ok(N):
+    N = 1 if single else int(n_samples)
+    if not single and not _tangent_samples_ok(N):
         raise NotImplementedError(f"n_samples must be a power of two in [2, 64] or a multiple of 64 up to 512, got {N}")
     if (rays is None) == (camera is None):
         raise ValueError("exactly one of rays= and camera= is required")
@@ -675,7 +687,7 @@ def render_rays_depthnet_tangent(depthnet_or_mean, nerf: PackedWeights, *, rays=
     R, device, _keep = _set_ray_source(a, rays, camera, device)
     if mean is not None:
         t.mean_dev = mean.data_ptr()
-    a.mode, a.N, a.std_ = _lib.MODE_UNIFORM, N, float(std)
+    a.mode, a.N, a.std_ = _MODES[mode], N, float(std)
     a.near_, a.far_, a.sphere_radius, a.white_bkgd = float(near), float(far), float(sphere_radius), int(bool(white_bkgd))
     out = {"rgb": torch.empty((R, 3), dtype=torch.float32, device=device), "disp": torch.empty((R,), dtype=torch.float32, device=device)}
     J = {"rgb": torch.empty((R, 3), dtype=torch.float32, device=device)}

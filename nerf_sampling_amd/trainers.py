@@ -290,7 +290,8 @@ class GraphedDepthNetStep:
     Eagerly the step is bound by the host side of those launches; captured once (torch.cuda.CUDAGraph = hipGraph on
     ROCm) and replayed, the host issues ONE launch per step.  What makes the step capturable: HipAdam's device-resident
     step counter / learning rate (ns_adam_step_dev), render_rays without its three host copies (nothing in the step
-    reads them), and fixed batch shapes.  The first ``warmup`` calls run eagerly (they are real steps and warm every
+    reads them), and fixed batch shapes.  With ``fused_step`` in the render kwargs the step's two one-call renderers work in
+    workspaces this object owns and on f16x3 streams it keeps alive.  The first ``warmup`` calls run eagerly (they are real steps and warm every
     lazily-built cache); the next call captures and replays.  A batch of another shape runs eagerly.
 
     Call: ``step(batch_rays, i, target_s) -> (img_loss, depth_net_loss, psnr, None)`` like core_optimization_loop."""
@@ -300,13 +301,21 @@ class GraphedDepthNetStep:
         self.calls, self.graph, self.shape = 0, None, None
         self.opt.use_device_step()
         # everything the captured kernels point into must outlive the graph: packed weight streams of the frozen networks
-        self._keep = [n.packed() for n in (render_kwargs_train.get("network_fn"), render_kwargs_train.get("network_fine"))
-                      if n is not None]
+        nets = [n for n in (render_kwargs_train.get("network_fn"), render_kwargs_train.get("network_fine")) if n is not None]
+        self._keep = [n.packed() for n in nets]
+        self._extra = {"_skip_host_copies": True}
+        if render_kwargs_train.get("fused_step", False):
+            # the fused step's two one-call renderers: their f16x3 streams, and workspaces of this object's own (the module's
+            # shared one may be regrown, i.e. freed, by any other render call between two replays)
+            field = nerf_utils._fused_step_field(nets[-1], render_kwargs_train.get("network_query_fn"), trainer, True)
+            if field is not None:
+                self._keep.append(field)
+            self._extra["_workspaces"] = {"vanilla": ops.RenderWorkspace(), "tangent": ops.RenderWorkspace()}
 
     def _eager(self, batch_rays, i, target_s):
         from .run_nerf_helpers import mse2psnr
 
-        img_loss, dn_loss = self.tr._optimization_step(self.opt, self.kw, batch_rays, i, target_s, _skip_host_copies=True)
+        img_loss, dn_loss = self.tr._optimization_step(self.opt, self.kw, batch_rays, i, target_s, **self._extra)
         self.kw["depth_network"].repack()
         return img_loss, dn_loss, mse2psnr(img_loss), None
 
@@ -319,7 +328,7 @@ class GraphedDepthNetStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.img_loss, self.dn_loss = self.tr._optimization_step(self.opt, self.kw, self.rays, 1 << 30, self.target,
-                                                                     _skip_host_copies=True)
+                                                                     **self._extra)
 
     def __call__(self, batch_rays, i, target_s):
         from .run_nerf_helpers import mse2psnr
@@ -363,7 +372,10 @@ class DepthNetTrainer(BlenderTrainer):
 
     def __init__(self, distance=None, sampling_mode=None, n_depth_samples=None,
                  depth_net_path: Optional[str] = None, n_layers: int = 6, layer_width: int = 256,
-                 sphere_radius: float = 2.0, **kwargs):
+                 sphere_radius: float = 2.0, fused_step: bool = False, **kwargs):
+        # fused_step (not in the reference; default off): render_rays runs the DepthNet branch of the training step as one
+        # kernel and the target pass as one call (nerf_utils.render_rays)
+        self.fused_step = bool(fused_step)
         self.n_layers, self.layer_width = n_layers, layer_width
         self.depth_net_path, self.sphere_radius = depth_net_path, sphere_radius
         self.distance, self.n_depth_samples, self.sampling_mode = distance, n_depth_samples, sampling_mode
@@ -399,6 +411,8 @@ class DepthNetTrainer(BlenderTrainer):
         for kw, mode in ((render_kwargs_train, "train"), (render_kwargs_test, "test")):
             kw["depth_network"] = depth_network
             kw["model_mode"] = mode
+        if self.fused_step:
+            render_kwargs_train["fused_step"] = True
         return optimizer, sampling_optimizer, render_kwargs_train, render_kwargs_test
 
     def save_rays_data(self, rays_o, pts, alpha):
