@@ -260,12 +260,24 @@ typedef struct ns_render_args {
    * last sample of every ray is evaluated a second time through it (R of the R*N samples, ~5 % of the frame) and its
    * sigma replaces the 16-bit one before compositing.  Pair it with an F16X3 DepthNet handle for fp32-grade depths.  */
   const ns_weights* nerf_guard;
-  /* 0: the guard re-evaluates the last sample of EVERY ray.  > 0 (ns_render_rays_fused, N <= 64): only of the rays whose own
-   * 16-bit sigma of that sample lies within this distance of zero -- the only ones whose step can flip: a sigma beyond it
-   * composites to alpha = 0 or 1 either way -- found by the kernel itself, re-evaluated afterwards on a compacted list
-   * (three small launches; the count never leaves the device) and their pixels re-added from the kernel's partial sums, bit
-   * for bit what the every-ray guard gives wherever |sigma16 - sigma32| < guard_threshold.  The five-launch chain
-   * (ns_render_rays_depthnet), and the one-kernel renderer on an F16X3 field, ignore it and guard every ray.              */
+  /* (Two options of guard_threshold, which follows them and stays the last field of the guard block.)
+   * Rays of several 64-sample chunks (N a multiple of 64 in [128, 512]).  0 (the default): they take the every-ray guard whatever
+   * guard_threshold says.  1: with guard_threshold > 0, an F16X3 layout-16 guard handle and a 16-bit field they take the
+   * selective form as well -- the kernel flags the finished rays, the fix-up repeats the last chunk's additions from a
+   * 192-byte record per flagged ray, and the workspace is ns_render_fused_guard_long_workspace_bytes(R) bytes (a call the
+   * field is ignored for needs ns_render_fused_workspace_bytes(R) as before; the larger one serves both).  Ignored everywhere else (N <= 64, an F16X3 field, threshold 0, another guard packing,
+   * ns_render_rays_depthnet): the call does what it does with 0.                                                        */
+  int guard_long_selective;
+  /* NULL, or one uint32 on the device: when the selective form ran (either ray length), the number of flagged rays is copied
+   * there after the fix-up, device to device on `stream`; otherwise it is left as it is.                               */
+  uint32_t* guard_count_dev;
+  /* 0: the guard re-evaluates the last sample of EVERY ray.  > 0 (ns_render_rays_fused; N <= 64, or a multiple of 64 up to 512
+   * with guard_long_selective above): only of the rays whose own 16-bit sigma of that sample lies within this distance of zero
+   * -- the only ones whose step can flip: a sigma beyond it composites to alpha = 0 or 1 either way -- found by the kernel
+   * itself, re-evaluated afterwards on a compacted list (three small launches; the count never leaves the device) and their
+   * pixels re-added from the kernel's partial sums, bit for bit what the every-ray guard gives wherever
+   * |sigma16 - sigma32| < guard_threshold.  The five-launch chain (ns_render_rays_depthnet), and the one-kernel renderer on
+   * an F16X3 field, ignore it and guard every ray.                                                                        */
   float guard_threshold;
   float* depth_dev; /* [R] or NULL: expected depth sum_i w_i z_i (see above) */
   float* acc_dev;   /* [R] or NULL: opacity sum_i w_i, before the white-background add */
@@ -283,6 +295,7 @@ int ns_render_rays_depthnet(const ns_render_args* args, void* stream);
  * is served by ns_render_rays_depthnet.  Workspace: ns_render_fused_workspace_bytes(R) bytes, 256-byte aligned.        */
 int ns_render_fused_supported(const ns_weights* nerf, int mode, int N);
 int64_t ns_render_fused_workspace_bytes(int64_t R);
+int64_t ns_render_fused_guard_long_workspace_bytes(int64_t R); /* with guard_long_selective = 1: 192-byte records, 288 B per ray */
 int ns_render_rays_fused(const ns_render_args* args, void* stream);
 /* The one-kernel renderer with forward-mode tangents in the DepthNet depth m of every ray.  In uniform placement every sample
  * depth is m + a constant, clipped to [2, 6], so a ray's composited outputs depend on m alone and their Jacobian is six numbers

@@ -38,7 +38,7 @@ class RenderArgs(C.Structure):
         ("rgb_dev", _p), ("disp_dev", _p), ("z_dev", _p), ("weights_dev", _p), ("pts_dev", _p),
         ("ev_mlp_begin", _p), ("ev_mlp_end", _p),
         ("rgb_stride", _i64), ("disp_stride", _i64),
-        ("nerf_guard", _p), ("guard_threshold", _f),
+        ("nerf_guard", _p), ("guard_long_selective", _i), ("guard_count_dev", _p), ("guard_threshold", _f),
         ("depth_dev", _p), ("acc_dev", _p),
     ]
 
@@ -124,6 +124,7 @@ SIGNATURES = {
     "ns_render_rays_depthnet": (_i, [C.POINTER(RenderArgs), _p]),
     "ns_render_fused_supported": (_i, [_p, _i, _i]),
     "ns_render_fused_workspace_bytes": (_i64, [_i64]),
+    "ns_render_fused_guard_long_workspace_bytes": (_i64, [_i64]),
     "ns_render_rays_fused": (_i, [C.POINTER(RenderArgs), _p]),
     "ns_render_tangent_supported": (_i, [_p, _i, _i]),
     "ns_render_tangent_workspace_bytes": (_i64, [_i64]),

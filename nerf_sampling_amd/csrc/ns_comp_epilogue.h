@@ -21,6 +21,19 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 typedef v4f __attribute__((address_space(3))) * CrawPtr;
 typedef v2f __attribute__((address_space(3))) * CzdPtr;
 typedef float __attribute__((address_space(3))) * CsigPtr;
+typedef uint32_t __attribute__((address_space(3))) * CslotPtr;
+
+// The selective guard's record of a flagged ray of SEVERAL chunks (ns_render_args::guard_long_selective): kFixLongFloats floats.
+// The last sample's share sits inside the last chunk's 64-lane sum, which reduce5<64> forms on lane 63 as
+//   u6 + (u5 + (u4 + (u3 + (u2 + (x62 + x63)))))        x_i: lane i's share;  u_k: what lane 63 - 2^(k-1) holds after k - 1 steps
+// (u2 = x60 + x61, u3 the sum of lanes 56 .. 59, u4 of 48 .. 55, u5 of 32 .. 47, u6 of 0 .. 31, each as the scan rounds it), and
+// the ray's totals are (the earlier chunks' running totals) + that.  The record keeps, per sum, the earlier total and the six
+// operands beside x63, so the fix-up repeats the seven additions with the re-evaluated share -- the forward's own arithmetic
+// stays as it is.  Floats 5 .. 12 are those of the single-chunk record (ns_fix_gather reads either):
+//   0..4 earlier totals {r, g, b, depth, acc} | 5 T entering the last sample | 6..8 its raw rgb | 9 z | 10 dist | 11, 12 ray index
+//   lo / hi | 16 + 5 k + 0..4, k = 0 .. 5: x62, u2, u3, u4, u5, u6 of {r, g, b, depth, acc}
+constexpr int kFixLongFloats = NS_FIX_LONG_FLOATS, kFixLongOperands = 16;
+static_assert(kFixLongOperands + 6 * 5 <= kFixLongFloats, "six operands of five sums behind the single-chunk record's fields");
 
 // The compositing fields of a kernel's argument struct, which place_wave / composite_group / set_comp_args read by name
 // (Nerf16Args, ns_nerf_mlp_ob16.hip, spells them out among its own fields and documents each)
@@ -67,6 +80,7 @@ __device__ __forceinline__ int opaque_lane() {
 //   kOPEN + 8 p + 0..5 the open ray's {carry, r, g, b, depth, acc}, parity p;  + 6..7 its max-weight sample so far: weight, z
 //   kMGB + 2 c + 0..1  chunk c's max-weight sample: sigmoid(raw g, b)
 //   kMOPEN + 3 p + 0..2  the open ray's max-weight sample so far: sigmoid(raw r, g, b), parity p
+//   kFIX + c           (uint32) chunk c ends a ray the selective guard flagged: 1 + the slot of its record in fix_rec; else 0
 template <int T, int NWAVES>
 struct Records {
   static constexpr int GS = NWAVES * T * 16;
@@ -74,9 +88,9 @@ struct Records {
   // rays of several chunks: per chunk of the group its transmittance factor (kCP) and its five sums (kCS); the ray that is open
   // at the group's end: {carry, r, g, b, depth, acc}, two parities (kOPEN + 8 par is read, kOPEN + 8 (par ^ 1) written)
   static constexpr int kCP = 0, kCS = 8, kOPEN = 8 + 8 * 8;          // float offsets inside the 128-float scalar block
-  static constexpr int kMGB = kOPEN + 16, kMOPEN = kMGB + 16;
+  static constexpr int kMGB = kOPEN + 16, kMOPEN = kMGB + 16, kFIX = kMOPEN + 2 * 3;
   static_assert(T <= 8, "eight chunks per group at most");
-  static_assert(kMOPEN + 2 * 3 <= 128, "the max-weight sample's slots end inside the 128-float scalar block (kBytes unchanged)");
+  static_assert(kFIX + 8 <= 128, "the max-weight sample's and the guard's slots end inside the 128-float scalar block (kBytes unchanged)");
   uint32_t base;
   __device__ __forceinline__ CrawPtr raw(int i) const { return reinterpret_cast<CrawPtr>(static_cast<uintptr_t>(base + static_cast<uint32_t>(i) * 16u)); }
   __device__ __forceinline__ CzdPtr zd(uint32_t par, int i) const {
@@ -87,6 +101,9 @@ struct Records {
   }
   __device__ __forceinline__ CsigPtr scal(int k) const {
     return reinterpret_cast<CsigPtr>(static_cast<uintptr_t>(base + GS * 36u + static_cast<uint32_t>(k) * 4u));
+  }
+  __device__ __forceinline__ CslotPtr slot(int c) const {
+    return reinterpret_cast<CslotPtr>(static_cast<uintptr_t>(base + GS * 36u + static_cast<uint32_t>(kFIX + c) * 4u));
   }
 };
 
@@ -152,6 +169,7 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
   constexpr int GS = Records<T, NWAVES>::GS;
   constexpr int kCP = Records<T, NWAVES>::kCP, kCS = Records<T, NWAVES>::kCS, kOPEN = Records<T, NWAVES>::kOPEN;
   constexpr int kMGB = Records<T, NWAVES>::kMGB, kMOPEN = Records<T, NWAVES>::kMOPEN;
+  const bool afix = a.fix_rec != nullptr;   // the selective guard (wave-uniform: a kernel argument)
   const bool amax = a.max_w != nullptr;   // the max-weight sample of every ray (wave-uniform: a kernel argument)
   if (comp && a.m_chunks) {
     // Rays of m = N / 64 chunks (N = 128, 192, ...): a ray's chunks sit on different waves, possibly in different groups
@@ -203,16 +221,54 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         const float w = L[ci].alpha * Tr;
         const int64_t s_ = grp * GS + c * 64 + le;
         if (okc[ci] && a.weights) a.weights[s_] = w;
-        nscomp::RayAccum A;
-        if (okc[ci]) {
-          A.r += w * L[ci].cr; A.g += w * L[ci].cg; A.b += w * L[ci].cb;
-          A.depth += w * zc[ci];
-          A.acc += w;
-        }
+        auto shares = [&]() {                                     // the lane's share of the chunk's five sums
+          nscomp::RayAccum X;
+          if (okc[ci]) {
+            X.r += w * L[ci].cr; X.g += w * L[ci].cg; X.b += w * L[ci].cb;
+            X.depth += w * zc[ci];
+            X.acc += w;
+          }
+          return X;
+        };
+        nscomp::RayAccum A = shares();
         nscomp::reduce_sums<64>(A, le);
         if (le == 63) {
           *rec.scal(kCS + 8 * c + 0) = A.r; *rec.scal(kCS + 8 * c + 1) = A.g; *rec.scal(kCS + 8 * c + 2) = A.b;
           *rec.scal(kCS + 8 * c + 3) = A.depth; *rec.scal(kCS + 8 * c + 4) = A.acc;
+        }
+        if (__builtin_expect(afix && pos == m - 1, 0)) {
+          // The selective guard, on the chunk that ends a ray (wave-uniform): lane 63 holds the ray's last sample.  A sigma within
+          // fix_thr of zero (a NaN compares false: a NaN ray stays NaN) flags the ray: the wave writes the record's operands
+          // (kFixLongFloats above) at the slot lane 63 draws, and phase 3 adds the earlier chunks' totals through kFIX.
+          const int i = c * 64 + le;
+          const v4f qv = *rec.raw(i);                             // (this group's until the barrier below)
+          const bool flag = le == 63 && okc[ci] && __builtin_fabsf(qv.w) < a.fix_thr;
+          if (le == 63 && !flag) *rec.slot(c) = 0u;
+          if (__builtin_amdgcn_ballot_w64(flag)) {
+            uint32_t slot = 0;
+            if (le == 63) slot = atomicAdd(a.fix_count, 1u);
+            slot = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(slot), 63));
+            float* q = a.fix_rec + static_cast<size_t>(slot) * kFixLongFloats;
+            if (le == 63) {
+              const v2f zd = *rec.zd(par, i);
+              const uint64_t r = static_cast<uint64_t>((C0 + c) / m);
+              *rec.slot(c) = slot + 1u;
+              q[5] = Tr; q[6] = qv.x; q[7] = qv.y;                                     // (floats 0 .. 4 are phase 3's)
+              reinterpret_cast<float4*>(q)[2] = make_float4(qv.z, zd.x, zd.y, __builtin_bit_cast(float, static_cast<uint32_t>(r)));
+              q[12] = __builtin_bit_cast(float, static_cast<uint32_t>(r >> 32));
+            }
+            // x62, then u2 .. u6: lane 63 - SW after the first log2 SW steps of the 64-lane reduction, which are reduce5<SW>'s own
+            nsmlp::static_for<6>([&](auto k_) {
+              constexpr int k = decltype(k_)::value;
+              constexpr int SW = 1 << k;
+              nscomp::RayAccum X = shares();
+              if constexpr (k > 0) nscomp::reduce_sums<SW>(X, le);
+              if (le == (k == 0 ? 62 : 63 - SW)) {
+                float* u = q + kFixLongOperands + 5 * k;
+                u[0] = X.r; u[1] = X.g; u[2] = X.b; u[3] = X.depth; u[4] = X.acc;
+              }
+            });
+          }
         }
         if (__builtin_expect(amax, 0)) {   // the chunk's max-weight sample (a ray's chunks are combined in order in phase 3)
           float best = w;
@@ -239,11 +295,21 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
           tot.carry = *rec.scal(kOPEN + 8 * par); tot.r = *rec.scal(kOPEN + 8 * par + 1); tot.g = *rec.scal(kOPEN + 8 * par + 2);
           tot.b = *rec.scal(kOPEN + 8 * par + 3); tot.depth = *rec.scal(kOPEN + 8 * par + 4); tot.acc = *rec.scal(kOPEN + 8 * par + 5);
         }
-        for (int cc = first < 0 ? 0 : first; cc <= c; ++cc) {
+        auto add_chunk = [&](int cc) {
           tot.carry = tot.carry * *rec.scal(kCP + cc);
           tot.r = tot.r + *rec.scal(kCS + 8 * cc); tot.g = tot.g + *rec.scal(kCS + 8 * cc + 1); tot.b = tot.b + *rec.scal(kCS + 8 * cc + 2);
           tot.depth = tot.depth + *rec.scal(kCS + 8 * cc + 3); tot.acc = tot.acc + *rec.scal(kCS + 8 * cc + 4);
+        };
+        for (int cc = first < 0 ? 0 : first; cc < c; ++cc) add_chunk(cc);
+        if (__builtin_expect(afix && ends, 0)) {     // a flagged ray: its totals before the last chunk, for the fix-up
+          const uint32_t slot = *rec.slot(c);
+          if (slot) {
+            float* q = a.fix_rec + static_cast<size_t>(slot - 1u) * kFixLongFloats;
+            reinterpret_cast<float4*>(q)[0] = make_float4(tot.r, tot.g, tot.b, tot.depth);
+            q[4] = tot.acc;
+          }
         }
+        add_chunk(c);
         // the ray's max-weight sample: the open ray's so far, then its chunks of this group in order (a later chunk's samples
         // have larger indices: it wins only where nscomp::beats says so without the index -- a larger weight, or the first NaN)
         float mw = 0.0f, mz = 0.0f, mr = 0.0f, mg = 0.0f, mb = 0.0f;

@@ -51,10 +51,11 @@ struct Nerf16Args {
   // groups -- lcm(group samples, N) samples, whole rays -- before it jumps, so that a ray's chunks meet in one workgroup and
   // the transmittance / sums of the ray that is open at a group boundary carry over in LDS
   int m_chunks, sg_groups;
-  // the selective guard (single-chunk rays): a ray whose own sigma of the last sample is within fix_thr of zero -- where the step
-  // alpha = step(sigma) could flip under the 16-bit rounding -- leaves a 16-float record {tree sums r g b depth acc, T, raw rgb of
-  // the last sample, its z and dist, ray index lo / hi} at slot atomicAdd(fix_count) of fix_rec (ns_fix_last_sample re-evaluates
-  // sigma through the fp32-grade handle and repeats the last addition)
+  // the selective guard: a ray whose own sigma of the last sample is within fix_thr of zero -- where the step
+  // alpha = step(sigma) could flip under the 16-bit rounding -- leaves a record at slot atomicAdd(fix_count) of fix_rec.  Rays of
+  // one chunk: 16 floats {tree sums r g b depth acc, T, raw rgb of the last sample, its z and dist, ray index lo / hi}
+  // (ns_fix_last_sample re-evaluates sigma through the fp32-grade handle and repeats the last addition).  Rays of several chunks:
+  // nsepi::kFixLongFloats floats, the operands of the last chunk's additions as well (ns_comp_epilogue.h, ns_fix_last_sample_long)
   float fix_thr;
   uint32_t* fix_count;
   float* fix_rec;
@@ -581,9 +582,8 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
   if (comp) {
     nsepi::set_comp_args(a, comp, N);
     if (comp->fix_rec_dev) {
-      if (N > 64 || comp->sigma_last_dev || comp->max_w_dev) {
-        ns::set_error("the selective guard serves rays of one chunk (N <= 64) and excludes the every-ray guard's sigma array and "
-                      "the max-weight sample");
+      if (comp->sigma_last_dev || comp->max_w_dev) {
+        ns::set_error("the selective guard excludes the every-ray guard's sigma array and the max-weight sample");
         return NS_E_INVALID;
       }
       a.fix_thr = comp->fix_thr; a.fix_count = comp->fix_count_dev; a.fix_rec = comp->fix_rec_dev;

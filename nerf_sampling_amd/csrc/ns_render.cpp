@@ -48,14 +48,16 @@ ChainLayout chain_layout(Carve& ws, int64_t R, int N) {
 }
 
 struct FusedLayout { RaySlices rays; float *mean, *z_last, *raw_last; uint32_t* fix_count; float* fix_rec; RaySlices fix_rays; };
-FusedLayout fused_layout(Carve& ws, int64_t R) {
+// long_records: the selective guard on rays of several chunks (ns_render_args::guard_long_selective) -- its records are
+// NS_FIX_LONG_FLOATS floats; every other call keeps the layout and the size it has had
+FusedLayout fused_layout(Carve& ws, int64_t R, bool long_records) {
   FusedLayout l;
   l.rays = take_rays(ws, R);
   l.mean = ws.take(R * 4);
   l.z_last = ws.take(R * 4);          // the every-ray guard's depth and raw of the last sample; the selective guard's z and raw
   l.raw_last = ws.take(R * 16);       // of the flagged rays' last samples
-  l.fix_count = reinterpret_cast<uint32_t*>(ws.take(256));   // the selective guard: counter, 64-byte records, compacted rays
-  l.fix_rec = ws.take(R * 64);
+  l.fix_count = reinterpret_cast<uint32_t*>(ws.take(256));   // the selective guard: counter, records (64 bytes for a ray of one
+  l.fix_rec = ws.take(R * (long_records ? NS_FIX_LONG_FLOATS * 4 : 64));   // chunk, 192 for one of several), compacted rays
   l.fix_rays = take_rays(ws, R);
   return l;
 }
@@ -209,7 +211,14 @@ int ns_render_fused_supported(const ns_weights* nerf, int mode, int N) {
 int64_t ns_render_fused_workspace_bytes(int64_t R) {
   if (R < 0) return 0;
   Carve ws;
-  fused_layout(ws, R);
+  fused_layout(ws, R, false);
+  return ws.total;
+}
+
+int64_t ns_render_fused_guard_long_workspace_bytes(int64_t R) {
+  if (R < 0) return 0;
+  Carve ws;
+  fused_layout(ws, R, true);
   return ws.total;
 }
 
@@ -225,9 +234,16 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   NS_REQUIRE(!a->noise_dev, "uniform placement takes no noise");
   int rc = a->nerf_guard ? guard_check(a) : NS_OK;
   if (rc != NS_OK) return rc;
+  // (the fix-up launches the split-operand MLP kernel with a device-side count: another packing of the guard handle, e.g. fp32,
+  // takes the every-ray pass through the generic dispatch.  An f16x3 field is fp32-grade itself: its guard is the every-ray one)
+  // Rays of several chunks take the selective form only when the caller opts in (guard_long_selective): an unflagged ray keeps
+  // its 16-bit sigma, and callers of N > 64 have had the every-ray guard's bits on every ray.
+  const bool long_rays = a->N > 64;
+  const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && (!long_rays || a->guard_long_selective == 1) &&
+                         a->nerf_guard->dtype == NS_DTYPE_F16X3 && a->nerf_guard->layout == 16 && a->nerf->dtype != NS_DTYPE_F16X3;
   FusedLayout l;
   Rays r;
-  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = fused_layout(ws, R); return l.rays; }, &r, stream);
+  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = fused_layout(ws, R, selective && long_rays); return l.rays; }, &r, stream);
   if (rc != NS_OK || r.R == 0) return rc;
   rc = ns_depthnet_forward(a->depthnet, r.o, r.d, r.R, a->near_, a->far_, a->sphere_radius, l.mean, stream);
   if (rc != NS_OK) return rc;
@@ -236,10 +252,6 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   c.mean_dev = l.mean; c.std_ = a->std_; c.white_bkgd = a->white_bkgd;
   set_outputs(c, out);
   c.z_out_dev = a->z_dev; c.pts_out_dev = a->pts_dev;
-  // (the fix-up launches the split-operand MLP kernel with a device-side count: another packing of the guard handle, e.g. fp32,
-  // takes the every-ray pass through the generic dispatch.  An f16x3 field is fp32-grade itself: its guard is the every-ray one)
-  const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && a->N <= 64 && a->nerf_guard->dtype == NS_DTYPE_F16X3 &&
-                         a->nerf_guard->layout == 16 && a->nerf->dtype != NS_DTYPE_F16X3;
   if (selective) {         // the kernel flags the rays itself; their last samples are re-evaluated after it
     c.fix_thr = a->guard_threshold;
     c.fix_count_dev = l.fix_count;
@@ -260,13 +272,18 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
   if (!selective) return NS_OK;
   const RaySlices& fr = l.fix_rays;
-  rc = ns_fix_gather(l.fix_rec, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view, l.z_last, stream);
+  rc = ns_fix_gather(l.fix_rec, long_rays ? NS_FIX_LONG_FLOATS : 16, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view,
+                     l.z_last, stream);
   if (rc != NS_OK) return rc;
   rc = ns_nerf_forward_x3(a->nerf_guard, nullptr, fr.o, fr.d, l.z_last, fr.view, nullptr, r.R, 1, l.raw_last,
                           ns::as_stream(stream), l.fix_count, nullptr);
   if (rc != NS_OK) return rc;
-  return ns_fix_last_sample(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride, out.disp,
-                            out.disp_stride, out.weights, out.depth, out.acc, stream);
+  rc = (long_rays ? ns_fix_last_sample_long : ns_fix_last_sample)(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd,
+                                                                  out.rgb, out.rgb_stride, out.disp, out.disp_stride, out.weights,
+                                                                  out.depth, out.acc, stream);
+  if (rc != NS_OK || !a->guard_count_dev) return rc;
+  NS_HIP(hipMemcpyAsync(a->guard_count_dev, l.fix_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, ns::as_stream(stream)));
+  return NS_OK;
 }
 
 // ---- the one-kernel renderer with forward-mode tangents in the DepthNet depth (ns_tangent.h, instantiated by

@@ -635,7 +635,8 @@ def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer
         out = ops.render_rays_depthnet(dn_w, net_w, rays=(rays_o, rays_d, viewdirs),
                                        n_samples=trainer.n_depth_samples, mode=trainer.sampling_mode, std=trainer.distance,
                                        near=dn.near, far=dn.far, sphere_radius=float(dn.sphere_radius.reshape(-1)[0]),
-                                       white_bkgd=True, extras=True, device=rays_o.device, mlp_events=ev, guard=guard_w)
+                                       white_bkgd=True, extras=True, device=rays_o.device, mlp_events=ev, guard=guard_w,
+                                       guard_long_rays=ops.guard_long_rays())
         if sink is not None:
             sink.release(after=ev[0])    # the PREVIOUS chunk's host copies start with this chunk's MLP kernel
             if held is not None and held is not sink:

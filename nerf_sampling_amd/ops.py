@@ -79,10 +79,27 @@ _guard_threshold = 16.0
 # frames within 0.03 dB but a 60-row band can read 0.06 (tools/guard_experiment.py, tests/test_scene_psnr.py): the economy setting,
 # built for the production trunk (ten layers, 256 wide; any other shape falls back to "f16x3").
 _guard_depthnet = "f16x3"
+# Which form of the guard rays of several 64-sample chunks take in the one-kernel renderer (n_samples = 128 .. 512,
+# ns_render_args::guard_long_selective).  "every" (the default): every ray, before the kernel, whatever the threshold -- the
+# every-ray guard's bits on all rays.  "selective": as n_samples <= 64 does -- the kernel flags the rays within the threshold, and
+# an unflagged ray whose step flips on its 16-bit sigma keeps the 16-bit one.
+_GUARD_LONG_RAYS = ("every", "selective")
+_guard_long_rays = "every"
 
 
-def set_psnr_guard(on: bool, threshold: Optional[float] = None, depthnet: Optional[str] = None) -> None:
-    global _psnr_guard, _guard_threshold, _guard_depthnet
+def _check_guard_long_rays(value) -> str:
+    if value not in _GUARD_LONG_RAYS:
+        raise ValueError(f"guard_long_rays: 'every' or 'selective', got {value!r}")
+    return value
+
+
+def set_psnr_guard(on: bool, threshold: Optional[float] = None, depthnet: Optional[str] = None,
+                   long_rays: Optional[str] = None) -> None:
+    """``long_rays``: "every" or "selective", the guard's form for rays of several chunks (see _guard_long_rays); None leaves
+    it as it is."""
+    global _psnr_guard, _guard_threshold, _guard_depthnet, _guard_long_rays
+    if long_rays is not None:
+        _check_guard_long_rays(long_rays)
     _psnr_guard = bool(on)
     if threshold is not None:
         if not threshold >= 0.0:
@@ -92,17 +109,25 @@ def set_psnr_guard(on: bool, threshold: Optional[float] = None, depthnet: Option
         if depthnet not in ("f16m", "f16x3"):
             raise ValueError("the guard's DepthNet runs on 'f16m' or 'f16x3' operands")
         _guard_depthnet = depthnet
+    if long_rays is not None:
+        _guard_long_rays = long_rays
 
 
 def psnr_guard() -> bool:
     return _psnr_guard
 
 
+def guard_long_rays() -> str:
+    """The module's setting of the guard's form for rays of several chunks (set_psnr_guard(long_rays=...))."""
+    return _guard_long_rays
+
+
 def psnr_guard_handles(depth_net, nerf, mode: Optional[str] = None, n_samples: Optional[int] = None):
     """(DepthNet handle, field handle, guard handle or None) for the current compute dtype and guard setting: what the
     one-call renderers take.  ``depth_net`` / ``nerf``: this package's DepthNet / NeRF modules.  Given the sampling ``mode``
     / ``n_samples`` of the render, the guard is None where it does not apply: the guard pass is defined for uniform placement
-    with n_samples >= 2."""
+    with n_samples >= 2.  Which rays the guard re-evaluates is the caller's to pass on: guard_threshold (None = the module's)
+    and guard_long_rays=ops.guard_long_rays(), as nerf_utils.render_rays_test and parallel.hip_row_renderer do."""
     dn, nf = depth_net.packed(), nerf.packed()
     applies = mode in (None, "uniform") and (n_samples is None or n_samples >= 2)
     guard = nerf.packed("f16x3") if (_psnr_guard and applies and nf.dtype in ("bf16", "f16")) else None
@@ -520,13 +545,13 @@ def _rgb_disp_outputs(a, R: int, device, shard: Optional[Tensor]):
     return {"rgb": shard[:R, :3], "disp": shard[:R, 3]}
 
 
-def _extras_names(extras, per_sample: Tuple[str, ...]) -> Tuple[str, ...]:
+def _extras_names(extras, per_sample: Tuple[str, ...], more: Tuple[str, ...] = ()) -> Tuple[str, ...]:
     """``extras`` of a one-call renderer -> the names asked for: True = its per-sample arrays, False / None = none, or a tuple
-    drawn from those and the per-ray maps "depth" / "acc"."""
+    drawn from those, the per-ray maps "depth" / "acc" and what else the renderer offers (``more``)."""
     if isinstance(extras, (bool, int, np.bool_)):
         return per_sample if extras else ()
     names = tuple(extras or ())
-    allowed = per_sample + ("depth", "acc")
+    allowed = per_sample + ("depth", "acc") + more
     if not set(names) <= set(allowed):
         raise ValueError(f"extras: True, False or a tuple of {', '.join(repr(n) for n in allowed)}, got {extras!r}")
     return names
@@ -546,7 +571,7 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
                          white_bkgd: bool = True, extras=False, workspace: Optional[RenderWorkspace] = None,
                          device="cuda", mlp_events=None, shard: Optional[Tensor] = None,
                          one_kernel: Optional[bool] = None, guard: Optional[PackedWeights] = None,
-                         guard_threshold: Optional[float] = None):
+                         guard_threshold: Optional[float] = None, guard_long_rays: str = "every"):
     """DepthNet -> placement -> NeRF MLP -> compositing as one C call.
 
     rays = (o, d, viewdirs) device tensors, or camera = (H, W, K, c2w, row0, row1) to generate
@@ -565,11 +590,20 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     composites with dist = 1e10, so that alpha = step(sigma) -- is then evaluated a second time through it and its sigma
     replaces the 16-bit one (R of the R * N samples; uniform placement only).  Pair it with an "f16x3" DepthNet handle:
     the two together are the PSNR guard of the 16-bit paths (see psnr_guard_handles).
-    ``guard_threshold`` (one-kernel renderer, n_samples <= 64): None = the module setting (set_psnr_guard, 16.0); > 0 = only the
-    rays whose own sigma of the last sample lies within it of zero are re-evaluated, after the kernel, on a compacted list
-    (the same bits as the every-ray guard wherever |sigma16 - sigma32| stays below it); 0 = every ray, before the kernel.
+    ``guard_threshold`` (one-kernel renderer; n_samples <= 64, or 128 .. 512 under guard_long_rays="selective"): None = the
+    module setting (set_psnr_guard, 16.0); > 0 = only the rays whose own sigma of the last sample lies within it of zero are
+    re-evaluated, after the kernel, on a compacted list (the same bits as the every-ray guard wherever |sigma16 - sigma32|
+    stays below it); 0 = every ray, before the kernel.
+    ``guard_long_rays``: "every" (default) or "selective" -- the guard's form for rays of several 64-sample chunks (n_samples a
+    multiple of 64 in [128, 512]) in the one-kernel renderer on a 16-bit field with an "f16x3" guard and a threshold > 0.
+    "every": every ray before the kernel, whatever the threshold.  "selective": the kernel flags the rays within the threshold
+    as it does for n_samples <= 64, and an unflagged ray whose step flips on its 16-bit sigma keeps the 16-bit one.  Ignored
+    where it does not apply (n_samples <= 64, an f16x3 field, threshold 0, another guard packing, the chain).
+    extras "guard_count": a 1-element int32 device tensor, initialised to -1; a call that ran the selective form (either ray
+    length) writes the number of flagged rays there, on the stream, without a host synchronisation.
     """
-    names = _extras_names(extras, ("z", "weights", "pts"))
+    names = _extras_names(extras, ("z", "weights", "pts"), ("guard_count",))
+    _check_guard_long_rays(guard_long_rays)
     lib = _lib.load()
     a = _lib.RenderArgs()
     a.depthnet, a.nerf = depthnet.handle, nerf.handle
@@ -578,7 +612,7 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
         out = {"rgb": torch.empty((0, 3), device=dev0), "disp": torch.empty((0,), device=dev0)}
         empty = dict(z=torch.empty((0, n0), device=dev0), weights=torch.empty((0, 0 if n0 == 1 else n0), device=dev0),
                      pts=torch.empty((0, n0, 3), device=dev0), depth=torch.empty((0,), device=dev0),
-                     acc=torch.empty((0,), device=dev0))
+                     acc=torch.empty((0,), device=dev0), guard_count=torch.full((1,), -1, dtype=torch.int32, device=dev0))
         out.update((k, empty[k]) for k in names)
         return out
     R, device, keep = _set_ray_source(a, rays, camera, device)
@@ -596,7 +630,10 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
         raise NotImplementedError(f"the one-kernel renderer needs uniform placement, a bf16 / f16 / f16x3 field with view directions and "
                                   f"n_samples a power of two in [2, 64] or a multiple of 64 up to 512 (mode {mode!r}, n_samples {N}, dtype {getattr(nerf, 'dtype', '?')})")
     use_fused = fused_ok if one_kernel is None else bool(one_kernel)
-    nbytes = int(lib.ns_render_fused_workspace_bytes(R) if use_fused else lib.ns_render_workspace_bytes(R, N))
+    if use_fused and guard is not None and guard_long_rays == "selective" and N > 64:   # 192-byte records (ns_render_args)
+        nbytes = int(lib.ns_render_fused_guard_long_workspace_bytes(R))
+    else:
+        nbytes = int(lib.ns_render_fused_workspace_bytes(R) if use_fused else lib.ns_render_workspace_bytes(R, N))
     _set_workspace(a, workspace, nbytes, device)
     out = _rgb_disp_outputs(a, R, device, shard)
     # one sample: the reference's weights are [R, 0] (its dists are empty) and ns_raw2outputs writes none
@@ -611,6 +648,10 @@ def render_rays_depthnet(depthnet: PackedWeights, nerf: PackedWeights, *, rays=N
     if guard is not None:
         a.nerf_guard = guard.handle
         a.guard_threshold = float(_guard_threshold if guard_threshold is None else guard_threshold)
+        a.guard_long_selective = int(guard_long_rays == "selective")
+    if "guard_count" in names:
+        out["guard_count"] = torch.full((1,), -1, dtype=torch.int32, device=device)
+        a.guard_count_dev = out["guard_count"].data_ptr()
     if use_fused:
         check(lib.ns_render_rays_fused(C.byref(a), _stream(device)), "ns_render_rays_fused")
     else:
