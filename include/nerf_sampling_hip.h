@@ -414,6 +414,19 @@ typedef struct ns_gemm_problem {
 int ns_gemm_fused_batched(const ns_gemm_problem* problems_host, int count, void* stream);
 /* out[j] = sum_i X[i*ld + j]  (bias gradient) */
 int ns_colsum(const float* X_dev, int64_t ld, int M, int N, float* out_dev, void* stream);
+/* Grad-weight GEMM of the field fit, split over workgroups along the reduced dimension (split-K):
+ *   dW[n*ldw + k] (+)= sum_m dy[m*dy_row_stride + n*dy_col_stride] * x[m*x_row_stride + k],   db[n] = sum_m dy[m, n]
+ * for m < rows in [1, 2^31), n < N <= 512, k < K <= 512 (larger N or K: NS_E_UNSUPPORTED); x is contiguous along k.  accumulate
+ * (0 / 1) adds to dW; db_dev may be NULL and is overwritten otherwise.  The rows are cut into ns_gemm_wgrad_splits slices, a pure
+ * function of (rows, N, K) -- not of the device -- that is 1 for rows <= 1024; each workgroup reduces one slice for one output
+ * tile.  With one split dW and db are written directly; otherwise the partial tiles go to workspace_dev (at least
+ * ns_gemm_wgrad_workspace_bytes(rows, N, K) = splits * (N * K + N) * 4 rounded up to 256 bytes; 0 and unused with one split) and
+ * a second launch sums them in split order: no floating-point atomics, the same bits on every call.                          */
+int ns_gemm_wgrad_splits(int64_t rows, int N, int K);
+int64_t ns_gemm_wgrad_workspace_bytes(int64_t rows, int N, int K);
+int ns_gemm_wgrad(const float* dy_dev, int64_t dy_row_stride, int64_t dy_col_stride, const float* x_dev,
+                  int64_t x_row_stride, int64_t rows, int N, int K, float* dW_dev, int64_t ldw, int accumulate,
+                  float* db_dev, void* workspace_dev, void* stream);
 /* activations in place: act 0 none, 1 ReLU, 2 LeakyReLU(0.01), 3 sigmoid; backward scales dy by act'(.)
  * evaluated from the activation OUTPUT y                                                            */
 int ns_act_forward(float* y_dev, int64_t n, int act, void* stream);

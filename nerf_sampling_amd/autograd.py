@@ -94,6 +94,40 @@ def linear_backward_weight(dy: Tensor, x: Tensor):
     return dW, db
 
 
+_WGRAD_WORKSPACE = {}        # device -> byte tensor: the split-K partial tiles of ns_gemm_wgrad, one buffer per device
+
+
+def _wgrad_workspace(dev, nbytes: int) -> Optional[Tensor]:
+    """The device's split-K workspace, grown on demand (calls on one stream run in order, so one buffer serves them all)"""
+    if nbytes == 0:
+        return None
+    ws = _WGRAD_WORKSPACE.get(dev)
+    if ws is None or ws.numel() < nbytes:
+        ws = _WGRAD_WORKSPACE[dev] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def linear_backward_weight_splitk(dy: Tensor, x: Tensor, want_db: bool = True):
+    """dW = dy.T @ x [N,K], db = dy.sum(0) [N] (None without ``want_db``) on ns_gemm_wgrad: the rows are split over workgroups
+    and the slices summed in a fixed order.  dy [M,N] and x [M,K] may be strided views (x contiguous along K)."""
+    lib = _lib.load()
+    if not (dy.is_cuda and x.is_cuda and dy.dtype == torch.float32 and x.dtype == torch.float32):
+        raise RuntimeError("dy and x must be float32 tensors on the GPU; this path has no CPU fallback")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError(f"dy [M,N] and x [M,K] expected, got {tuple(dy.shape)} and {tuple(x.shape)}")
+    if x.stride(1) != 1 and x.shape[1] > 1:
+        x = x.contiguous()
+    M, N = dy.shape
+    K = x.shape[1]
+    dev = dy.device
+    dW = torch.empty((N, K), dtype=torch.float32, device=dev)
+    db = torch.empty((N,), dtype=torch.float32, device=dev) if want_db else None
+    ws = _wgrad_workspace(dev, int(lib.ns_gemm_wgrad_workspace_bytes(M, N, K)))
+    check(lib.ns_gemm_wgrad(_ptr(dy), dy.stride(0), dy.stride(1), _ptr(x), x.stride(0), M, N, K, _ptr(dW), K, 0, _ptr(db),
+                            _ptr(ws), _stream(dev)), "ns_gemm_wgrad")
+    return dW, db
+
+
 def act_backward_(dy: Tensor, y: Tensor, act: int) -> Tensor:
     if act != NONE:
         check(_lib.load().ns_act_backward(_ptr(dy), _ptr(y), dy.numel(), act, _stream(dy.device)), "ns_act_backward")
@@ -204,6 +238,108 @@ def place_samples(o: Tensor, d: Tensor, mean: Tensor, n_samples: int, mode: str,
     return PointsAlongRays.apply(o, d, z), z
 
 
+# ---- the NeRF layer by layer: shared by NerfInputGrad (frozen field) and NerfFunction (field fit) --------------------------
+def _nerf_layers_forward(net, xe: Tensor, ve: Optional[Tensor], want_raw: bool):
+    """NeRF.forward (run_nerf_helpers.py:114-133) on _gemm with the ReLU in the epilogue, from the module's live parameters.
+    xe [M,63], ve [M,27] (view-direction head only).  Returns (raw [M,C] or None, saved): saved holds what the backward reads --
+    ``acts`` (each trunk layer's output), ``ins`` (each trunk layer's input: xe, the layer below's output or the cat[xe, h]
+    buffer), ``h`` (the trunk's output), and for the view-direction head ``vin`` = cat[feature, ve] and ``hv``."""
+    skips = net._check_supported()
+    M = xe.shape[0]
+
+    def fwd(x, lin, act, out=None):    # act(x W^T + b), activation in the GEMM epilogue
+        return _gemm(x, x.stride(0), 1, lin.weight, lin.weight.shape[1], 1, lin.bias, M, lin.weight.shape[0], x.shape[1], act=act,
+                     out=out)
+
+    acts, ins = [], []
+    h = xe
+    for i, lin in enumerate(net.pts_linears):               # (run_nerf_helpers.py:114-118)
+        ins.append(h)
+        h = fwd(h, lin, RELU)
+        acts.append(h)
+        if i in skips:
+            h = torch.cat([xe, h], -1)
+    saved = dict(xe=xe, acts=acts, ins=ins, h=h, skips=skips)
+    raw = None
+    if net.use_viewdirs:                  # alpha / feature / views / rgb head (run_nerf_helpers.py:119-131)
+        feat = fwd(h, net.feature_linear, NONE)
+        vin = torch.cat([feat, ve], -1)
+        hv = fwd(vin, net.views_linears[0], RELU)
+        saved.update(vin=vin, hv=hv)
+        if want_raw:
+            raw = torch.empty((M, 4), dtype=torch.float32, device=xe.device)
+            fwd(hv, net.rgb_linear, NONE, out=raw[:, :3])
+            fwd(h, net.alpha_linear, NONE, out=raw[:, 3:4])
+    elif want_raw:                        # output_linear head (:132-133)
+        raw = fwd(h, net.output_linear, NONE)
+    return raw, saved
+
+
+def _nerf_layers_backward(net, saved, draw: Tensor, weight_grad=None, want_input: bool = True) -> Optional[Tensor]:
+    """The transposed chain from d raw down to the embedded point: returns d xe [M,63] (None without ``want_input``: the
+    grad-input GEMM of layer 0 is then skipped).  ``weight_grad(lin, dy, x)`` is called once per Linear with the gradient of its
+    pre-activation output and its input."""
+    xe, acts, skips = saved["xe"], saved["acts"], saved["skips"]
+    lins = list(net.pts_linears)
+    M = xe.shape[0]
+    h = saved["h"]
+
+    def bwd(dy, lin, n_cols=None, dref=None):   # dy W[:, :n_cols], times relu'(dref) when the layer below has a ReLU
+        Wt = lin.weight
+        return _gemm(dy, dy.stride(0), 1, Wt, 1, Wt.shape[1], None, M, n_cols or Wt.shape[1], dy.shape[1],
+                     dact=RELU if dref is not None else 0, dact_ref=dref)
+
+    wg = weight_grad or (lambda lin, dy, x: None)
+    last = len(lins) - 1
+    # d h_last: through the head, then times relu'(trunk output) -- the trunk's last activation.  When that output was
+    # concatenated with the embedding (a skip after the last layer cannot occur: _check_supported), plain [M, W].
+    if net.use_viewdirs:
+        hv = saved["hv"]
+        g = _dev(draw, "draw").reshape(-1, 4)
+        g_rgb, g_sigma = g[:, :3], g[:, 3:4]                         # strided views, no copies
+        wg(net.rgb_linear, g_rgb, hv)
+        d_hv = bwd(g_rgb, net.rgb_linear, dref=hv)
+        wg(net.views_linears[0], d_hv, saved["vin"])
+        d_feat = bwd(d_hv, net.views_linears[0], n_cols=net.W)
+        wg(net.feature_linear, d_feat, h)
+        d_h = bwd(d_feat, net.feature_linear)
+        # + the sigma head, accumulated in place, then the trunk's last ReLU on the sum
+        wg(net.alpha_linear, g_sigma, h)
+        Wa = net.alpha_linear.weight
+        _gemm(g_sigma, g_sigma.stride(0), 1, Wa, 1, Wa.shape[1], None, M, Wa.shape[1], 1, out=d_h, accumulate=True,
+              dact=RELU, dact_ref=acts[last])
+    else:                             # output_linear head (:132-133): raw = h W_out^T + b, no view directions
+        g = _dev(draw, "draw").reshape(-1, net.output_channels)
+        wg(net.output_linear, g, h)
+        d_h = bwd(g, net.output_linear, dref=acts[last])
+    d_xe = torch.zeros_like(xe) if want_input else None
+    for i in range(last, -1, -1):     # d_h is the gradient w.r.t. the PRE-activation of layer i here
+        wg(lins[i], d_h, saved["ins"][i])
+        below = i - 1
+        if below >= 0 and below in skips:               # layer i saw cat[xe, h_{i-1}]
+            d_in = bwd(d_h, lins[i])                     # [M, 63 + W]: the xe part has no activation
+            if want_input:
+                d_xe = d_xe + d_in[:, :63]
+            d_h = d_in[:, 63:].contiguous()
+            act_backward_(d_h, acts[below], RELU)
+        elif below >= 0:
+            d_h = bwd(d_h, lins[i], dref=acts[below])
+        elif want_input:
+            d_h = bwd(d_h, lins[i])                      # layer 0's input is xe
+    return d_xe + d_h if want_input else None
+
+
+def _nerf_embed(pts: Tensor, viewdirs: Optional[Tensor], use_viewdirs: bool):
+    """flat points [M,3], their embedding [M,63] and the samples' embedded view directions [M,27] (or None)"""
+    flat = pts.reshape(-1, 3).contiguous()
+    xe = ops.posenc(flat, 10)
+    ve = None
+    if use_viewdirs:
+        dirs = viewdirs[:, None].expand(pts.shape).reshape(-1, 3).contiguous()
+        ve = ops.posenc(dirs, 4)
+    return flat, xe, ve
+
+
 # ---- frozen NeRF, gradient w.r.t. the input points -------------------------------------------------------
 class NerfInputGrad(torch.autograd.Function):
     """forward: the fused MFMA kernel; backward: recompute the layers in fp32 (masks for ReLU), then the
@@ -220,63 +356,68 @@ class NerfInputGrad(torch.autograd.Function):
         pts, viewdirs = ctx.saved_tensors
         net = ctx.net
         R, N = pts.shape[0], pts.shape[1]
-        flat = pts.reshape(-1, 3).contiguous()
-        xe = ops.posenc(flat, 10)
-        skips = net._check_supported()
-        lins = list(net.pts_linears)
-        M = xe.shape[0]
-
-        def fwd(x, lin, act):              # act(x W^T + b), activation in the GEMM epilogue
-            return _gemm(x, x.stride(0), 1, lin.weight, lin.weight.shape[1], 1, lin.bias, M, lin.weight.shape[0], x.shape[1], act=act)
-
-        def bwd(dy, lin, n_cols=None, dref=None):   # dy W[:, :n_cols], times relu'(dref) when the layer below has a ReLU
-            Wt = lin.weight
-            return _gemm(dy, dy.stride(0), 1, Wt, 1, Wt.shape[1], None, M, n_cols or Wt.shape[1], dy.shape[1],
-                         dact=RELU if dref is not None else 0, dact_ref=dref)
-
-        acts = []
-        h = xe
-        for i, lin in enumerate(lins):                      # recompute (run_nerf_helpers.py:114-118)
-            h = fwd(h, lin, RELU)
-            acts.append(h)
-            if i in skips:
-                h = torch.cat([xe, h], -1)
-        last = len(lins) - 1
-        # d h_last: through the head, then times relu'(trunk output) -- the trunk's last activation.  When that output was
-        # concatenated with the embedding (a skip after the last layer cannot occur: _check_supported), plain [M, W].
-        if net.use_viewdirs:              # alpha / feature / views / rgb head (run_nerf_helpers.py:119-131)
-            dirs = viewdirs[:, None].expand(pts.shape).reshape(-1, 3).contiguous()
-            ve = ops.posenc(dirs, 4)
-            feat = fwd(h, net.feature_linear, NONE)
-            vin = torch.cat([feat, ve], -1)
-            hv = fwd(vin, net.views_linears[0], RELU)
-            g = _dev(draw, "draw").reshape(-1, 4)
-            g_rgb, g_sigma = g[:, :3], g[:, 3:4]                         # strided views, no copies
-            d_hv = bwd(g_rgb, net.rgb_linear, dref=hv)
-            d_feat = bwd(d_hv, net.views_linears[0], n_cols=net.W)
-            d_h = bwd(d_feat, net.feature_linear)
-            # + the sigma head, accumulated in place, then the trunk's last ReLU on the sum
-            Wa = net.alpha_linear.weight
-            _gemm(g_sigma, g_sigma.stride(0), 1, Wa, 1, Wa.shape[1], None, M, Wa.shape[1], 1, out=d_h, accumulate=True,
-                  dact=RELU, dact_ref=acts[last])
-        else:                             # output_linear head (:132-133): raw = h W_out^T + b, no view directions
-            g = _dev(draw, "draw").reshape(-1, net.output_channels)
-            d_h = bwd(g, net.output_linear, dref=acts[last])
-        d_xe = torch.zeros_like(xe)
-        for i in range(last, -1, -1):     # d_h is the gradient w.r.t. the PRE-activation of layer i here
-            below = i - 1
-            if below >= 0 and below in skips:               # layer i saw cat[xe, h_{i-1}]
-                d_in = bwd(d_h, lins[i])                     # [M, 63 + W]: the xe part has no activation
-                d_xe = d_xe + d_in[:, :63]
-                d_h = d_in[:, 63:].contiguous()
-                act_backward_(d_h, acts[below], RELU)
-            elif below >= 0:
-                d_h = bwd(d_h, lins[i], dref=acts[below])
-            else:
-                d_h = bwd(d_h, lins[i])                      # layer 0's input is xe
-        d_xe = d_xe + d_h
+        flat, xe, ve = _nerf_embed(pts, viewdirs, net.use_viewdirs)
+        _, saved = _nerf_layers_forward(net, xe, ve, want_raw=False)     # recompute (run_nerf_helpers.py:114-118)
+        d_xe = _nerf_layers_backward(net, saved, draw)
         dpts = posenc_backward(flat, d_xe.contiguous(), 10)
         return dpts.reshape(R, N, 3), None, None
+
+
+# ---- the NeRF, gradient w.r.t. its weights (and its points, when they ask for one) -----------------------------------------
+def nerf_params(net) -> List[Tensor]:
+    """The NeRF's parameters in NerfFunction's order: [w, b] of pts_linears, then feature, alpha, views, rgb (view-direction
+    head) or output_linear."""
+    mods = list(net.pts_linears) + ([net.feature_linear, net.alpha_linear, net.views_linears[0], net.rgb_linear]
+                                    if net.use_viewdirs else [net.output_linear])
+    params = []
+    for m in mods:
+        params += [m.weight, m.bias]
+    return params
+
+
+class NerfFunction(torch.autograd.Function):
+    """raw [R,N,C] of NeRF.forward (run_nerf_helpers.py:67-134) from the module's live parameters, layer by layer on
+    ns_gemm_fused (no packed stream: nothing is repacked inside a training loop); the activations are kept.  backward: the
+    grad-input chain NerfInputGrad runs, one ns_gemm_wgrad per Linear for (dW, db), and the gradient of ``pts`` (through the
+    positional encoding) only when pts.requires_grad.  Any ``skips``, both heads, any W <= 256."""
+
+    @staticmethod
+    def forward(ctx, pts: Tensor, viewdirs: Optional[Tensor], net, *params: Tensor):
+        flat, xe, ve = _nerf_embed(pts, viewdirs, net.use_viewdirs)
+        raw, saved = _nerf_layers_forward(net, xe, ve, want_raw=True)
+        ctx.net, ctx.saved, ctx.flat = net, saved, flat
+        ctx.pts_shape = tuple(pts.shape)
+        return raw.reshape(pts.shape[0], pts.shape[1], raw.shape[1])
+
+    @staticmethod
+    def backward(ctx, draw: Tensor):
+        net, saved = ctx.net, ctx.saved
+        params = nerf_params(net)
+        slot = {id(p): k for k, p in enumerate(params)}
+        grads: List[Optional[Tensor]] = [None] * len(params)
+
+        def weight_grad(lin, dy, x):
+            kw, kb = slot[id(lin.weight)], slot[id(lin.bias)]
+            if not (ctx.needs_input_grad[3 + kw] or ctx.needs_input_grad[3 + kb]):
+                return
+            grads[kw], grads[kb] = linear_backward_weight_splitk(dy, x)
+
+        want_pts = ctx.needs_input_grad[0]
+        d_xe = _nerf_layers_backward(net, saved, draw, weight_grad=weight_grad, want_input=want_pts)
+        dpts = posenc_backward(ctx.flat, d_xe.contiguous(), 10).reshape(ctx.pts_shape) if want_pts else None
+        ctx.saved = None
+        return (dpts, None, None, *grads)
+
+
+def nerf_forward_train(net, pts: Tensor, viewdirs: Optional[Tensor]) -> Tensor:
+    """raw [R,N,C] of ``net`` at pts [R,N,3] (viewdirs [R,3], or None for a network without view directions), differentiable in
+    the network's parameters and, when it requires a gradient, in ``pts`` (NerfFunction)."""
+    pts = _dev(pts, "pts")
+    if net.use_viewdirs:
+        viewdirs = _dev(viewdirs, "viewdirs")
+    else:
+        viewdirs = None
+    return NerfFunction.apply(pts, viewdirs, net, *nerf_params(net))
 
 
 # ---- DepthNet, gradient w.r.t. its weights -----------------------------------------------------------------

@@ -34,6 +34,9 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--fused-step", "fused_step", is_flag=True, default=False,
               help="Run the DepthNet branch of the training step as one kernel and the target pass as one call (not in the "
                    "reference; DepthNetTrainer(fused_step=True)).")
+@click.option("--fit-field", "fit_field", is_flag=True, default=False,
+              help="Fit the radiance field itself (trainers.FieldFitter: both NeRFs' weights on the HIP kernels) instead of "
+                   "training the DepthNet; writes {root}/logs/{expname}_field/NNNNNN.tar (not in the reference).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -57,8 +60,35 @@ def main(**kw):
     k.update(ft_path=ft_path, depth_net_path=None, datadir=datadir, basedir=f"{root}/logs")
     if kw["fused_step"]:
         k["fused_step"] = True
+    if kw["fit_field"]:
+        k.update(ft_path=None)
+        return fit_field(load_obj_from_config(cfg=config), kw["iters"])
     trainer = load_obj_from_config(cfg=config)
     trainer.train(N_iters=kw["iters"] + 1)
+
+
+def fit_field(trainer, n_iters):
+    """--fit-field: a FieldFitter built from the trainer's configuration (network shapes, sample counts, learning rate, noise,
+    background) on the trainer's dataset; checkpoints load as ft_path of the DepthNet training and of experiments/render.py."""
+    from nerf_sampling_amd import nerf_utils
+    from nerf_sampling_amd.run_nerf_helpers import NeRF
+    from nerf_sampling_amd.trainers import FieldFitter
+    from nerf_sampling_amd.utils import unfreeze_model
+
+    hwf, poses, _i_test, _i_val, i_train, images, _render_poses = trainer.load_data()
+    trainer.cast_intrinsics_to_right_types(hwf=hwf)
+    trainer.no_reload = True
+    kw_train, _kw_test, _start, _grad_vars, _optimizer = nerf_utils.create_nerf(trainer, NeRF)
+    for key in ("network_fn", "network_fine"):
+        if kw_train[key] is not None:
+            unfreeze_model(kw_train[key])
+    fitter = FieldFitter(kw_train["network_fn"], kw_train["network_fine"], N_samples=trainer.N_samples,
+                         N_importance=trainer.N_importance, lrate=trainer.lrate, lrate_decay=trainer.lrate_decay,
+                         white_bkgd=trainer.white_bkgd, raw_noise_std=trainer.raw_noise_std, perturb=trainer.perturb,
+                         lindisp=trainer.lindisp, near=trainer.near, far=trainer.far)
+    split = dict(images=images, poses=poses, hwf=hwf, i_train=i_train)
+    return fitter.fit(split, n_iters, N_rand=trainer.N_rand, basedir=trainer.basedir, expname=f"{trainer.expname}_field",
+                      i_weights=trainer.i_weights, i_print=trainer.i_print)
 
 
 if __name__ == "__main__":

@@ -348,6 +348,149 @@ class GraphedDepthNetStep:
         return self.img_loss, self.dn_loss, mse2psnr(self.img_loss), None
 
 
+class FieldFitter:
+    """Fit the radiance field itself on the HIP kernels: the vanilla objective the reference's forward implies
+    (sample_as_in_NeRF, nerf_utils.py:497-611) -- coarse depths, coarse field, compositing, importance sampling on the detached
+    weights, fine field on the Nc + Nf depths, compositing, loss = img2mse(rgb) + img2mse(rgb0) -- with the weight gradients of
+    autograd.NerfFunction (ns_gemm_wgrad), autograd.Composite and HipAdam over both networks' parameters.
+
+    ``network_fine=None``: the coarse-only objective when N_importance == 0, else the coarse network runs both passes (as
+    sample_fine_points does).  One module passed as both networks accumulates both passes' gradients into the same tensors.
+    ``near`` / ``far``: the ray bounds (Blender's 2 / 6)."""
+
+    def __init__(self, network_fn, network_fine=None, N_samples=64, N_importance=128, lrate=5e-4, lrate_decay=250,
+                 white_bkgd=True, raw_noise_std=0.0, perturb=1.0, lindisp=False, near=2.0, far=6.0):
+        from .autograd import HipAdam
+
+        self.network_fn, self.network_fine = network_fn, network_fine
+        self.N_samples, self.N_importance = int(N_samples), int(N_importance)
+        self.lrate, self.lrate_decay = float(lrate), lrate_decay
+        self.white_bkgd, self.raw_noise_std = bool(white_bkgd), float(raw_noise_std)
+        self.perturb, self.lindisp = float(perturb), bool(lindisp)
+        self.near, self.far = float(near), float(far)
+        params, seen = [], set()
+        for net in (network_fn, network_fine):
+            for p in ([] if net is None else net.parameters()):
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    params.append(p)
+        self.optimizer = HipAdam(params=params, lr=self.lrate, betas=(0.9, 0.999))
+        self.optimizer.use_device_step()           # one launch for all parameter tensors
+        self.global_step = 0
+
+    def _noise(self, shape, device):
+        if self.raw_noise_std > 0.0:
+            return torch.randn(shape, device=device) * self.raw_noise_std
+        return None
+
+    def forward_loss(self, batch_rays, target, t_rand=None, u=None):
+        """(loss, info) of one batch: batch_rays [2,B,3] (origins, directions), target [B,3].  info: img_loss / img_loss0 (the
+        fine / coarse image losses, detached), rgb / rgb0, z0 [B,Nc] and z [B,Nc+Nf].  ``t_rand`` [B,Nc] / ``u`` [B,Nf]: the
+        stratified and importance draws (drawn here when perturb > 0 and not given)."""
+        from .autograd import composite, nerf_forward_train
+        from .run_nerf_helpers import img2mse
+
+        o, d = ops._dev(batch_rays[0], "rays_o"), ops._dev(batch_rays[1], "rays_d")
+        target = ops._dev(target, "target")
+        B, dev = o.shape[0], o.device
+        viewdirs = d / torch.norm(d, dim=-1, keepdim=True)
+        near = torch.full((B,), self.near, dtype=torch.float32, device=dev)
+        far = torch.full((B,), self.far, dtype=torch.float32, device=dev)
+        if t_rand is None and self.perturb > 0.0:
+            t_rand = torch.rand((B, self.N_samples), device=dev)
+        z0 = ops.coarse_z(near, far, self.N_samples, self.lindisp, t_rand)
+        raw0 = nerf_forward_train(self.network_fn, ops.points_along_rays(o, d, z0), viewdirs)
+        rgb0, _, _, _, _, w0 = composite(raw0, z0, d, self._noise(z0.shape, dev), self.white_bkgd)
+        img_loss0 = img2mse(rgb0, target)
+        info = dict(z0=z0, rgb0=rgb0, img_loss0=img_loss0.detach())
+        if self.N_importance <= 0:
+            info.update(z=z0, rgb=rgb0, img_loss=img_loss0.detach())
+            return img_loss0, info
+        if u is None and self.perturb > 0.0:
+            u = torch.rand((B, self.N_importance), device=dev)
+        z = ops.importance_z(z0, w0.detach(), self.N_importance, u)       # the reference detaches z_samples (Trainer.py:572)
+        fine = self.network_fn if self.network_fine is None else self.network_fine
+        raw = nerf_forward_train(fine, ops.points_along_rays(o, d, z), viewdirs)
+        rgb, _, _, _, _, _ = composite(raw, z, d, self._noise(z.shape, dev), self.white_bkgd)
+        img_loss = img2mse(rgb, target)
+        info.update(z=z, rgb=rgb, img_loss=img_loss.detach())
+        return img_loss + img_loss0, info
+
+    def step(self, batch_rays, target):
+        """One update of both networks: (loss, psnr, psnr0) as device scalars (psnr0: the coarse pass's, None without a fine
+        pass), then the reference's learning-rate decay (Trainer.py:546-551)."""
+        from .run_nerf_helpers import mse2psnr
+
+        loss, info = self.forward_loss(batch_rays, target)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        new_lrate = self.lrate * (0.1 ** (self.global_step / (self.lrate_decay * 1000)))
+        for group in self.optimizer.param_groups:
+            group["lr"] = new_lrate
+        self.global_step += 1
+        psnr0 = mse2psnr(info["img_loss0"]) if self.N_importance > 0 else None
+        return loss.detach(), mse2psnr(info["img_loss"]), psnr0
+
+    def repack(self):
+        """Drop the packed inference streams of both networks: the next render packs the fitted weights."""
+        for net in (self.network_fn, self.network_fine):
+            if net is not None:
+                net.repack()
+
+    def save(self, path):
+        """A checkpoint in the reference's .tar layout (utils.save_state): network_fn_state_dict, network_fine_state_dict,
+        optimizer_state_dict, global_step."""
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        utils.save_state(self.global_step, self.network_fn, self.network_fine, self.optimizer, None, None, path)
+
+    def _blender_source(self, split, N_rand):
+        """Batches of N_rand rays of a Blender split as Trainer.sample_random_ray_batch draws them (one random training image
+        per batch).  ``split``: load_blender_data's (images, poses, render_poses, hwf, i_split), or a dict with images
+        [n,H,W,3|4], poses, hwf and i_train."""
+        if isinstance(split, dict):
+            images, poses, hwf, i_train = split["images"], split["poses"], split["hwf"], split["i_train"]
+        else:
+            images, poses, _render_poses, hwf, i_split = split
+            i_train = i_split[0]
+        images = np.asarray(images)
+        if images.shape[-1] == 4:
+            images = (images[..., :3] * images[..., -1:] + (1.0 - images[..., -1:])) if self.white_bkgd else images[..., :3]
+        tr = Trainer(dataset_type="blender", basedir="", expname="", no_batching=True, datadir="", N_rand=N_rand, device="cuda")
+        tr.cast_intrinsics_to_right_types(hwf)
+        poses_t = torch.tensor(np.asarray(poses), dtype=torch.float32).to("cuda")
+
+        def draw(i):
+            _, _, batch_rays, target = tr.sample_random_ray_batch(None, None, i_train, images, poses_t, i)
+            return batch_rays, target
+
+        return draw
+
+    def fit(self, rays_source, n_iters, N_rand=1024, basedir=None, expname="field", i_weights=10000, i_print=100,
+            evaluate=None):
+        """``n_iters`` steps on batches from ``rays_source``: a loaded Blender split (see _blender_source) or a callable
+        returning (batch_rays [2,B,3], target [B,3]).  With ``basedir`` a checkpoint {basedir}/{expname}/{step:06d}.tar is written
+        every ``i_weights`` steps and at the end.  ``evaluate(fitter)``, if given, runs at every ``i_print`` steps after repack().
+        Both networks are repacked before the call returns.  Returns the last (loss, psnr, psnr0)."""
+        if callable(rays_source):
+            draw = lambda i: rays_source()  # noqa: E731
+        else:
+            draw = self._blender_source(rays_source, N_rand)
+        out = None
+        for i in range(1, int(n_iters) + 1):
+            batch_rays, target = draw(i)
+            out = self.step(batch_rays, target)
+            if i_print and i % i_print == 0:
+                print(f"[FIT] Iter: {self.global_step} Loss: {float(out[0])} PSNR: {float(out[1])}")
+                if evaluate is not None:
+                    self.repack()
+                    evaluate(self)
+            if basedir is not None and (i % i_weights == 0 or i == int(n_iters)):
+                self.save(os.path.join(basedir, expname, "{:06d}.tar".format(self.global_step)))
+        self.repack()
+        return out
+
+
 class BlenderTrainer(Trainer):
     def __init__(self, half_res, white_bkgd, testskip=8, near=2.0, far=6.0, **kwargs):
         self.half_res, self.testskip, self.white_bkgd = half_res, testskip, white_bkgd

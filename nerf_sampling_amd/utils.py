@@ -46,14 +46,17 @@ def unfreeze_model(model):
 
 
 def save_state(global_step, network_fn, network_fine, optimizer, depth_network, sampling_optimizer, path) -> None:
-    """Checkpoint in the reference's layout (utils.py:59-89)."""
+    """Checkpoint in the reference's layout (utils.py:59-89).  ``depth_network`` / ``sampling_optimizer`` may be None (a field
+    fit has neither, trainers.FieldFitter): their keys are then left out, and the file loads as a NeRF checkpoint (ft_path)."""
     data = {
         "global_step": global_step,
         "network_fn_state_dict": network_fn.state_dict(),
         "optimizer_state_dict": optimizer.state_dict(),
-        "sampling_optimizer_state_dict": sampling_optimizer.state_dict(),
-        "depth_network": depth_network.state_dict(),
     }
+    if sampling_optimizer is not None:
+        data["sampling_optimizer_state_dict"] = sampling_optimizer.state_dict()
+    if depth_network is not None:
+        data["depth_network"] = depth_network.state_dict()
     if network_fine is not None:
         data["network_fine_state_dict"] = network_fine.state_dict()
     torch.save(data, path)

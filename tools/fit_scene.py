@@ -105,12 +105,19 @@ def fit_nerf(args):
     dev = torch.device(args.device)
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
-    net = TorchNeRF().to(dev)
+    hip = args.engine == "hip"
+    if hip:     # the package's own module: NerfFunction (ns_gemm_fused / ns_gemm_wgrad), Composite and HipAdam
+        from nerf_sampling_amd import autograd as ag
+        from nerf_sampling_amd.run_nerf_helpers import NeRF
+
+        net = NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True).to(dev)
+    else:
+        net = TorchNeRF().to(dev)
     lr0 = args.nerf_lr
     if args.resume and os.path.exists(os.path.join(args.init, "nerf.safetensors")):
         net.load_state_dict(load(os.path.join(args.init, "nerf.safetensors")))
         print("[nerf] resuming from", args.init, flush=True)
-    opt = torch.optim.Adam(net.parameters(), lr=lr0)
+    opt = ag.HipAdam(list(net.parameters()), lr=lr0) if hip else torch.optim.Adam(net.parameters(), lr=lr0)
     H = W = 800
     _, K = synthetic.blender_intrinsics(H, W)
     B, n_pose = args.rays, 8
@@ -135,8 +142,13 @@ def fit_nerf(args):
             z = torch.sort(torch.cat([z_s, z_g.clamp(NEAR, FAR)], -1), -1).values
             pts = o[:, None] + d[:, None] * z[..., None]
             view = (d / d.norm(dim=-1, keepdim=True))[:, None].expand(pts.shape)
-        raw = net(pts.reshape(-1, 3), view.reshape(-1, 3)).reshape(B, -1, 4)
-        rgb, _ = composite(raw, z, d, args.raw_noise_std)
+        if hip:
+            raw = ag.nerf_forward_train(net, pts, view[:, 0].contiguous())
+            noise = torch.randn(z.shape, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
+            rgb = ag.composite(raw, z, d, noise, True)[0]
+        else:
+            raw = net(pts.reshape(-1, 3), view.reshape(-1, 3)).reshape(B, -1, 4)
+            rgb, _ = composite(raw, z, d, args.raw_noise_std)
         loss = ((rgb - gt) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -162,7 +174,7 @@ def fit_nerf(args):
         if planned and it >= planned:
             break
     json.dump({"iterations": it, "rays_per_iteration": B, "log": log, "raw_noise_std": args.raw_noise_std,
-               "resumed": bool(args.resume), "lr0": lr0},
+               "resumed": bool(args.resume), "lr0": lr0, "engine": args.engine},
               open(os.path.join(args.out, "nerf_fit.json"), "w"))
 
 
@@ -398,6 +410,9 @@ if __name__ == "__main__":
     ap.add_argument("--huber", type=float, default=0.02, help="phase depthnet_direct: Huber delta in depth units")
     ap.add_argument("--lr-floor", type=float, default=0.03, help="phase depthnet_direct: final / initial learning rate")
     ap.add_argument("--device", default="cuda", help="phase nerf only (plain torch); the other phases need the GPU")
+    ap.add_argument("--engine", default="torch", choices=["torch", "hip"],
+                    help="phase nerf: 'hip' fits the package's own NeRF module through autograd.NerfFunction, Composite and "
+                         "HipAdam; 'torch' (the committed fixture's provenance) the plain-torch twin")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     {"nerf": fit_nerf, "depthnet": fit_depthnet, "depthnet_direct": fit_depthnet_direct, "eval": evaluate}[a.phase](a)
