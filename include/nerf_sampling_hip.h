@@ -427,6 +427,16 @@ int64_t ns_gemm_wgrad_workspace_bytes(int64_t rows, int N, int K);
 int ns_gemm_wgrad(const float* dy_dev, int64_t dy_row_stride, int64_t dy_col_stride, const float* x_dev,
                   int64_t x_row_stride, int64_t rows, int N, int K, float* dW_dev, int64_t ldw, int accumulate,
                   float* db_dev, void* workspace_dev, void* stream);
+/* Tall GEMM of the field fit: the layer forwards and the grad-input products over rows = rays x samples,
+ *   C[i*ldc + j] (+)= sum_k A[i*lda + k] * B[j*sb0 + k*sb1] (+ bias[j]),  then act, then dact (both as in ns_gemm_fused)
+ * for i < rows in [1, 2^31), j < N <= 512, k < K <= 512 (larger N or K: NS_E_UNSUPPORTED); A is contiguous along k with
+ * lda >= K, ldc >= N, and dact_ref_dev[i*ld_ref + j] (ld_ref >= N) is read when dact != 0.  A, C and dact_ref may be column
+ * slices of wider buffers (4-byte alignment is all that is asked); B is W (sb1 == 1, a forward layer) or the W^T view
+ * (sb0 == 1, grad-input).  One workgroup owns 128 rows and all N columns, so a row of A is fetched once; B is re-read per
+ * slab through L2 and LDS.  The order of the sum over k depends on K alone: the same bits on every call, no atomics.      */
+int ns_gemm_tall(const float* A_dev, int64_t lda, const float* B_dev, int64_t sb0, int64_t sb1,
+                 const float* bias_dev, float* C_dev, int64_t ldc, int64_t rows, int N, int K, int accumulate,
+                 int act, int dact, const float* dact_ref_dev, int64_t ld_ref, void* stream);
 /* activations in place: act 0 none, 1 ReLU, 2 LeakyReLU(0.01), 3 sigmoid; backward scales dy by act'(.)
  * evaluated from the activation OUTPUT y                                                            */
 int ns_act_forward(float* y_dev, int64_t n, int act, void* stream);

@@ -139,6 +139,7 @@ SIGNATURES = {
     "ns_gemm_wgrad_splits": (_i, [_i64, _i, _i]),
     "ns_gemm_wgrad_workspace_bytes": (_i64, [_i64, _i, _i]),
     "ns_gemm_wgrad": (_i, [_p, _i64, _i64, _p, _i64, _i64, _i, _i, _p, _i64, _i, _p, _p, _p]),
+    "ns_gemm_tall": (_i, [_p, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "ns_act_forward": (_i, [_p, _i64, _i, _p]),
     "ns_act_backward": (_i, [_p, _p, _i64, _i, _p]),
     "ns_posenc_backward": (_i, [_p, _p, _i64, _i, _i, _p, _p]),

@@ -13,6 +13,9 @@ Each torch.autograd.Function below runs its arithmetic in libnerf_sampling_hip.s
 ns_act_*, ns_posenc[_backward], ns_points_backward, ns_raw2outputs_backward, ns_place_samples_backward); torch is used for tensor storage and `cat`/slicing.
 Training batches are N_rand = 1024 rays: launch-bound, so layers are individual fp32 GEMMs here rather than
 the fused inference kernels.
+The field fit (NerfFunction, trainers.FieldFitter) runs the same layers over 1024 rays x 64 .. 192 samples: its grad-weight
+products are ns_gemm_wgrad (split-K), and with engine="tall" its layer forwards and grad-input products are ns_gemm_tall (a
+workgroup per 128 rows and all columns) instead of ns_gemm_fused.
 """
 
 from __future__ import annotations
@@ -81,6 +84,86 @@ def linear_backward_input(dy: Tensor, W: Tensor, n_cols: Optional[int] = None) -
     M, N = dy.shape
     K = W.shape[1]
     return _gemm(dy, N, 1, W, 1, K, None, M, n_cols or K, N)
+
+
+GEMM_ENGINES = ("tile", "tall")
+
+
+def _check_engine(engine: str) -> str:
+    if engine not in GEMM_ENGINES:
+        raise ValueError(f"gemm engine must be one of {GEMM_ENGINES}, got {engine!r}")
+    return engine
+
+
+def _tall_operand(t: Tensor, name: str) -> Tensor:
+    """A [rows, n] float32 GPU matrix that is contiguous along its columns (a column slice of a wider buffer is fine)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); this path has no CPU fallback")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError(f"{name}: a 2-D tensor expected, got {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} must be contiguous along its columns (strides {tuple(t.stride())})")
+    return t
+
+
+def _gemm_tall(A: Tensor, B: Tensor, sb0: int, sb1: int, bias: Optional[Tensor], N: int, K: int, out: Optional[Tensor] = None,
+               accumulate: bool = False, act: int = 0, dact: int = 0, dact_ref: Optional[Tensor] = None) -> Tensor:
+    """C = A B^T (+ bias), act, dact through ns_gemm_tall: A [rows, K], ``out`` [rows, N] and ``dact_ref`` [rows, N] may be
+    column slices of wider buffers (their row strides are the leading dimensions)."""
+    rows = A.shape[0]
+    if out is None:
+        out = torch.empty((rows, N), dtype=torch.float32, device=A.device)
+    elif tuple(out.shape) != (rows, N):
+        raise ValueError(f"out must be [{rows}, {N}], got {tuple(out.shape)}")
+    if dact_ref is not None and tuple(dact_ref.shape) != (rows, N):
+        raise ValueError(f"dact_ref must be [{rows}, {N}], got {tuple(dact_ref.shape)}")
+    if rows == 0:
+        return out
+    check(_lib.load().ns_gemm_tall(_ptr(A), A.stride(0), _ptr(B), sb0, sb1, _ptr(bias), _ptr(out), out.stride(0), rows, N, K,
+                                   int(accumulate), int(act), int(dact), _ptr(dact_ref),
+                                   0 if dact_ref is None else dact_ref.stride(0), _stream(A.device)), "ns_gemm_tall")
+    return out
+
+
+def linear_forward_tall(x: Tensor, W: Tensor, b: Optional[Tensor], act: int = NONE, out: Optional[Tensor] = None) -> Tensor:
+    """act(x @ W.T + b) on ns_gemm_tall: x [M,K] and ``out`` [M,N] may be column slices of wider buffers (contiguous along
+    their columns), W [N,K] is in nn.Linear layout, N and K at most 512."""
+    x, W = _tall_operand(x, "x"), _dev(W, "weight")
+    if W.dim() != 2 or W.shape[1] != x.shape[1] or not W.is_contiguous():
+        raise ValueError(f"weight must be a contiguous [N, {x.shape[1]}] matrix, got {tuple(W.shape)}")
+    if b is not None:
+        b = _dev(b, "bias")
+        if tuple(b.shape) != (W.shape[0],) or not b.is_contiguous():
+            raise ValueError(f"bias must be a contiguous [{W.shape[0]}] vector, got {tuple(b.shape)}")
+    if out is not None:
+        out = _tall_operand(out, "out")
+    N, K = W.shape
+    return _gemm_tall(x, W, K, 1, b, N, K, out=out, act=act)
+
+
+def linear_backward_input_tall(dy: Tensor, W: Tensor, n_cols: Optional[int] = None, dact_ref: Optional[Tensor] = None,
+                               dact: int = RELU, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """dx[:, :n_cols] = dy @ W[:, :n_cols] on ns_gemm_tall (dy [M,N], W [N,K], N and n_cols at most 512), times
+    act'(``dact_ref``) when the activation output ``dact_ref`` [M,n_cols] of the layer below is given (``dact``: which
+    activation, ReLU by default).  dy, ``dact_ref`` and ``out`` may be column slices of wider buffers; ``accumulate`` adds the
+    product to ``out`` before the derivative is applied."""
+    dy, W = _tall_operand(dy, "dy"), _dev(W, "weight")
+    if W.dim() != 2 or W.shape[0] != dy.shape[1] or not W.is_contiguous():
+        raise ValueError(f"weight must be a contiguous [{dy.shape[1]}, K] matrix, got {tuple(W.shape)}")
+    Kw = W.shape[1]
+    n = Kw if n_cols is None else int(n_cols)
+    if not 1 <= n <= Kw:
+        raise ValueError(f"n_cols must be in [1, {Kw}], got {n_cols}")
+    if dact_ref is not None:
+        dact_ref = _tall_operand(dact_ref, "dact_ref")
+    if out is not None:
+        out = _tall_operand(out, "out")
+    return _gemm_tall(dy, W, 1, Kw, None, n, dy.shape[1], out=out, accumulate=accumulate,
+                      dact=dact if dact_ref is not None else 0, dact_ref=dact_ref)
 
 
 def linear_backward_weight(dy: Tensor, x: Tensor):
@@ -239,15 +322,19 @@ def place_samples(o: Tensor, d: Tensor, mean: Tensor, n_samples: int, mode: str,
 
 
 # ---- the NeRF layer by layer: shared by NerfInputGrad (frozen field) and NerfFunction (field fit) --------------------------
-def _nerf_layers_forward(net, xe: Tensor, ve: Optional[Tensor], want_raw: bool):
+def _nerf_layers_forward(net, xe: Tensor, ve: Optional[Tensor], want_raw: bool, engine: str = "tile"):
     """NeRF.forward (run_nerf_helpers.py:114-133) on _gemm with the ReLU in the epilogue, from the module's live parameters.
     xe [M,63], ve [M,27] (view-direction head only).  Returns (raw [M,C] or None, saved): saved holds what the backward reads --
     ``acts`` (each trunk layer's output), ``ins`` (each trunk layer's input: xe, the layer below's output or the cat[xe, h]
-    buffer), ``h`` (the trunk's output), and for the view-direction head ``vin`` = cat[feature, ve] and ``hv``."""
+    buffer), ``h`` (the trunk's output), and for the view-direction head ``vin`` = cat[feature, ve] and ``hv``.
+    ``engine``: "tile" (ns_gemm_fused) or "tall" (ns_gemm_tall, the throughput kernel for the field fit's row counts)."""
     skips = net._check_supported()
     M = xe.shape[0]
+    tall = _check_engine(engine) == "tall"
 
     def fwd(x, lin, act, out=None):    # act(x W^T + b), activation in the GEMM epilogue
+        if tall:
+            return linear_forward_tall(x, lin.weight, lin.bias, act, out=out)
         return _gemm(x, x.stride(0), 1, lin.weight, lin.weight.shape[1], 1, lin.bias, M, lin.weight.shape[0], x.shape[1], act=act,
                      out=out)
 
@@ -255,6 +342,12 @@ def _nerf_layers_forward(net, xe: Tensor, ve: Optional[Tensor], want_raw: bool):
     h = xe
     for i, lin in enumerate(net.pts_linears):               # (run_nerf_helpers.py:114-118)
         ins.append(h)
+        if tall and i in skips:          # the layer writes its output into its column slice of the cat[xe, h] buffer
+            cat = torch.empty((M, xe.shape[1] + lin.weight.shape[0]), dtype=torch.float32, device=xe.device)
+            cat[:, :xe.shape[1]] = xe
+            acts.append(fwd(h, lin, RELU, out=cat[:, xe.shape[1]:]))
+            h = cat
+            continue
         h = fwd(h, lin, RELU)
         acts.append(h)
         if i in skips:
@@ -275,17 +368,21 @@ def _nerf_layers_forward(net, xe: Tensor, ve: Optional[Tensor], want_raw: bool):
     return raw, saved
 
 
-def _nerf_layers_backward(net, saved, draw: Tensor, weight_grad=None, want_input: bool = True) -> Optional[Tensor]:
+def _nerf_layers_backward(net, saved, draw: Tensor, weight_grad=None, want_input: bool = True,
+                          engine: str = "tile") -> Optional[Tensor]:
     """The transposed chain from d raw down to the embedded point: returns d xe [M,63] (None without ``want_input``: the
     grad-input GEMM of layer 0 is then skipped).  ``weight_grad(lin, dy, x)`` is called once per Linear with the gradient of its
-    pre-activation output and its input."""
+    pre-activation output and its input.  ``engine``: as in _nerf_layers_forward, for every grad-input product."""
     xe, acts, skips = saved["xe"], saved["acts"], saved["skips"]
     lins = list(net.pts_linears)
     M = xe.shape[0]
     h = saved["h"]
+    tall = _check_engine(engine) == "tall"
 
     def bwd(dy, lin, n_cols=None, dref=None):   # dy W[:, :n_cols], times relu'(dref) when the layer below has a ReLU
         Wt = lin.weight
+        if tall:
+            return linear_backward_input_tall(dy, Wt, n_cols, dact_ref=dref)
         return _gemm(dy, dy.stride(0), 1, Wt, 1, Wt.shape[1], None, M, n_cols or Wt.shape[1], dy.shape[1],
                      dact=RELU if dref is not None else 0, dact_ref=dref)
 
@@ -306,8 +403,11 @@ def _nerf_layers_backward(net, saved, draw: Tensor, weight_grad=None, want_input
         # + the sigma head, accumulated in place, then the trunk's last ReLU on the sum
         wg(net.alpha_linear, g_sigma, h)
         Wa = net.alpha_linear.weight
-        _gemm(g_sigma, g_sigma.stride(0), 1, Wa, 1, Wa.shape[1], None, M, Wa.shape[1], 1, out=d_h, accumulate=True,
-              dact=RELU, dact_ref=acts[last])
+        if tall:
+            linear_backward_input_tall(g_sigma, Wa, dact_ref=acts[last], out=d_h, accumulate=True)
+        else:
+            _gemm(g_sigma, g_sigma.stride(0), 1, Wa, 1, Wa.shape[1], None, M, Wa.shape[1], 1, out=d_h, accumulate=True,
+                  dact=RELU, dact_ref=acts[last])
     else:                             # output_linear head (:132-133): raw = h W_out^T + b, no view directions
         g = _dev(draw, "draw").reshape(-1, net.output_channels)
         wg(net.output_linear, g, h)
@@ -316,7 +416,13 @@ def _nerf_layers_backward(net, saved, draw: Tensor, weight_grad=None, want_input
     for i in range(last, -1, -1):     # d_h is the gradient w.r.t. the PRE-activation of layer i here
         wg(lins[i], d_h, saved["ins"][i])
         below = i - 1
-        if below >= 0 and below in skips:               # layer i saw cat[xe, h_{i-1}]
+        if below >= 0 and below in skips and tall:      # layer i saw cat[xe, h_{i-1}]: the two column ranges of W apart
+            Wt = lins[i].weight
+            if want_input:
+                d_xe = d_xe + bwd(d_h, lins[i], n_cols=63)   # the xe part has no activation
+            d_h = _gemm_tall(d_h, Wt[:, 63:], 1, Wt.shape[1], None, Wt.shape[1] - 63, d_h.shape[1], dact=RELU,
+                             dact_ref=acts[below])
+        elif below >= 0 and below in skips:
             d_in = bwd(d_h, lins[i])                     # [M, 63 + W]: the xe part has no activation
             if want_input:
                 d_xe = d_xe + d_in[:, :63]
@@ -377,15 +483,15 @@ def nerf_params(net) -> List[Tensor]:
 
 class NerfFunction(torch.autograd.Function):
     """raw [R,N,C] of NeRF.forward (run_nerf_helpers.py:67-134) from the module's live parameters, layer by layer on
-    ns_gemm_fused (no packed stream: nothing is repacked inside a training loop); the activations are kept.  backward: the
+    ns_gemm_fused (``engine`` "tile") or ns_gemm_tall ("tall") (no packed stream: nothing is repacked inside a training loop); the activations are kept.  backward: the
     grad-input chain NerfInputGrad runs, one ns_gemm_wgrad per Linear for (dW, db), and the gradient of ``pts`` (through the
     positional encoding) only when pts.requires_grad.  Any ``skips``, both heads, any W <= 256."""
 
     @staticmethod
-    def forward(ctx, pts: Tensor, viewdirs: Optional[Tensor], net, *params: Tensor):
+    def forward(ctx, pts: Tensor, viewdirs: Optional[Tensor], net, engine: str, *params: Tensor):
         flat, xe, ve = _nerf_embed(pts, viewdirs, net.use_viewdirs)
-        raw, saved = _nerf_layers_forward(net, xe, ve, want_raw=True)
-        ctx.net, ctx.saved, ctx.flat = net, saved, flat
+        raw, saved = _nerf_layers_forward(net, xe, ve, want_raw=True, engine=engine)
+        ctx.net, ctx.saved, ctx.flat, ctx.engine = net, saved, flat, engine
         ctx.pts_shape = tuple(pts.shape)
         return raw.reshape(pts.shape[0], pts.shape[1], raw.shape[1])
 
@@ -398,26 +504,28 @@ class NerfFunction(torch.autograd.Function):
 
         def weight_grad(lin, dy, x):
             kw, kb = slot[id(lin.weight)], slot[id(lin.bias)]
-            if not (ctx.needs_input_grad[3 + kw] or ctx.needs_input_grad[3 + kb]):
+            if not (ctx.needs_input_grad[4 + kw] or ctx.needs_input_grad[4 + kb]):
                 return
             grads[kw], grads[kb] = linear_backward_weight_splitk(dy, x)
 
         want_pts = ctx.needs_input_grad[0]
-        d_xe = _nerf_layers_backward(net, saved, draw, weight_grad=weight_grad, want_input=want_pts)
+        d_xe = _nerf_layers_backward(net, saved, draw, weight_grad=weight_grad, want_input=want_pts, engine=ctx.engine)
         dpts = posenc_backward(ctx.flat, d_xe.contiguous(), 10).reshape(ctx.pts_shape) if want_pts else None
         ctx.saved = None
-        return (dpts, None, None, *grads)
+        return (dpts, None, None, None, *grads)
 
 
-def nerf_forward_train(net, pts: Tensor, viewdirs: Optional[Tensor]) -> Tensor:
+def nerf_forward_train(net, pts: Tensor, viewdirs: Optional[Tensor], engine: str = "tile") -> Tensor:
     """raw [R,N,C] of ``net`` at pts [R,N,3] (viewdirs [R,3], or None for a network without view directions), differentiable in
-    the network's parameters and, when it requires a gradient, in ``pts`` (NerfFunction)."""
+    the network's parameters and, when it requires a gradient, in ``pts`` (NerfFunction).  ``engine``: "tile" runs the layer
+    forwards and grad-input products on ns_gemm_fused, "tall" on ns_gemm_tall; grad-weight is ns_gemm_wgrad either way."""
+    _check_engine(engine)
     pts = _dev(pts, "pts")
     if net.use_viewdirs:
         viewdirs = _dev(viewdirs, "viewdirs")
     else:
         viewdirs = None
-    return NerfFunction.apply(pts, viewdirs, net, *nerf_params(net))
+    return NerfFunction.apply(pts, viewdirs, net, engine, *nerf_params(net))
 
 
 # ---- DepthNet, gradient w.r.t. its weights -----------------------------------------------------------------

@@ -37,6 +37,8 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--fit-field", "fit_field", is_flag=True, default=False,
               help="Fit the radiance field itself (trainers.FieldFitter: both NeRFs' weights on the HIP kernels) instead of "
                    "training the DepthNet; writes {root}/logs/{expname}_field/NNNNNN.tar (not in the reference).")
+@click.option("--gemm-engine", "gemm_engine", default="tile", type=click.Choice(["tile", "tall"]), show_default=True,
+              help="With --fit-field: the GEMM kernel of the layer forwards and grad-input products (FieldFitter(gemm_engine=...)).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -62,12 +64,12 @@ def main(**kw):
         k["fused_step"] = True
     if kw["fit_field"]:
         k.update(ft_path=None)
-        return fit_field(load_obj_from_config(cfg=config), kw["iters"])
+        return fit_field(load_obj_from_config(cfg=config), kw["iters"], gemm_engine=kw["gemm_engine"])
     trainer = load_obj_from_config(cfg=config)
     trainer.train(N_iters=kw["iters"] + 1)
 
 
-def fit_field(trainer, n_iters):
+def fit_field(trainer, n_iters, gemm_engine="tile"):
     """--fit-field: a FieldFitter built from the trainer's configuration (network shapes, sample counts, learning rate, noise,
     background) on the trainer's dataset; checkpoints load as ft_path of the DepthNet training and of experiments/render.py."""
     from nerf_sampling_amd import nerf_utils
@@ -85,7 +87,7 @@ def fit_field(trainer, n_iters):
     fitter = FieldFitter(kw_train["network_fn"], kw_train["network_fine"], N_samples=trainer.N_samples,
                          N_importance=trainer.N_importance, lrate=trainer.lrate, lrate_decay=trainer.lrate_decay,
                          white_bkgd=trainer.white_bkgd, raw_noise_std=trainer.raw_noise_std, perturb=trainer.perturb,
-                         lindisp=trainer.lindisp, near=trainer.near, far=trainer.far)
+                         lindisp=trainer.lindisp, near=trainer.near, far=trainer.far, gemm_engine=gemm_engine)
     split = dict(images=images, poses=poses, hwf=hwf, i_train=i_train)
     return fitter.fit(split, n_iters, N_rand=trainer.N_rand, basedir=trainer.basedir, expname=f"{trainer.expname}_field",
                       i_weights=trainer.i_weights, i_print=trainer.i_print)

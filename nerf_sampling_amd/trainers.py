@@ -356,12 +356,16 @@ class FieldFitter:
 
     ``network_fine=None``: the coarse-only objective when N_importance == 0, else the coarse network runs both passes (as
     sample_fine_points does).  One module passed as both networks accumulates both passes' gradients into the same tensors.
-    ``near`` / ``far``: the ray bounds (Blender's 2 / 6)."""
+    ``near`` / ``far``: the ray bounds (Blender's 2 / 6).  ``gemm_engine``: "tile" runs the layer forwards and the grad-input
+    products of both passes on ns_gemm_fused, "tall" on ns_gemm_tall (autograd.nerf_forward_train's ``engine``)."""
 
     def __init__(self, network_fn, network_fine=None, N_samples=64, N_importance=128, lrate=5e-4, lrate_decay=250,
-                 white_bkgd=True, raw_noise_std=0.0, perturb=1.0, lindisp=False, near=2.0, far=6.0):
-        from .autograd import HipAdam
+                 white_bkgd=True, raw_noise_std=0.0, perturb=1.0, lindisp=False, near=2.0, far=6.0, gemm_engine="tile"):
+        from .autograd import GEMM_ENGINES, HipAdam
 
+        if gemm_engine not in GEMM_ENGINES:
+            raise ValueError(f"gemm_engine must be one of {GEMM_ENGINES}, got {gemm_engine!r}")
+        self.gemm_engine = gemm_engine
         self.network_fn, self.network_fine = network_fn, network_fine
         self.N_samples, self.N_importance = int(N_samples), int(N_importance)
         self.lrate, self.lrate_decay = float(lrate), lrate_decay
@@ -399,7 +403,7 @@ class FieldFitter:
         if t_rand is None and self.perturb > 0.0:
             t_rand = torch.rand((B, self.N_samples), device=dev)
         z0 = ops.coarse_z(near, far, self.N_samples, self.lindisp, t_rand)
-        raw0 = nerf_forward_train(self.network_fn, ops.points_along_rays(o, d, z0), viewdirs)
+        raw0 = nerf_forward_train(self.network_fn, ops.points_along_rays(o, d, z0), viewdirs, engine=self.gemm_engine)
         rgb0, _, _, _, _, w0 = composite(raw0, z0, d, self._noise(z0.shape, dev), self.white_bkgd)
         img_loss0 = img2mse(rgb0, target)
         info = dict(z0=z0, rgb0=rgb0, img_loss0=img_loss0.detach())
@@ -410,7 +414,7 @@ class FieldFitter:
             u = torch.rand((B, self.N_importance), device=dev)
         z = ops.importance_z(z0, w0.detach(), self.N_importance, u)       # the reference detaches z_samples (Trainer.py:572)
         fine = self.network_fn if self.network_fine is None else self.network_fine
-        raw = nerf_forward_train(fine, ops.points_along_rays(o, d, z), viewdirs)
+        raw = nerf_forward_train(fine, ops.points_along_rays(o, d, z), viewdirs, engine=self.gemm_engine)
         rgb, _, _, _, _, _ = composite(raw, z, d, self._noise(z.shape, dev), self.white_bkgd)
         img_loss = img2mse(rgb, target)
         info.update(z=z, rgb=rgb, img_loss=img_loss.detach())

@@ -106,8 +106,10 @@ def fit_nerf(args):
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
     hip = args.engine == "hip"
-    if hip:     # the package's own module: NerfFunction (ns_gemm_fused / ns_gemm_wgrad), Composite and HipAdam
+    if hip:     # the package's own module: NerfFunction (ns_gemm_fused or ns_gemm_tall / ns_gemm_wgrad), Composite and HipAdam
         from nerf_sampling_amd import autograd as ag
+        if args.gemm_engine not in ag.GEMM_ENGINES:
+            raise ValueError(f"--gemm-engine must be one of {ag.GEMM_ENGINES}, got {args.gemm_engine!r}")
         from nerf_sampling_amd.run_nerf_helpers import NeRF
 
         net = NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True).to(dev)
@@ -143,7 +145,7 @@ def fit_nerf(args):
             pts = o[:, None] + d[:, None] * z[..., None]
             view = (d / d.norm(dim=-1, keepdim=True))[:, None].expand(pts.shape)
         if hip:
-            raw = ag.nerf_forward_train(net, pts, view[:, 0].contiguous())
+            raw = ag.nerf_forward_train(net, pts, view[:, 0].contiguous(), engine=args.gemm_engine)
             noise = torch.randn(z.shape, device=dev) * args.raw_noise_std if args.raw_noise_std > 0 else None
             rgb = ag.composite(raw, z, d, noise, True)[0]
         else:
@@ -413,6 +415,9 @@ if __name__ == "__main__":
     ap.add_argument("--engine", default="torch", choices=["torch", "hip"],
                     help="phase nerf: 'hip' fits the package's own NeRF module through autograd.NerfFunction, Composite and "
                          "HipAdam; 'torch' (the committed fixture's provenance) the plain-torch twin")
+    ap.add_argument("--gemm-engine", default="tile",
+                    help="phase nerf with --engine hip: 'tile' (ns_gemm_fused) or 'tall' (ns_gemm_tall) for the layer forwards "
+                         "and grad-input products")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     {"nerf": fit_nerf, "depthnet": fit_depthnet, "depthnet_direct": fit_depthnet_direct, "eval": evaluate}[a.phase](a)
