@@ -70,6 +70,47 @@ int ns_get_rays(int H, int W, float fx, float fy, float cx, float cy, const floa
                 int row0, int row1, float near_, float far_, float* rays_o_dev, float* rays_d_dev,
                 float* viewdirs_dev, float* ray_batch_dev, void* stream);
 
+/* ---- training ray batches from a device-resident dataset  (Trainer.sample_random_ray_batch, Trainer.py:400-475) ----
+ * "B training rays and their target colours" with images and poses uploaded once.  images_dev is fp32 [n_images, H, W, C],
+ * C = 3 or 4; poses_dev holds pose_stride = 12 or 16 floats per image, the first 12 being c2w[:3,:4] row-major.  The target of
+ * a ray is its pixel's rgb; with C == 4 and white_bkgd it is rgb * a + (1 - a) in separate fp32 roundings (Blender.py:26-29).
+ * rays_o / rays_d / viewdirs are the bits a1 writes at that pixel.  n_images * H * W must stay below 2^31.                 */
+typedef struct ns_ray_dataset {
+  const float* images_dev;
+  const float* poses_dev;
+  int n_images, H, W, C;
+  int pose_stride, white_bkgd;
+  float fx, fy, cx, cy;
+} ns_ray_dataset;
+/* Ray i of the batch is pixel pixel_dev[i] (int32, flat row * W + col) of image image_idx_dev[i] (int32), or of image
+ * `image_idx` for every ray when image_idx_dev is NULL.  Outputs are [B,3]; any of them may be NULL.  Indices read from
+ * device memory are clamped into range by the kernel; the host scalar is checked here.                                     */
+int ns_ray_batch_gather(const ns_ray_dataset* ds, const int* image_idx_dev, int image_idx, const int* pixel_dev, int64_t B,
+                        float* rays_o_dev, float* rays_d_dev, float* viewdirs_dev, float* target_dev, void* stream);
+/* The same with the indices drawn in the launch, without replacement, by a keyed permutation P_{seed,counter} of [0, n): a
+ * balanced Feistel network of NS_RAY_DRAW_ROUNDS rounds over the smallest even bit width covering n, cycle-walked into
+ * [0, n) -- O(1) per ray, no memory (DESIGN.md section 8 states the constants).  This is NOT numpy's generator.
+ *   NS_RAY_SCOPE_PER_IMAGE  (no_batching): every ray from image train_idx[h(seed, step) mod n_train]; ray i is pixel
+ *       P_{seed,step}(i) of the window rows [row0,row1) x columns [col0,col1), as a full-frame flat index; B <= window size.
+ *   NS_RAY_SCOPE_ALL_IMAGES (use_batching): pos = step * B + i, N = n_train * H * W, g = P_{seed, pos div N}(pos mod N):
+ *       image train_idx[g div (H * W)], pixel g mod (H * W); every epoch of N rays visits each ray once.  The window is unused.
+ * {step, row0, row1, col0, col1} is read from params_dev (five int32 in device memory: nothing in the launch changes from
+ * step to step, so a captured hipGraph replays it, ns_add_i32 advancing the step) or from *params_host -- exactly one of
+ * the two is given.  Host params are checked here (NS_E_INVALID: empty window, window outside the frame, B above the
+ * window size); device params cannot be, so the kernel clamps the window to a non-empty part of the frame and wraps ray
+ * indices beyond it.  train_idx_dev: int32 [n_train], clamped into [0, n_images).  image_idx_out_dev / pixel_out_dev:
+ * int32 [B] or NULL, the indices drawn.                                                                                   */
+#define NS_RAY_SCOPE_PER_IMAGE 0
+#define NS_RAY_SCOPE_ALL_IMAGES 1
+#define NS_RAY_DRAW_ROUNDS 6
+typedef struct ns_ray_draw_params {
+  int step, row0, row1, col0, col1;
+} ns_ray_draw_params;
+int ns_ray_batch_draw(const ns_ray_dataset* ds, const int* train_idx_dev, int n_train, int scope, const int* params_dev,
+                      const ns_ray_draw_params* params_host, uint64_t seed, int64_t B, int* image_idx_out_dev,
+                      int* pixel_out_dev, float* rays_o_dev, float* rays_d_dev, float* viewdirs_dev, float* target_dev,
+                      void* stream);
+
 /* ---- a2  find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("NS_LIB_PATH") or os.path.join(_HERE, "libnerf_samplin
 NS_OK = 0
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F16X3, DTYPE_F16M = 0, 1, 2, 3, 4
 MODE_DEPTH_ONLY, MODE_UNIFORM, MODE_GAUSSIAN = 0, 1, 2
+RAY_SCOPE_PER_IMAGE, RAY_SCOPE_ALL_IMAGES = 0, 1
 
 _p = C.c_void_p
 _i = C.c_int
@@ -87,6 +88,23 @@ class HierArgs(C.Structure):
     ]
 
 
+class RayDataset(C.Structure):
+    """struct ns_ray_dataset"""
+
+    _fields_ = [
+        ("images_dev", _p), ("poses_dev", _p),
+        ("n_images", _i), ("H", _i), ("W", _i), ("C", _i),
+        ("pose_stride", _i), ("white_bkgd", _i),
+        ("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f),
+    ]
+
+
+class RayDrawParams(C.Structure):
+    """struct ns_ray_draw_params"""
+
+    _fields_ = [("step", _i), ("row0", _i), ("row1", _i), ("col0", _i), ("col1", _i)]
+
+
 # name -> (restype, argtypes); every symbol include/nerf_sampling_hip.h declares
 SIGNATURES = {
     "ns_last_error": (C.c_char_p, []),
@@ -94,6 +112,9 @@ SIGNATURES = {
     "ns_device_cu_count": (_i, []),
     "ns_debug_set": (_i, [C.c_char_p, _i]),
     "ns_get_rays": (_i, [_i, _i, _f, _f, _f, _f, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
+    "ns_ray_batch_gather": (_i, [C.POINTER(RayDataset), _p, _i, _p, _i64, _p, _p, _p, _p, _p]),
+    "ns_ray_batch_draw": (_i, [C.POINTER(RayDataset), _p, _i, _i, _p, C.POINTER(RayDrawParams), C.c_uint64, _i64, _p, _p,
+                               _p, _p, _p, _p, _p]),
     "ns_sphere_intersect": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "ns_solve_quadratic": (_i, [_p, _p, _p, _i64, _p, _p]),
     "ns_posenc": (_i, [_p, _i64, _i, _i, _p, _p]),

@@ -17,7 +17,19 @@ struct Cam {
   float t[3];  // c2w[:3,3]
 };
 
-// a1: run_nerf_helpers.py:187-202 + nerf_utils.py:156-188
+// a1: run_nerf_helpers.py:187-202 + nerf_utils.py:156-188.  The direction of pixel (column i, row j) and its norm: the ONE
+// statement of the ray arithmetic, shared by get_rays_kernel and the ray-batch kernels below (same bits from all of them).
+__device__ __forceinline__ void pixel_ray(const Cam& cam, int i, int j, float d[3], float& nrm) {
+  const float dx = (static_cast<float>(i) - cam.cx) / cam.fx;
+  const float dy = -((static_cast<float>(j) - cam.cy) / cam.fy);
+  const float dz = -1.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    d[c] = (dx * cam.r[3 * c + 0] + dy * cam.r[3 * c + 1]) + dz * cam.r[3 * c + 2];
+  // torch.norm on the CPU accumulates squares as an fma chain (verified bit-for-bit on the golden rays)
+  nrm = sqrtf(__builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], d[0] * d[0])));
+}
+
 __global__ void __launch_bounds__(kBlock)
 get_rays_kernel(Cam cam, int W, int row0, int64_t R, float near_, float far_,
                 float* __restrict__ rays_o, float* __restrict__ rays_d,
@@ -26,15 +38,8 @@ get_rays_kernel(Cam cam, int W, int row0, int64_t R, float near_, float far_,
        idx += (int64_t)gridDim.x * kBlock) {
     const int j = row0 + static_cast<int>(idx / W);
     const int i = static_cast<int>(idx % W);
-    const float dx = (static_cast<float>(i) - cam.cx) / cam.fx;
-    const float dy = -((static_cast<float>(j) - cam.cy) / cam.fy);
-    const float dz = -1.0f;
-    float d[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      d[c] = (dx * cam.r[3 * c + 0] + dy * cam.r[3 * c + 1]) + dz * cam.r[3 * c + 2];
-    // torch.norm on the CPU accumulates squares as an fma chain (verified bit-for-bit on the golden rays)
-    const float nrm = sqrtf(__builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], d[0] * d[0])));
+    float d[3], nrm;
+    pixel_ray(cam, i, j, d, nrm);
     if (rays_o) {
       rays_o[idx * 3 + 0] = cam.t[0]; rays_o[idx * 3 + 1] = cam.t[1]; rays_o[idx * 3 + 2] = cam.t[2];
     }
@@ -51,6 +56,139 @@ get_rays_kernel(Cam cam, int W, int row0, int64_t R, float near_, float far_,
       b[6] = near_; b[7] = far_;
       b[8] = d[0] / nrm; b[9] = d[1] / nrm; b[10] = d[2] / nrm;
     }
+  }
+}
+
+// ---- training ray batches from a device-resident dataset (ns_ray_batch_gather / ns_ray_batch_draw) ----------------------
+struct BatchOut {
+  float* rays_o;
+  float* rays_d;
+  float* viewdirs;
+  float* target;
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Ray b of a batch: pixel `pix` (flat row * W + col) of image `img`, both clamped into range (no index reads out of bounds).
+__device__ __forceinline__ void emit_batch_ray(const ns_ray_dataset& ds, int img, int pix, int64_t b, const BatchOut& out) {
+  img = clampi(img, 0, ds.n_images - 1);
+  pix = clampi(pix, 0, ds.H * ds.W - 1);
+  if (out.rays_o || out.rays_d || out.viewdirs) {
+    const float* pose = ds.poses_dev + static_cast<int64_t>(img) * ds.pose_stride;
+    Cam cam;
+    cam.fx = ds.fx; cam.fy = ds.fy; cam.cx = ds.cx; cam.cy = ds.cy;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) cam.r[3 * r + c] = pose[4 * r + c];
+      cam.t[r] = pose[4 * r + 3];
+    }
+    float d[3], nrm;
+    pixel_ray(cam, pix % ds.W, pix / ds.W, d, nrm);
+    if (out.rays_o) {
+      out.rays_o[b * 3 + 0] = cam.t[0]; out.rays_o[b * 3 + 1] = cam.t[1]; out.rays_o[b * 3 + 2] = cam.t[2];
+    }
+    if (out.rays_d) {
+      out.rays_d[b * 3 + 0] = d[0]; out.rays_d[b * 3 + 1] = d[1]; out.rays_d[b * 3 + 2] = d[2];
+    }
+    if (out.viewdirs) {
+      out.viewdirs[b * 3 + 0] = d[0] / nrm; out.viewdirs[b * 3 + 1] = d[1] / nrm; out.viewdirs[b * 3 + 2] = d[2] / nrm;
+    }
+  }
+  if (out.target) {
+    const float* px = ds.images_dev + (static_cast<int64_t>(img) * (ds.H * ds.W) + pix) * ds.C;
+    float rgb[3] = {px[0], px[1], px[2]};
+    if (ds.C == 4 && ds.white_bkgd) {          // BlenderTrainer.load_data: rgb * a + (1 - a), three separate roundings
+      const float a = px[3];
+      const float inv = 1.0f - a;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] * a + inv;
+    }
+    out.target[b * 3 + 0] = rgb[0]; out.target[b * 3 + 1] = rgb[1]; out.target[b * 3 + 2] = rgb[2];
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+ray_batch_gather_kernel(ns_ray_dataset ds, const int* __restrict__ image_idx, int image_scalar,
+                        const int* __restrict__ pixel, int64_t B, BatchOut out) {
+  for (int64_t b = blockIdx.x * (int64_t)kBlock + threadIdx.x; b < B; b += (int64_t)gridDim.x * kBlock)
+    emit_batch_ray(ds, image_idx ? image_idx[b] : image_scalar, pixel[b], b, out);
+}
+
+// The keyed permutation of ns_ray_batch_draw (ray_batches.permute_index repeats it in integers).
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {        // splitmix64's finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kImageSalt = 0xD1B54A32D192ED03ull;
+constexpr int kRounds = NS_RAY_DRAW_ROUNDS;
+
+__device__ __forceinline__ uint64_t draw_key(uint64_t seed, uint64_t counter) { return mix64(seed ^ mix64(counter + kGolden)); }
+
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {        // murmur3's finaliser
+  h ^= h >> 16; h *= 0x85EBCA6Bu;
+  h ^= h >> 13; h *= 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+
+// P_{seed,counter}(i) on [0, n), 1 <= n < 2^31, 0 <= i < n: a balanced Feistel network over the smallest even bit width that
+// covers n, walked along its cycle until the value is below n again (it is a bijection of the wider range and starts below n).
+__device__ __forceinline__ uint32_t permute_index(uint32_t n, uint64_t key, uint32_t i) {
+  int half = 1;
+  while ((1ull << (2 * half)) < n) ++half;
+  const uint32_t mask = (1u << half) - 1u;
+  uint32_t rk[kRounds];
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) rk[r] = static_cast<uint32_t>(mix64(key + static_cast<uint64_t>(r + 1) * kGolden));
+  uint32_t v = i;
+  do {
+    uint32_t l = v >> half, r = v & mask;
+#pragma unroll
+    for (int k = 0; k < kRounds; ++k) {
+      const uint32_t t = l ^ (mix32(r + rk[k]) & mask);
+      l = r;
+      r = t;
+    }
+    v = (l << half) | r;
+  } while (v >= n);
+  return v;
+}
+
+__global__ void __launch_bounds__(kBlock)
+ray_batch_draw_kernel(ns_ray_dataset ds, const int* __restrict__ train_idx, int n_train, int scope,
+                      const int* __restrict__ params_dev, ns_ray_draw_params host, uint64_t seed, int64_t B,
+                      int* __restrict__ image_idx_out, int* __restrict__ pixel_out, BatchOut out) {
+  ns_ray_draw_params p = host;
+  if (params_dev) {
+    p.step = params_dev[0]; p.row0 = params_dev[1]; p.row1 = params_dev[2]; p.col0 = params_dev[3]; p.col1 = params_dev[4];
+  }
+  const int HW = ds.H * ds.W;
+  for (int64_t b = blockIdx.x * (int64_t)kBlock + threadIdx.x; b < B; b += (int64_t)gridDim.x * kBlock) {
+    int slot, pix;
+    if (scope == NS_RAY_SCOPE_ALL_IMAGES) {
+      const uint64_t N = static_cast<uint64_t>(n_train) * static_cast<uint64_t>(HW);
+      const uint64_t pos = static_cast<uint64_t>(static_cast<uint32_t>(p.step)) * static_cast<uint64_t>(B) + static_cast<uint64_t>(b);
+      const uint32_t g = permute_index(static_cast<uint32_t>(N), draw_key(seed, pos / N), static_cast<uint32_t>(pos % N));
+      slot = static_cast<int>(g / static_cast<uint32_t>(HW));
+      pix = static_cast<int>(g % static_cast<uint32_t>(HW));
+    } else {
+      // a window read from device memory is clamped to a non-empty part of the frame, and a ray index beyond it wraps
+      const int r0 = clampi(p.row0, 0, ds.H - 1), r1 = clampi(p.row1, r0 + 1, ds.H);
+      const int c0 = clampi(p.col0, 0, ds.W - 1), c1 = clampi(p.col1, c0 + 1, ds.W);
+      const int cols = c1 - c0;
+      const uint32_t n = static_cast<uint32_t>((r1 - r0) * cols);
+      const uint64_t key = draw_key(seed, static_cast<uint64_t>(static_cast<uint32_t>(p.step)));
+      slot = static_cast<int>(mix64(key ^ kImageSalt) % static_cast<uint64_t>(n_train));
+      const uint32_t w = permute_index(n, key, static_cast<uint32_t>(static_cast<uint64_t>(b) % n));
+      pix = (r0 + static_cast<int>(w) / cols) * ds.W + c0 + static_cast<int>(w) % cols;
+    }
+    const int img = clampi(train_idx[slot], 0, ds.n_images - 1);
+    if (image_idx_out) image_idx_out[b] = img;
+    if (pixel_out) pixel_out[b] = pix;
+    emit_batch_ray(ds, img, pix, b, out);
   }
 }
 
@@ -249,6 +387,62 @@ int ns_get_rays(int H, int W, float fx, float fy, float cx, float cy, const floa
   }
   get_rays_kernel<<<ns::ew_grid(R, kBlock), kBlock, 0, ns::as_stream(stream)>>>(
       cam, W, row0, R, near_, far_, rays_o_dev, rays_d_dev, viewdirs_dev, ray_batch_dev);
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+// what both ray-batch entries ask of the dataset descriptor and the batch size
+static int check_ray_dataset(const ns_ray_dataset* ds, int64_t B, bool rays, bool target, const char* who) {
+  auto bad = [&](const char* msg) { ns::set_error("%s: %s", who, msg); return NS_E_INVALID; };
+  if (!ds) return bad("null dataset");
+  if (B < 0 || B >= (int64_t(1) << 31)) return bad("batch size outside [0, 2^31)");
+  if (ds->n_images <= 0 || ds->H <= 0 || ds->W <= 0) return bad("empty dataset");
+  if (static_cast<int64_t>(ds->n_images) * ds->H * ds->W >= (int64_t(1) << 31)) return bad("n_images * H * W must be below 2^31");
+  if (ds->C != 3 && ds->C != 4) return bad("images have 3 or 4 channels");
+  if (ds->pose_stride != 12 && ds->pose_stride != 16) return bad("pose_stride is 12 or 16 floats");
+  if (rays && !ds->poses_dev) return bad("rays requested without poses");
+  if (target && !ds->images_dev) return bad("target requested without images");
+  return NS_OK;
+}
+
+int ns_ray_batch_gather(const ns_ray_dataset* ds, const int* image_idx_dev, int image_idx, const int* pixel_dev, int64_t B,
+                        float* rays_o_dev, float* rays_d_dev, float* viewdirs_dev, float* target_dev, void* stream) {
+  const int rc = check_ray_dataset(ds, B, rays_o_dev || rays_d_dev || viewdirs_dev, target_dev != nullptr, __func__);
+  if (rc != NS_OK) return rc;
+  NS_REQUIRE(image_idx_dev || (image_idx >= 0 && image_idx < ds->n_images), "image index out of range");
+  if (B == 0) return NS_OK;
+  NS_REQUIRE(pixel_dev, "null pixel indices");
+  ray_batch_gather_kernel<<<ns::ew_grid(B, kBlock), kBlock, 0, ns::as_stream(stream)>>>(
+      *ds, image_idx_dev, image_idx, pixel_dev, B, BatchOut{rays_o_dev, rays_d_dev, viewdirs_dev, target_dev});
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+int ns_ray_batch_draw(const ns_ray_dataset* ds, const int* train_idx_dev, int n_train, int scope, const int* params_dev,
+                      const ns_ray_draw_params* params_host, uint64_t seed, int64_t B, int* image_idx_out_dev,
+                      int* pixel_out_dev, float* rays_o_dev, float* rays_d_dev, float* viewdirs_dev, float* target_dev,
+                      void* stream) {
+  const int rc = check_ray_dataset(ds, B, rays_o_dev || rays_d_dev || viewdirs_dev, target_dev != nullptr, __func__);
+  if (rc != NS_OK) return rc;
+  NS_REQUIRE(scope == NS_RAY_SCOPE_PER_IMAGE || scope == NS_RAY_SCOPE_ALL_IMAGES, "unknown scope");
+  NS_REQUIRE(train_idx_dev && n_train > 0, "no training images");
+  NS_REQUIRE(static_cast<int64_t>(n_train) * ds->H * ds->W < (int64_t(1) << 31), "n_train * H * W must be below 2^31");
+  NS_REQUIRE((params_dev != nullptr) != (params_host != nullptr), "params come from the device or from the host");
+  ns_ray_draw_params host{0, 0, ds->H, 0, ds->W};
+  if (params_host) {
+    host = *params_host;
+    NS_REQUIRE(host.step >= 0, "negative step");
+    if (scope == NS_RAY_SCOPE_PER_IMAGE) {
+      NS_REQUIRE(host.row0 >= 0 && host.row1 <= ds->H && host.col0 >= 0 && host.col1 <= ds->W, "window outside the frame");
+      NS_REQUIRE(host.row0 < host.row1 && host.col0 < host.col1, "empty window");
+      NS_REQUIRE(B <= static_cast<int64_t>(host.row1 - host.row0) * (host.col1 - host.col0),
+                 "a per-image batch is drawn without replacement: B exceeds the window");
+    }
+  }
+  if (B == 0) return NS_OK;
+  ray_batch_draw_kernel<<<ns::ew_grid(B, kBlock), kBlock, 0, ns::as_stream(stream)>>>(
+      *ds, train_idx_dev, n_train, scope, params_dev, host, seed, B, image_idx_out_dev, pixel_out_dev,
+      BatchOut{rays_o_dev, rays_d_dev, viewdirs_dev, target_dev});
   NS_LAUNCH_CHECK();
   return NS_OK;
 }

@@ -39,6 +39,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                    "training the DepthNet; writes {root}/logs/{expname}_field/NNNNNN.tar (not in the reference).")
 @click.option("--gemm-engine", "gemm_engine", default="tile", type=click.Choice(["tile", "tall"]), show_default=True,
               help="With --fit-field: the GEMM kernel of the layer forwards and grad-input products (FieldFitter(gemm_engine=...)).")
+@click.option("--device-batches", "device_batches", default=None, type=click.Choice(["gather", "draw"]),
+              help="Make the training ray batches from a dataset resident on the device (Trainer(device_batches=...), not in the "
+                   "reference): 'gather' uploads the host's np.random draws as indices (the same batches), 'draw' draws them "
+                   "in the kernel with its own generator (other batches than np.random's).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -62,6 +66,8 @@ def main(**kw):
     k.update(ft_path=ft_path, depth_net_path=None, datadir=datadir, basedir=f"{root}/logs")
     if kw["fused_step"]:
         k["fused_step"] = True
+    if kw["device_batches"]:
+        k["device_batches"] = kw["device_batches"]
     if kw["fit_field"]:
         k.update(ft_path=None)
         return fit_field(load_obj_from_config(cfg=config), kw["iters"], gemm_engine=kw["gemm_engine"])
@@ -90,7 +96,8 @@ def fit_field(trainer, n_iters, gemm_engine="tile"):
                          lindisp=trainer.lindisp, near=trainer.near, far=trainer.far, gemm_engine=gemm_engine)
     split = dict(images=images, poses=poses, hwf=hwf, i_train=i_train)
     return fitter.fit(split, n_iters, N_rand=trainer.N_rand, basedir=trainer.basedir, expname=f"{trainer.expname}_field",
-                      i_weights=trainer.i_weights, i_print=trainer.i_print)
+                      i_weights=trainer.i_weights, i_print=trainer.i_print, device_batches=trainer.device_batches,
+                      batch_seed=trainer.batch_seed)
 
 
 if __name__ == "__main__":

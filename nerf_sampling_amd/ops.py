@@ -177,6 +177,24 @@ def get_rays(H: int, W: int, K, c2w, row0: int = 0, row1: Optional[int] = None, 
     return (o, d, v, b) if want_batch else (o, d, v)
 
 
+# ---- training ray batches from a device-resident dataset (ray_batches.py holds the dataset and the generator) -----------
+def ray_dataset(images, poses, hwf_or_K, i_train, white_bkgd: bool = False, device="cuda"):
+    """Upload a scene once: ray_batches.DeviceRayDataset."""
+    from .ray_batches import DeviceRayDataset
+
+    return DeviceRayDataset(images, poses, hwf_or_K, i_train, white_bkgd=white_bkgd, device=device)
+
+
+def ray_batch_gather(dataset, image_idx, pixels, want_viewdirs: bool = False, out=None):
+    """ns_ray_batch_gather: (batch_rays [2,B,3], target [B,3][, viewdirs]) of the named pixels (DeviceRayDataset.gather)."""
+    return dataset.gather(image_idx, pixels, want_viewdirs=want_viewdirs, out=out)
+
+
+def ray_batch_draw(dataset, B: int, step: int = 0, window=None, scope: str = "per_image", seed: int = 0, **kw):
+    """ns_ray_batch_draw: batch ``step`` drawn in the kernel, without replacement (DeviceRayDataset.draw)."""
+    return dataset.draw(B, step=step, window=window, scope=scope, seed=seed, **kw)
+
+
 # ---- a2 -------------------------------------------------------------------------------------------
 def sphere_intersect(o: Tensor, d: Tensor, radius: float) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()

@@ -33,11 +33,22 @@ class Trainer:
                  input_dims_embed: int = 1, save_train_set_render: bool = True, depth_net_lr: float = 0.0001,
                  train_depth_net_only: bool = False, trial=None, single_image=False, single_ray=False,
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
-                 hip_graph: bool = True):
+                 hip_graph: bool = True, device_batches=False, batch_seed: int = 0):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
         self.use_batching = not no_batching
+        # device_batches (not in the reference; default off): batches come from a dataset resident on the device
+        # (ray_batches.DeviceRayDataset).  "gather": the host draws below, uploaded as indices -- the same batch bit for bit;
+        # "draw": the kernel draws them with its own generator (seed: batch_seed), which is NOT np.random's stream.
+        self.device_batches = device_batches or False
+        if self.device_batches not in (False, "gather", "draw"):
+            raise ValueError(f"device_batches: False, 'gather' or 'draw', got {device_batches!r}")
+        if self.device_batches == "gather" and self.use_batching:
+            raise ValueError("device_batches='gather' repeats the no_batching draws; with use_batching choose 'draw'")
+        if self.device_batches == "draw" and single_ray:
+            raise ValueError("single_ray names its ray on the host: use device_batches='gather'")
+        self._ray_dataset = self._draw_source = None
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -168,12 +179,17 @@ class Trainer:
         images, poses, rays_rgb, i_batch = self.prepare_raybatch_tensor_if_batching_random_rays(poses, images, i_train)
         psnr = None
         # hip_graph (not in the reference; default on): the step is captured as one hipGraph after two eager steps
-        step = (self.graphed_optimization_loop(sampling_optimizer, render_kwargs_train)
-                if self.hip_graph and dev == "cuda" and hasattr(sampling_optimizer, "use_device_step")
+        graphed = self.hip_graph and dev == "cuda" and hasattr(sampling_optimizer, "use_device_step")
+        # device_batches='draw' under the graphed step: the draw is the first node of the captured graph
+        in_graph = graphed and self.device_batches == "draw"
+        source = self.draw_source(i_train, images, poses, self.start + 1) if in_graph else None
+        step = (self.graphed_optimization_loop(sampling_optimizer, render_kwargs_train, batch_source=source) if graphed
                 else lambda rays, it, tgt: self.core_optimization_loop(sampling_optimizer, render_kwargs_train, rays, it, tgt))
         for i in range(self.start + 1, N_iters):
-            rays_rgb, i_batch, batch_rays, target_s = self.sample_random_ray_batch(rays_rgb, i_batch, i_train, images,
-                                                                                   poses, i)
+            batch_rays = target_s = None
+            if not in_graph:
+                rays_rgb, i_batch, batch_rays, target_s = self.sample_random_ray_batch(rays_rgb, i_batch, i_train, images,
+                                                                                       poses, i)
             loss, depth_net_loss, psnr, _ = step(batch_rays, i, target_s)
             self.update_learning_rate(optimizer)
             if i % self.i_print == 0:
@@ -207,6 +223,8 @@ class Trainer:
         poses_t = torch.tensor(np.asarray(poses), dtype=torch.float32).to(dev)
         if not self.use_batching:
             return images, poses_t, None, None
+        if self.device_batches == "draw":         # the draw kernel walks the epoch itself: no rays_rgb, no permutation
+            return images, poses_t, None, 0
         rows = []
         for img_i in i_train:
             o, d, _ = ops.get_rays(self.H, self.W, self.K, poses_t[img_i, :3, :4], device=dev)
@@ -221,7 +239,10 @@ class Trainer:
 
     def sample_random_ray_batch(self, rays_rgb, i_batch, i_train, images, poses, i):
         """use_batching: the next N_rand rows of the shuffled rays_rgb, reshuffled (torch.randperm, as the reference)
-        after an epoch; otherwise N_rand random pixels of one random training image -- Trainer.py:400-475."""
+        after an epoch; otherwise N_rand random pixels of one random training image -- Trainer.py:400-475.  With
+        device_batches the batch comes from the device-resident dataset (see _device_batch)."""
+        if self.device_batches:
+            return (rays_rgb, i_batch) + self._device_batch(i_train, images, poses, i)
         if self.use_batching:
             batch = torch.transpose(rays_rgb[i_batch : i_batch + self.N_rand], 0, 1)     # [ro+rd+rgb, B, 3]
             batch_rays, target_s = batch[:2], batch[2]
@@ -253,6 +274,48 @@ class Trainer:
         target_s = target[sel[:, 0], sel[:, 1]].to(rays_o.device)
         return rays_rgb, i_batch, batch_rays, target_s
 
+    def ray_dataset(self, i_train, images, poses):
+        """The device-resident dataset of device_batches, uploaded at the first call."""
+        if self._ray_dataset is None:
+            from .ray_batches import DeviceRayDataset
+
+            self._ray_dataset = DeviceRayDataset(images, poses, self.K, i_train, white_bkgd=False)
+        return self._ray_dataset
+
+    def draw_source(self, i_train, images, poses, first_step):
+        """device_batches='draw': the batch source of this run (ray_batches.DrawBatchSource).  Its step counter lives on the
+        device, starts at ``first_step`` and advances by one per batch; the pre-crop is its window, use_batching its scope."""
+        if self._draw_source is None:
+            from .ray_batches import DrawBatchSource, precrop_window
+
+            ds = self.ray_dataset(i_train, images, poses)
+            crop = precrop_window(self.H, self.W, self.precrop_frac)
+            self._draw_source = DrawBatchSource(
+                ds, self.N_rand, scope="all_images" if self.use_batching else "per_image", seed=self.batch_seed,
+                first_step=first_step, window_fn=lambda it: crop if it < self.precrop_iters else None,
+                train_idx=[42] if (self.single_image and not self.use_batching) else i_train)
+        return self._draw_source
+
+    def _device_batch(self, i_train, images, poses, i):
+        """(batch_rays, target_s) of iteration ``i`` under device_batches.  'gather' makes the np.random.choice calls of the
+        default path in the same order, maps the drawn window positions to full-frame pixels on the host and uploads only
+        those indices: the default path's batch bit for bit.  'draw' asks the draw source."""
+        if self.device_batches == "draw":
+            return self.draw_source(i_train, images, poses, i)(i)
+        from .ray_batches import full_window, precrop_window
+
+        ds = self.ray_dataset(i_train, images, poses)
+        img_i = 42 if self.single_image else np.random.choice(i_train)
+        self.c2w = poses[img_i, :3, :4].clone().detach()
+        r0, r1, c0, c1 = (precrop_window(self.H, self.W, self.precrop_frac) if i < self.precrop_iters
+                          else full_window(self.H, self.W))
+        cols = c1 - c0
+        if self.single_ray:
+            select = np.array([91])
+        else:
+            select = np.random.choice((r1 - r0) * cols, size=[self.N_rand], replace=False)
+        return ds.gather(int(img_i), (r0 + select // cols) * self.W + c0 + select % cols)
+
     def _optimization_step(self, sampling_optimizer, render_kwargs_train, batch_rays, i, target_s, **render_extra):
         """forward + two losses + backward + update; (img_loss, depth_net_loss) as device scalars."""
         from .run_nerf_helpers import img2mse
@@ -276,10 +339,11 @@ class Trainer:
         render_kwargs_train["depth_network"].repack()
         return img_loss, depth_net_loss, psnr, None
 
-    def graphed_optimization_loop(self, sampling_optimizer, render_kwargs_train):
+    def graphed_optimization_loop(self, sampling_optimizer, render_kwargs_train, batch_source=None):
         """core_optimization_loop as ONE hipGraph replay per step (see GraphedDepthNetStep): same arguments after the
-        first two, same return value, same updates bit for bit."""
-        return GraphedDepthNetStep(self, sampling_optimizer, render_kwargs_train)
+        first two, same return value, same updates bit for bit.  ``batch_source``: a ray_batches.DrawBatchSource whose draw
+        becomes part of the graph."""
+        return GraphedDepthNetStep(self, sampling_optimizer, render_kwargs_train, batch_source=batch_source)
 
 
 class GraphedDepthNetStep:
@@ -294,10 +358,16 @@ class GraphedDepthNetStep:
     workspaces this object owns and on f16x3 streams it keeps alive.  The first ``warmup`` calls run eagerly (they are real steps and warm every
     lazily-built cache); the next call captures and replays.  A batch of another shape runs eagerly.
 
-    Call: ``step(batch_rays, i, target_s) -> (img_loss, depth_net_loss, psnr, None)`` like core_optimization_loop."""
+    Call: ``step(batch_rays, i, target_s) -> (img_loss, depth_net_loss, psnr, None)`` like core_optimization_loop.
 
-    def __init__(self, trainer, sampling_optimizer, render_kwargs_train, warmup: int = 2):
+    ``batch_source`` (a ray_batches.DrawBatchSource, optional): the batches are drawn on the device and ``batch_rays`` /
+    ``target_s`` of the call are ignored (pass None).  Eager steps draw one batch each; the capture records the draw launch and
+    its counter increment in front of the step, writing into the graph's own ray and target buffers, so a replay copies nothing
+    in.  The host only rewrites the source's window when it changes (``batch_source.begin(i)``)."""
+
+    def __init__(self, trainer, sampling_optimizer, render_kwargs_train, warmup: int = 2, batch_source=None):
         self.tr, self.opt, self.kw, self.warmup = trainer, sampling_optimizer, render_kwargs_train, warmup
+        self.source = batch_source
         self.calls, self.graph, self.shape = 0, None, None
         self.opt.use_device_step()
         # everything the captured kernels point into must outlive the graph: packed weight streams of the frozen networks
@@ -320,13 +390,18 @@ class GraphedDepthNetStep:
         return img_loss, dn_loss, mse2psnr(img_loss), None
 
     def _capture(self, batch_rays, target_s):
-        self.shape = (tuple(batch_rays.shape), tuple(target_s.shape))
-        self.rays, self.target = batch_rays.clone(), target_s.clone()
+        if self.source is not None:
+            self.rays, self.target = self.source.empty_batch()
+        else:
+            self.rays, self.target = batch_rays.clone(), target_s.clone()
+        self.shape = (tuple(self.rays.shape), tuple(self.target.shape))
         self.opt.zero_grad(set_to_none=True)           # backward inside the capture allocates the grads in the graph's pool
         torch.cuda.synchronize()
         self.opt.claim_capture_table()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
+            if self.source is not None:
+                self.source.launch(self.rays, self.target)
             self.img_loss, self.dn_loss = self.tr._optimization_step(self.opt, self.kw, self.rays, 1 << 30, self.target,
                                                                      **self._extra)
 
@@ -334,13 +409,19 @@ class GraphedDepthNetStep:
         from .run_nerf_helpers import mse2psnr
 
         self.calls += 1
-        if self.calls <= self.warmup or (self.shape is not None and
-                                         self.shape != (tuple(batch_rays.shape), tuple(target_s.shape))):
+        if self.source is not None:
+            if self.calls <= self.warmup:
+                batch_rays, target_s = self.source(i)
+                return self._eager(batch_rays, i, target_s)
+            self.source.begin(i)
+        elif self.calls <= self.warmup or (self.shape is not None and
+                                           self.shape != (tuple(batch_rays.shape), tuple(target_s.shape))):
             return self._eager(batch_rays, i, target_s)
         if self.graph is None:
             self._capture(batch_rays, target_s)        # records, does not execute
-        self.rays.copy_(batch_rays)
-        self.target.copy_(target_s)
+        if self.source is None:
+            self.rays.copy_(batch_rays)
+            self.target.copy_(target_s)
         self.opt.sync_device_lr()
         self.graph.replay()
         self.opt.note_replayed_step()
@@ -448,21 +529,28 @@ class FieldFitter:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         utils.save_state(self.global_step, self.network_fn, self.network_fine, self.optimizer, None, None, path)
 
-    def _blender_source(self, split, N_rand):
+    def _blender_source(self, split, N_rand, device_batches=False, batch_seed=0):
         """Batches of N_rand rays of a Blender split as Trainer.sample_random_ray_batch draws them (one random training image
         per batch).  ``split``: load_blender_data's (images, poses, render_poses, hwf, i_split), or a dict with images
-        [n,H,W,3|4], poses, hwf and i_train."""
+        [n,H,W,3|4], poses, hwf and i_train.  ``device_batches``: Trainer's option -- the images (all their channels) and poses
+        go to the device once, and the background blend happens per drawn pixel in the batch kernel."""
         if isinstance(split, dict):
             images, poses, hwf, i_train = split["images"], split["poses"], split["hwf"], split["i_train"]
         else:
             images, poses, _render_poses, hwf, i_split = split
             i_train = i_split[0]
         images = np.asarray(images)
-        if images.shape[-1] == 4:
-            images = (images[..., :3] * images[..., -1:] + (1.0 - images[..., -1:])) if self.white_bkgd else images[..., :3]
-        tr = Trainer(dataset_type="blender", basedir="", expname="", no_batching=True, datadir="", N_rand=N_rand, device="cuda")
+        tr = Trainer(dataset_type="blender", basedir="", expname="", no_batching=True, datadir="", N_rand=N_rand, device="cuda",
+                     device_batches=device_batches, batch_seed=batch_seed)
         tr.cast_intrinsics_to_right_types(hwf)
         poses_t = torch.tensor(np.asarray(poses), dtype=torch.float32).to("cuda")
+        if device_batches:
+            from .ray_batches import DeviceRayDataset
+
+            tr._ray_dataset = DeviceRayDataset(images.astype(np.float32, copy=False), poses_t, tr.K, i_train,
+                                               white_bkgd=self.white_bkgd)
+        elif images.shape[-1] == 4:
+            images = (images[..., :3] * images[..., -1:] + (1.0 - images[..., -1:])) if self.white_bkgd else images[..., :3]
 
         def draw(i):
             _, _, batch_rays, target = tr.sample_random_ray_batch(None, None, i_train, images, poses_t, i)
@@ -471,15 +559,18 @@ class FieldFitter:
         return draw
 
     def fit(self, rays_source, n_iters, N_rand=1024, basedir=None, expname="field", i_weights=10000, i_print=100,
-            evaluate=None):
+            evaluate=None, device_batches=False, batch_seed=0):
         """``n_iters`` steps on batches from ``rays_source``: a loaded Blender split (see _blender_source) or a callable
         returning (batch_rays [2,B,3], target [B,3]).  With ``basedir`` a checkpoint {basedir}/{expname}/{step:06d}.tar is written
         every ``i_weights`` steps and at the end.  ``evaluate(fitter)``, if given, runs at every ``i_print`` steps after repack().
-        Both networks are repacked before the call returns.  Returns the last (loss, psnr, psnr0)."""
+        Both networks are repacked before the call returns.  ``device_batches`` / ``batch_seed``: how a Blender split's batches
+        are made (_blender_source).  Returns the last (loss, psnr, psnr0)."""
         if callable(rays_source):
+            if device_batches:
+                raise ValueError("device_batches applies to a Blender split, not to a callable ray source")
             draw = lambda i: rays_source()  # noqa: E731
         else:
-            draw = self._blender_source(rays_source, N_rand)
+            draw = self._blender_source(rays_source, N_rand, device_batches=device_batches, batch_seed=batch_seed)
         out = None
         for i in range(1, int(n_iters) + 1):
             batch_rays, target = draw(i)
