@@ -41,6 +41,23 @@ int& prod_tiles_hint();
 int cu_count();
 hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes);
 
+// The launch rule of the persistent MLP kernels.  launch_plan refuses more dynamic LDS than a CU's 160 KiB (NS_E_UNSUPPORTED),
+// raises the kernel's limit to `lds` and sizes the grid: one workgroup per unit of `work` (groups, or runs of groups), at most
+// one per CU (256 when the CU count is unknown).  `who` names the entry point in the error string.
+int launch_plan(const char* who, const void* kernel, size_t lds, int64_t work, int* grid);
+template <class Args>
+int launch_persistent(const char* who, void (*kernel)(Args), const Args& a, int threads, size_t lds, int64_t work,
+                      hipStream_t stream) {
+  int grid = 0;
+  const int rc = launch_plan(who, reinterpret_cast<const void*>(kernel), lds, work, &grid);
+  if (rc != NS_OK) return rc;
+  kernel<<<grid, threads, lds, stream>>>(a);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return NS_OK;
+  set_error("%s: launch -> %s", who, hipGetErrorString(e));
+  return NS_E_HIP;
+}
+
 }  // namespace ns
 
 // internal (not part of the public header)

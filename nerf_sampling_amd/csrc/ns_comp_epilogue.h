@@ -3,7 +3,7 @@
 // this code with their own group shape.  A group is NWAVES x T tiles of 16 samples = T chunks of 64 consecutive samples; wave w
 // holds samples w * 16 T .. (w + 1) * 16 T - 1 of it, so with T != 4 a chunk straddles waves.
 //
-// Args (Nerf16Args, NerfX3CompArgs, nstan::TanArgs) carries the fields of nsepi::CompFields under the same names.
+// Args (Nerf16Args, NerfX3CompArgs, nstan::TanArgs) inherits nsepi::CompFields.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,27 +35,43 @@ typedef uint32_t __attribute__((address_space(3))) * CslotPtr;
 constexpr int kFixLongFloats = NS_FIX_LONG_FLOATS, kFixLongOperands = 16;
 static_assert(kFixLongOperands + 6 * 5 <= kFixLongFloats, "six operands of five sums behind the single-chunk record's fields");
 
-// The compositing fields of a kernel's argument struct, which place_wave / composite_group / set_comp_args read by name
-// (Nerf16Args, ns_nerf_mlp_ob16.hip, spells them out among its own fields and documents each)
+// The compositing fields of a kernel's argument struct (Nerf16Args, NerfX3CompArgs, nstan::TanArgs inherit them), which place_wave /
+// composite_group / set_comp_args read by name.
+// In-kernel compositing (the DepthNet branch of render_rays_test as ONE kernel, nerf_utils.py:836-865): comp != 0 runs
+// raw2outputs (sampling_trainer.py:153-230) on the wave scan of ns_composite_ray.h in the epilogue -- raw then never
+// leaves the CU (raw may be NULL).  comp == 1: depths from the array z [S];  comp == 2: sample_points_around_mean
+// ("uniform", utils.py:231-241) evaluated in-kernel from the DepthNet depth mean [R] -- no z array exists.
+// N is a power of two <= 64 (whole rays per 64-sample chunk) or a multiple of 64 up to 512 (whole chunks per ray).
 struct CompFields {
   int comp;
-  int n_shift;
+  int n_shift;             // log2 N when N is a power of two, else -1
   const float* mean;
-  float std_, lin_step;
+  float std_, lin_step;    // the grid linspace(-std, std, N - 1) and its step (correctly rounded on the host)
   int white_bkgd;
   float* rgb; int64_t rgb_stride;
   float* disp; int64_t disp_stride;
-  float* weights;
-  float* z_out;
-  float* pts_out;
-  const float* sig_last;
+  float* weights;          // [S] or NULL
+  float* z_out;            // [S] or NULL (comp == 2: the depths the kernel placed)
+  float* pts_out;          // [S,3] or NULL
+  const float* sig_last;   // NULL, or [R,4]: element 3 of row r replaces sigma of ray r's last sample (the guard pass)
+  // rays longer than a 64-sample chunk (N = 64 m, m = m_chunks >= 2; 0 otherwise): a workgroup then walks sg_groups CONSECUTIVE
+  // groups -- lcm(group samples, N) samples, whole rays -- before it jumps, so that a ray's chunks meet in one workgroup and
+  // the transmittance / sums of the ray that is open at a group boundary carry over in LDS
   int m_chunks, sg_groups;
+  // the selective guard: a ray whose own sigma of the last sample is within fix_thr of zero -- where the step
+  // alpha = step(sigma) could flip under the 16-bit rounding -- leaves a record at slot atomicAdd(fix_count) of fix_rec.  Rays of
+  // one chunk: 16 floats {tree sums r g b depth acc, T, raw rgb of the last sample, its z and dist, ray index lo / hi}
+  // (ns_fix_last_sample re-evaluates sigma through the fp32-grade handle and repeats the last addition).  Rays of several chunks:
+  // kFixLongFloats floats, the operands of the last chunk's additions as well (above, ns_fix_last_sample_long)
   float fix_thr;
   uint32_t* fix_count;
   float* fix_rec;
+  // the max-weight sample of every ray (nerf_utils.py:813-819), all three or none: max_z, max_w [R] and max_rgb [R,3] get the z,
+  // the weight and sigmoid(raw rgb) of the sample argmax(weights) picks
   float* max_z;
   float* max_w;
   float* max_rgb;
+  // the per-ray expected depth and opacity sums (ns_composite_args::depth_dev / acc_dev): [R] each, or NULL
   float* depth;
   float* acc;
 };

@@ -498,7 +498,7 @@ patch_sigma_last_kernel(float4* __restrict__ raw, const float4* __restrict__ raw
 }  // namespace
 // sigma of every ray's last sample <- the guard pass's (ns_render_args::nerf_guard; the chain renderer)
 // ---- the selective guard (ns_render_args::guard_threshold): the one-kernel renderer left a record per ray whose 16-bit sigma of
-// the last sample lies within the threshold of zero (Nerf16Args::fix_rec); the count lives on the device, the launches cover the
+// the last sample lies within the threshold of zero (nsepi::CompFields::fix_rec); the count lives on the device, the launches cover the
 // capacity and return at once past it.
 __device__ __forceinline__ int64_t fix_ray_of(const float* rec) {
   return static_cast<int64_t>(static_cast<uint64_t>(__builtin_bit_cast(uint32_t, rec[11])) |

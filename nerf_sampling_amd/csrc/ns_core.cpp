@@ -49,6 +49,22 @@ hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes) {
   return e;
 }
 
+int launch_plan(const char* who, const void* kernel, size_t lds, int64_t work, int* grid) {
+  if (lds > 160 * 1024) {
+    set_error("%s: %zu bytes of LDS needed (too deep a network for the resident bias image)", who, lds);
+    return NS_E_UNSUPPORTED;
+  }
+  const hipError_t e = ensure_dynamic_lds(kernel, lds);
+  if (e != hipSuccess) {
+    set_error("%s: dynamic LDS limit of %zu bytes -> %s", who, lds, hipGetErrorString(e));
+    return NS_E_HIP;
+  }
+  int cus = cu_count();
+  if (cus <= 0) cus = 256;
+  *grid = static_cast<int>(work < cus ? work : cus);
+  return NS_OK;
+}
+
 // Diagnostic switches: read from the environment ONCE (first use), changed afterwards only through ns_debug_set -- no
 // getenv on the launch path.
 DebugFlags& debug_flags() {

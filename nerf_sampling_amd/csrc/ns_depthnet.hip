@@ -11,30 +11,23 @@ namespace {
 
 using namespace nsmlp;
 
-struct DepthArgs {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
-  int n_layers;   // trunk layers (layer 0 is the folded 252 -> W one)
-  const float* o;
-  const float* d;
-  int64_t R;
-  float near_, far_, radius;
-  float* z;
-};
+constexpr int kWaves = 4;   // one wave per SIMD
 
-template <class M, int NB, int NWAVES, bool PRECISE_TRIG>
-__global__ void __launch_bounds__(NWAVES * 64)
+// the exact-fp32 path: Trig<true>, the polynomial sine
+template <class M, int NB>
+__global__ void __launch_bounds__(kWaves * 64)
 depthnet_kernel(DepthArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NWAVES = kWaves;
+  constexpr bool PRECISE_TRIG = true;
   using Block = typename M::Block;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5;
 
-  using PipeT = Pipe<M, NWAVES, 0>;
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using PipeT = Pipe<M, NWAVES>;
+  constexpr uint32_t kBiasAt = KMajorLds<PipeT>(0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
 
@@ -105,29 +98,15 @@ int depthnet_program_slabs(int cpb, int NB, int n) {
   return seg_slabs(cpb, NB, 8) + (n - 1) * seg_slabs(cpb, NB, NB) + seg_slabs(cpb, 1, NB);
 }
 
-template <class M, int NB, int NWAVES, bool PRECISE>
+template <class M, int NB>
 int launch(DepthArgs& a, hipStream_t stream) {
-  const size_t lds = static_cast<size_t>(Pipe<M, NWAVES, 0>::kLdsBytes) + static_cast<size_t>(a.bias_floats) * 4;
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_depthnet_forward: %zu bytes of LDS needed (too many layers for the resident bias image)", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  auto kern = depthnet_kernel<M, NB, NWAVES, PRECISE>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t n_tiles = (a.R + 31) / 32;
-  const int64_t n_groups = (n_tiles + NWAVES - 1) / NWAVES;
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
-  const int grid = static_cast<int>(n_groups < cus ? n_groups : cus);
-  kern<<<grid, NWAVES * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  const int64_t n_groups = (n_tiles + kWaves - 1) / kWaves;
+  return ns::launch_persistent("ns_depthnet_forward", depthnet_kernel<M, NB>, a, kWaves * 64,
+                               KMajorLds<Pipe<M, kWaves>>(a.bias_floats).end, n_groups, stream);
 }
 
 }  // namespace
-
-int ns_depthnet_forward_ob16(const ns_weights* net, const float* o_dev, const float* d_dev, int64_t R, float near_,
-                             float far_, float sphere_radius, float* z_dev, hipStream_t stream);
 
 extern "C" {
 
@@ -147,11 +126,8 @@ int ns_depthnet_forward(const ns_weights* net, const float* o_dev, const float* 
     return NS_E_INVALID;
   }
   DepthArgs a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.n_layers = net->depth; a.o = o_dev; a.d = d_dev; a.R = R;
-  a.near_ = near_; a.far_ = far_; a.radius = sphere_radius; a.z = z_dev;
-  return NB == 8 ? launch<MmaF32, 8, 4, true>(a, s) : launch<MmaF32, 4, 4, true>(a, s);
+  set_depth_args(a, net, o_dev, d_dev, R, near_, far_, sphere_radius, z_dev);
+  return NB == 8 ? launch<MmaF32, 8>(a, s) : launch<MmaF32, 4>(a, s);
 }
 
 }  // extern "C"

@@ -48,41 +48,45 @@ struct Split16 {
   __device__ static __forceinline__ void convert_last(OutT& out, const f32x4a (&last)[T]) { convert_last16x3<ACT, T, NSB>(out, last); }
 };
 
-struct Depth16Args {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
-  int n_layers;   // trunk layers; layer 0 is the folded 252 -> W one
-  const float* o;
-  const float* d;
-  int64_t R;
-  float near_, far_, radius;
-  float* z;
+// dynamic LDS of both kernels: [weight ring][bias image][input staging: per wave 6 x 256 B] and, for the mixed-operand kernel
+// (PARK), [parked half: per wave 16 blocks x 1 KiB]
+template <bool PARK>
+struct Depth16Lds {
+  static constexpr uint32_t kWaveStage = 6 * 256, kWavePark = PARK ? 16 * 1024 : 0;
+  uint32_t ring = 0, bias = 0, stage = 0, park = 0, end = 0;
+  __host__ __device__ constexpr explicit Depth16Lds(int bias_floats) {
+    LdsCarve c;
+    ring = c.take(kOb16RingBytes);
+    bias = c.take(static_cast<uint32_t>(bias_floats) * 4u);
+    stage = c.take(kWaves * kWaveStage);
+    park = c.take(kWaves * kWavePark);
+    end = c.at;
+  }
 };
 
 // PROD: ten layers of 8 K-blocks -> 256 (the production DepthNet after the fold) as straight-line code, every layer a
 // generated statement: the embedding is set V (v[128:255]), layers alternate V -> A -> V, the head reads set V.
 template <class E, int NKB, bool PROD = false>   // E: engine policy; NKB = W / 32 K-blocks of a hidden layer
 __global__ void __launch_bounds__(kWaves * 64)
-depthnet_ob16_kernel(Depth16Args a) {
+depthnet_ob16_kernel(DepthArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using M = typename E::M;
   constexpr int T = E::T, NWAVES = kWaves, NSB = 2 * NKB;
   constexpr bool PT = E::kPreciseTrig;
   using Block = typename M::Block;
-  using PipeT = Pipe<M, NWAVES, 0, kOb16Depth, kOb16Ahead>;
+  using PipeT = Pipe<M, NWAVES, kOb16Depth, kOb16Ahead>;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
 
-  // LDS: [weight ring][bias image][input staging: per wave 6 x 256 B]
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using Lds = Depth16Lds<false>;
+  constexpr uint32_t kBiasAt = Lds(0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
   const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NS_LDS_PTR(smem)));
-  const uint32_t stage_base = lds0 + PipeT::kLdsBytes + ((static_cast<uint32_t>(a.bias_floats) * 4u + 15u) & ~15u) +
-                              static_cast<uint32_t>(wave) * (6 * 256);
+  const Lds lm(a.bias_floats);
+  const uint32_t stage_base = lds0 + lm.stage + static_cast<uint32_t>(wave) * Lds::kWaveStage;
 
   PipeT ring;
   ring.init(a.stream, smem, a.n_slabs, wave, lane);
@@ -230,25 +234,26 @@ depthnet_ob16_kernel(Depth16Args a) {
 // MFMAs per ray: (3 KX + 10 - KX) / 10 of the fp16 kernel's (1.6 x at KX = 3; all-split: 3 x).
 template <int KX>
 __global__ void __launch_bounds__(kWaves * 64)
-depthnet_mix_kernel(Depth16Args a) {
+depthnet_mix_kernel(DepthArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(KX >= 1 && KX <= 9 && (KX & 1) == 1, "an odd number of split layers: their output is set A, as layer KX expects");
   using MS = Mma16F16x3;
   using MP = Mma16F16;
   constexpr int T = 4, NWAVES = kWaves, NKB = 8, NSB = 16, NT = 4;
-  using PipeT = Pipe<MP, NWAVES, 0, kOb16Depth, kOb16Ahead>;
+  using PipeT = Pipe<MP, NWAVES, kOb16Depth, kOb16Ahead>;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
 
-  // LDS: [weight ring][bias image][input staging: per wave 6 x 256 B][parked half: per wave 16 blocks x 1 KiB]
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using Lds = Depth16Lds<true>;
+  constexpr uint32_t kBiasAt = Lds(0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
   const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NS_LDS_PTR(smem)));
-  const uint32_t after_bias = lds0 + PipeT::kLdsBytes + ((static_cast<uint32_t>(a.bias_floats) * 4u + 15u) & ~15u);
-  const uint32_t stage_base = after_bias + static_cast<uint32_t>(wave) * (6 * 256);
-  const uint32_t park_base = after_bias + NWAVES * (6 * 256) + static_cast<uint32_t>(wave) * (16 * 1024) + static_cast<uint32_t>(lane) * 16u;
+  const Lds lm(a.bias_floats);
+  const uint32_t stage_base = lds0 + lm.stage + static_cast<uint32_t>(wave) * Lds::kWaveStage;
+  const uint32_t park_base = lds0 + lm.park + static_cast<uint32_t>(wave) * Lds::kWavePark + static_cast<uint32_t>(lane) * 16u;
   typedef u32x4 __attribute__((address_space(3))) * ParkPtr;
   auto park_at = [&](int k) -> ParkPtr { return reinterpret_cast<ParkPtr>(static_cast<uintptr_t>(park_base + static_cast<uint32_t>(k) * 1024u)); };
 
@@ -362,24 +367,11 @@ int depth16_mix_program_slabs(int kx) {
 }
 
 template <int KX>
-int launch_mix(Depth16Args& a, hipStream_t stream) {
-  const size_t lds = static_cast<size_t>(Pipe<Mma16F16, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
-                     ((static_cast<size_t>(a.bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * 6 * 256 +
-                     static_cast<size_t>(kWaves) * 16 * 1024;
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_depthnet_forward: %zu bytes of LDS needed by the mixed-operand kernel", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  auto kern = depthnet_mix_kernel<KX>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+int launch_mix(DepthArgs& a, hipStream_t stream) {
   const int64_t n_tiles = (a.R + 15) / 16;
   const int64_t n_groups = (n_tiles + kWaves * 4 - 1) / (kWaves * 4);
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
-  const int grid = static_cast<int>(n_groups < cus ? n_groups : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  return ns::launch_persistent("ns_depthnet_forward", depthnet_mix_kernel<KX>, a, kWaves * 64,
+                               Depth16Lds<true>(a.bias_floats).end, n_groups, stream);
 }
 
 int depth16_program_slabs(int W, int n_layers, int cpk) {   // cpk: stream chunks per K-block (2 for split operands)
@@ -389,24 +381,11 @@ int depth16_program_slabs(int W, int n_layers, int cpk) {   // cpk: stream chunk
 }
 
 template <class E, int NKB, bool PROD = false>
-int launch(Depth16Args& a, hipStream_t stream) {
-  using M = typename E::M;
-  const size_t lds = static_cast<size_t>(Pipe<M, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
-                     ((static_cast<size_t>(a.bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * 6 * 256;
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_depthnet_forward: %zu bytes of LDS needed (too many layers for the resident bias image)", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  auto kern = depthnet_ob16_kernel<E, NKB, PROD>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+int launch(DepthArgs& a, hipStream_t stream) {
   const int64_t n_tiles = (a.R + 15) / 16;
   const int64_t n_groups = (n_tiles + kWaves * E::T - 1) / (kWaves * E::T);
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
-  const int grid = static_cast<int>(n_groups < cus ? n_groups : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  return ns::launch_persistent("ns_depthnet_forward", depthnet_ob16_kernel<E, NKB, PROD>, a, kWaves * 64,
+                               Depth16Lds<false>(a.bias_floats).end, n_groups, stream);
 }
 
 }  // namespace
@@ -414,17 +393,14 @@ int launch(Depth16Args& a, hipStream_t stream) {
 // called by ns_depthnet_forward for handles packed with layout 16 (arguments validated there)
 int ns_depthnet_forward_ob16(const ns_weights* net, const float* o_dev, const float* d_dev, int64_t R, float near_,
                              float far_, float sphere_radius, float* z_dev, hipStream_t stream) {
+  DepthArgs a{};
+  set_depth_args(a, net, o_dev, d_dev, R, near_, far_, sphere_radius, z_dev);
   if (net->dtype == NS_DTYPE_F16M) {      // mixed operands: the production shape only (the packer refuses others)
     if (net->width != 256 || net->depth != 10 || depth16_mix_program_slabs(NS_F16M_SPLIT_LAYERS) != static_cast<int>(net->n_slabs)) {
       ns::set_error("ns_depthnet_forward: not a mixed-operand stream of the 10 x 256 trunk (%u slabs)", net->n_slabs);
       return NS_E_INVALID;
     }
-    Depth16Args m{};
-    m.stream = static_cast<const char*>(net->stream_dev);
-    m.bias = net->bias_dev; m.n_slabs = net->n_slabs; m.bias_floats = net->bias_floats;
-    m.n_layers = net->depth; m.o = o_dev; m.d = d_dev; m.R = R;
-    m.near_ = near_; m.far_ = far_; m.radius = sphere_radius; m.z = z_dev;
-    return launch_mix<NS_F16M_SPLIT_LAYERS>(m, stream);
+    return launch_mix<NS_F16M_SPLIT_LAYERS>(a, stream);
   }
   const int cpk = net->dtype == NS_DTYPE_F16X3 ? 2 : 1;
   if (depth16_program_slabs(net->width, net->depth, cpk) != static_cast<int>(net->n_slabs)) {
@@ -432,11 +408,6 @@ int ns_depthnet_forward_ob16(const ns_weights* net, const float* o_dev, const fl
                   depth16_program_slabs(net->width, net->depth, cpk));
     return NS_E_INVALID;
   }
-  Depth16Args a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.n_layers = net->depth; a.o = o_dev; a.d = d_dev; a.R = R;
-  a.near_ = near_; a.far_ = far_; a.radius = sphere_radius; a.z = z_dev;
   const bool wide = net->width == 256;
   if (net->dtype == NS_DTYPE_BF16) return wide ? launch<Plain16<Mma16BF16>, 8>(a, stream) : launch<Plain16<Mma16BF16>, 4>(a, stream);
   if (net->dtype == NS_DTYPE_F16) {

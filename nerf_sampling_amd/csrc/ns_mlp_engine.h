@@ -27,6 +27,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "ns_weights.h"
+
 namespace nsmlp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -59,81 +61,6 @@ __host__ __device__ __forceinline__ void static_for(F&& f) {
 
 // ---- operand traits --------------------------------------------------------------------------
 // CPB = chunks per 32-feature input block; Block = one lane's 16 features of a 32-feature block.
-struct MmaBF16 {
-  static constexpr int kDtype = 1;
-  static constexpr int CPB = 2;
-  static constexpr int kElemBytes = 2;
-  struct Block { bf16x8 v[2]; };
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  // one dword = two consecutive features.  hipcc (ROCm 7.2) lowers a {(__bf16)a, (__bf16)b} pair to two
-  // single-value v_cvt_pk_bf16_f32 + a v_perm_b32; the packed form is ONE instruction (RNE, NaN-preserving).
-  // ReLU on the packed pair is a signed 16-bit max with 0 (sign-magnitude floats: negative <=> negative int16).
-  template <bool RELU>
-  __device__ static __forceinline__ uint32_t pack2(float a, float b) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 ab = {a, b};
-    uint32_t r = __builtin_bit_cast(uint32_t, __builtin_convertvector(ab, bf16x2));   // one v_cvt_pk_bf16_f32
-    if constexpr (RELU) {
-      s16x2 q = __builtin_bit_cast(s16x2, r);
-      q = __builtin_elementwise_max(q, (s16x2)(0));
-      r = __builtin_bit_cast(uint32_t, q);
-    }
-    return r;
-  }
-  template <bool RELU = false>
-  __device__ static __forceinline__ void from_f32(Block& b, const float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      u32x4 w = {pack2<RELU>(x[8 * i], x[8 * i + 1]), pack2<RELU>(x[8 * i + 2], x[8 * i + 3]),
-                 pack2<RELU>(x[8 * i + 4], x[8 * i + 5]), pack2<RELU>(x[8 * i + 6], x[8 * i + 7])};
-      b.v[i] = __builtin_bit_cast(bf16x8, w);
-    }
-  }
-  using AFrag = bf16x8;
-  template <int SUB>
-  __device__ static __forceinline__ void mma(f32x16& acc, const AFrag& a, const Block& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b.v[SUB], acc, 0, 0, 0);
-  }
-};
-
-struct MmaF16 {
-  static constexpr int kDtype = 2;
-  static constexpr int CPB = 2;
-  static constexpr int kElemBytes = 2;
-  struct Block { f16x8 v[2]; };
-  typedef short s16x2 __attribute__((ext_vector_type(2)));
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  template <bool RELU>
-  __device__ static __forceinline__ uint32_t pack2(float a, float b) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 ab = {a, b};
-    uint32_t r = __builtin_bit_cast(uint32_t, __builtin_convertvector(ab, f16x2));
-    if constexpr (RELU) {
-      s16x2 q = __builtin_bit_cast(s16x2, r);
-      q = __builtin_elementwise_max(q, (s16x2)(0));
-      r = __builtin_bit_cast(uint32_t, q);
-    }
-    return r;
-  }
-  template <bool RELU = false>
-  __device__ static __forceinline__ void from_f32(Block& b, const float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      u32x4 w = {pack2<RELU>(x[8 * i], x[8 * i + 1]), pack2<RELU>(x[8 * i + 2], x[8 * i + 3]),
-                 pack2<RELU>(x[8 * i + 4], x[8 * i + 5]), pack2<RELU>(x[8 * i + 6], x[8 * i + 7])};
-      b.v[i] = __builtin_bit_cast(f16x8, w);
-    }
-  }
-  using AFrag = f16x8;
-  template <int SUB>
-  __device__ static __forceinline__ void mma(f32x16& acc, const AFrag& a, const Block& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b.v[SUB], acc, 0, 0, 0);
-  }
-};
-
 struct MmaF32 {
   static constexpr int kDtype = 0;
   static constexpr int CPB = 4;
@@ -144,7 +71,6 @@ struct MmaF32 {
 #pragma unroll
     for (int j = 0; j < 16; ++j) b.v[j] = RELU ? (x[j] < 0.0f ? 0.0f : x[j]) : x[j];   // NaN stays NaN, as torch.relu (fmaxf would drop it)
   }
-  __device__ static __forceinline__ void relu_packed(Block&) {}
   using AFrag = f32x4;
   template <int SUB>
   __device__ static __forceinline__ void mma(f32x16& acc, const AFrag& a, const Block& b) {
@@ -188,18 +114,13 @@ __device__ __forceinline__ void lds_dma4(const void* gptr, uint32_t lds_base) {
 // issued right after the barrier that opens slab t into the slot slab t-1 just vacated.  Every DS
 // read is issued kFragDepth chunks before the MFMA that consumes it, so neither the LDS latency nor
 // the barrier sits on the MFMA critical path.
-//
-// LAG > 0 staggers the second half of the workgroup's waves (the SIMD partners of the first half:
-// MI355X_MICROARCH.md "Two waves per SIMD", item 9) LAG slabs behind the first half, so that one
-// partner's layer epilogue / tile prologue (VALU, global loads) runs under the other's MFMAs instead
-// of both leaving the matrix pipe idle at once.  It costs LAG more ring slots.
-template <class M, int NWAVES, int LAG = 0, int DEPTH = kFragDepth, int AHEAD = kRingBase - 1>
+template <class M, int NWAVES, int DEPTH = kFragDepth, int AHEAD = kRingBase - 1>
 struct Pipe {
   static_assert(AHEAD >= 2, "the slab after the open one must have landed, one more must be in flight");
   static constexpr int kDepth = DEPTH;   // A fragments in flight (LDS read-ahead, in chunks)
   using AFrag = typename M::AFrag;
   static constexpr int LPW = kSlabChunks / NWAVES;  // DMA instructions per wave per slab
-  static constexpr int RING = AHEAD + 1 + LAG;   // slabs issued ahead of the open one, + the open one
+  static constexpr int RING = AHEAD + 1;   // slabs issued ahead of the open one, + the open one
   static constexpr int kLdsBytes = RING * kSlabBytes;
   const char* stream;   // device weight stream, n_slabs * 16 KiB, cyclic
   char* lds;            // ring base in LDS
@@ -283,7 +204,6 @@ struct Pipe {
   __device__ __forceinline__ void load(AFrag& dst, uint32_t addr) const {
     dst = *reinterpret_cast<const AFrag __attribute__((address_space(3)))*>(static_cast<uintptr_t>(addr + OFF));
   }
-  __device__ static __forceinline__ void wait_frag(AFrag&) {}
 
   __device__ __forceinline__ void init(const char* stream_, char* lds_, uint32_t n_slabs_, int wave_, int lane_) {
     stream = stream_; lds = lds_; n_slabs = n_slabs_; wave = wave_; lane = lane_;
@@ -297,32 +217,10 @@ struct Pipe {
     nxt = lds_off + lane * 16;                    // slab 0 is "the following slab" until it is opened
     cur = nxt;
     static_for<DEPTH>([&](auto i_) { load<decltype(i_)::value * kChunkBytes>(f[decltype(i_)::value], nxt); });
-    if constexpr (LAG > 0) {
-      if (wave >= NWAVES / 2) {                   // trailing half: sit out the first LAG slabs
-#pragma unroll 1
-        for (int i = 0; i < LAG; ++i) idle_slab();
-      }
-    }
   }
 
-  // take part in a slab step (wait, barrier, DMA issue) without opening a slab
-  __device__ __forceinline__ void idle_slab() {
-    wait_vm<(AHEAD - 2) * LPW>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue();
-  }
-
-  // after the last tile: the leading half keeps the slab steps going until the trailing half is done
-  __device__ __forceinline__ void finish() {
-    if constexpr (LAG > 0) {
-      if (wave < NWAVES / 2) {
-#pragma unroll 1
-        for (int i = 0; i < LAG; ++i) idle_slab();
-      }
-    }
-    drain();
-  }
+  // after the last tile
+  __device__ __forceinline__ void finish() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 
   // Open the next slab: its first kFragDepth fragments are already in registers.
   __device__ __forceinline__ void begin_slab() {
@@ -334,9 +232,85 @@ struct Pipe {
     read_slot = next_slot(read_slot);
     nxt = lds_off + read_slot * kSlabBytes + lane * 16;
   }
-
-  __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 };
+
+// ---- dynamic-LDS maps -------------------------------------------------------------------------------
+// Hands out the regions of a kernel's dynamic LDS in order, 16-byte aligned, as byte offsets from its start (as Carve in
+// ns_render.cpp does for the renderers' workspace).  Every kernel's map is written once on it: the kernel adds a region's offset
+// to its LDS base, its launcher takes `end`, the bytes to ask for.  Only bias_floats is a run-time input.
+// The maps are constexpr: no region before the bias image depends on bias_floats, so a kernel takes the image's offset at
+// compile time, Map(0).bias, for the pointer it reads the biases through (a run-time offset there changes the code generated).
+struct LdsCarve {
+  uint32_t at = 0;
+  __host__ __device__ constexpr uint32_t take(uint32_t bytes) {
+    const uint32_t p = at;
+    at += (bytes + 15u) & ~15u;
+    return p;
+  }
+};
+// the k-major kernels (ns_nerf_mlp.hip, ns_depthnet.hip): [weight ring][bias image]
+template <class PipeT>
+struct KMajorLds {
+  uint32_t ring = 0, bias = 0, end = 0;
+  __host__ __device__ constexpr explicit KMajorLds(int bias_floats) {
+    LdsCarve c;
+    ring = c.take(PipeT::kLdsBytes);
+    bias = c.take(static_cast<uint32_t>(bias_floats) * 4u);
+    end = c.at;
+  }
+};
+
+// ---- kernel arguments -------------------------------------------------------------------------------
+// what every persistent MLP kernel takes of its ns_weights: the weight stream and the bias image
+struct StreamArgs {
+  const char* stream;
+  const float* bias;
+  uint32_t n_slabs;
+  int bias_floats;
+};
+inline void set_stream_args(StreamArgs& a, const ns_weights* net) {
+  a.stream = static_cast<const char*>(net->stream_dev);
+  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
+}
+// the radiance-field forward (ns_nerf_mlp.hip, ns_nerf_mlp_ob16.hip, ns_nerf_mlp_x3.hip)
+struct FieldArgs : StreamArgs {
+  int D;
+  uint32_t skip_mask;     // bit i: layer i + 1 sees cat[x, h]
+  int use_viewdirs, out_ch, x_stride;   // x_stride: row length of the pre-embedded input (90, or 63 without view directions)
+  // inputs: either pts [S,3] or (o,d [R,3], z [S]); or x [S,90] pre-embedded
+  const float* pts;
+  const float* o;
+  const float* d;
+  const float* z;
+  const float* viewdirs;  // [R,3]
+  const float* x90;
+  int64_t S;              // total samples R*N
+  int N;                  // samples per ray
+  float* raw;             // [S,4]
+};
+inline void set_field_args(FieldArgs& a, const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
+                           const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N, float* raw_dev) {
+  set_stream_args(a, net);
+  a.D = net->depth; a.skip_mask = net->skip_mask; a.use_viewdirs = net->use_viewdirs; a.out_ch = net->out_ch;
+  a.x_stride = net->use_viewdirs ? 90 : 63;
+  a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = x90_dev;
+  a.S = S; a.N = N; a.raw = raw_dev;
+}
+// the DepthNet forward (ns_depthnet.hip, ns_depthnet_ob16.hip)
+struct DepthArgs : StreamArgs {
+  int n_layers;   // trunk layers; layer 0 is the folded 252 -> W one
+  const float* o;
+  const float* d;
+  int64_t R;
+  float near_, far_, radius;
+  float* z;
+};
+inline void set_depth_args(DepthArgs& a, const ns_weights* net, const float* o_dev, const float* d_dev, int64_t R, float near_,
+                           float far_, float sphere_radius, float* z_dev) {
+  set_stream_args(a, net);
+  a.n_layers = net->depth; a.o = o_dev; a.d = d_dev; a.R = R;
+  a.near_ = near_; a.far_ = far_; a.radius = sphere_radius; a.z = z_dev;
+}
 
 // ---- one K-segment of a layer: acc[NBO] += W[:, segment] . in[NBLK] -----------------------------
 template <class M, int NBO, int NBLK, class PipeT>
@@ -355,7 +329,6 @@ __device__ __forceinline__ void consume(PipeT& pipe, f32x16 (&acc)[NBO],
       constexpr int p = decltype(p_)::value;
       constexpr int kk = p / NBO, nb = p % NBO;
       constexpr int kc = s * KPS + kk;
-      PipeT::wait_frag(pipe.f[p % kFragDepth]);
       M::template mma<kc % M::CPB>(acc[nb], pipe.f[p % kFragDepth], in[kc / M::CPB]);
       if constexpr (p + kFragDepth < USED)
         pipe.template load<(p + kFragDepth) * kChunkBytes>(pipe.f[p % kFragDepth], pipe.cur);
@@ -598,8 +571,23 @@ struct Mma16BF16 {
   static constexpr bool kPackedLeaky = false;     // (gfx950 has no packed bf16 multiply / max: LeakyReLU runs on the fp32 values)
   using AFrag = bf16x8;
   struct Block { bf16x8 v; };                       // one lane's 8 features of a 32-feature K-block
+  // one dword = two consecutive features.  hipcc (ROCm 7.2) lowers a {(__bf16)a, (__bf16)b} pair to two
+  // single-value v_cvt_pk_bf16_f32 + a v_perm_b32; the packed form is ONE instruction (RNE, NaN-preserving).
+  // ReLU on the packed pair is a signed 16-bit max with 0 (sign-magnitude floats: negative <=> negative int16).
   template <bool RELU>
-  __device__ static __forceinline__ uint32_t pack2(float a, float b) { return MmaBF16::pack2<RELU>(a, b); }
+  __device__ static __forceinline__ uint32_t pack2(float a, float b) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    const f32x2 ab = {a, b};
+    uint32_t r = __builtin_bit_cast(uint32_t, __builtin_convertvector(ab, bf16x2));   // one v_cvt_pk_bf16_f32
+    if constexpr (RELU) {
+      s16x2 q = __builtin_bit_cast(s16x2, r);
+      q = __builtin_elementwise_max(q, (s16x2)(0));
+      r = __builtin_bit_cast(uint32_t, q);
+    }
+    return r;
+  }
   __device__ static __forceinline__ void mma(f32x4a& acc, const AFrag& a, const Block& b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b.v, acc, 0, 0, 0);
   }
@@ -628,7 +616,19 @@ struct Mma16F16 {
   using AFrag = f16x8;
   struct Block { f16x8 v; };
   template <bool RELU>
-  __device__ static __forceinline__ uint32_t pack2(float a, float b) { return MmaF16::pack2<RELU>(a, b); }
+  __device__ static __forceinline__ uint32_t pack2(float a, float b) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    const f32x2 ab = {a, b};
+    uint32_t r = __builtin_bit_cast(uint32_t, __builtin_convertvector(ab, f16x2));
+    if constexpr (RELU) {
+      s16x2 q = __builtin_bit_cast(s16x2, r);
+      q = __builtin_elementwise_max(q, (s16x2)(0));
+      r = __builtin_bit_cast(uint32_t, q);
+    }
+    return r;
+  }
   __device__ static __forceinline__ void mma(f32x4a& acc, const AFrag& a, const Block& b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b.v, acc, 0, 0, 0);
   }
@@ -642,6 +642,27 @@ struct Mma16F16 {
   }
 };
 
+// LDS bytes of the weight ring of the 16x16x32 kernels (neither the operand type nor the wave count enters it)
+constexpr uint32_t kOb16RingBytes = Pipe<Mma16F16, 4, kOb16Depth, kOb16Ahead>::kLdsBytes;
+// Dynamic LDS of the radiance-field kernels on this engine (ns_nerf_mlp_ob16.hip, ns_nerf_mlp_x3.hip, ns_tangent.h; each names its
+// sizes once, in an alias):  [weight ring][bias image][embedding stash: WAVE_STASH bytes per wave][input staging: WAVE_STAGE bytes
+// per wave][compositing records, nsepi::Records: rec_bytes, 0 when the launch does not composite][tangent records: tan_bytes]
+template <int NWAVES, uint32_t WAVE_STASH, uint32_t WAVE_STAGE>
+struct FieldLds {
+  static constexpr uint32_t kWaveStash = WAVE_STASH, kWaveStage = WAVE_STAGE;
+  uint32_t ring = 0, bias = 0, stash = 0, stage = 0, rec = 0, tan = 0, end = 0;
+  __host__ __device__ constexpr FieldLds(int bias_floats, uint32_t rec_bytes, uint32_t tan_bytes = 0) {
+    LdsCarve c;
+    ring = c.take(kOb16RingBytes);
+    bias = c.take(static_cast<uint32_t>(bias_floats) * 4u);
+    stash = c.take(NWAVES * WAVE_STASH);
+    stage = c.take(NWAVES * WAVE_STAGE);
+    rec = c.take(rec_bytes);
+    tan = c.take(tan_bytes);
+    end = c.at;
+  }
+};
+
 // feature index (within a layer input of 32-feature K-blocks) held by element e of lane group g of K-block s
 __host__ __device__ constexpr int feature16(int s, int g, int e) { return 32 * s + 16 * (e >> 2) + 4 * g + (e & 3); }
 
@@ -649,6 +670,16 @@ __host__ __device__ constexpr int feature16(int s, int g, int e) { return 32 * s
 __host__ __device__ constexpr int ob16_chunks(int nsb, int nkb, int depth) { return ((nsb * nkb + depth - 1) / depth) * depth; }
 __host__ __device__ constexpr int ob16_layer_slabs(int nsb, int nkb, int depth) {
   return (ob16_chunks(nsb, nkb, depth) + kSlabChunks - 1) / kSlabChunks;
+}
+// slabs one pass of the 16x16x32 radiance-field program consumes (must equal ns_weights::n_slabs): layer 0, the trunk with
+// its skips, then (views + sigma, rgb) or output_linear.  cpk: stream chunks per K-block (2 for split operands: W_hi, W_lo)
+inline int ob16_field_slabs(int cpk, int W, int D, uint32_t skip_mask, int use_viewdirs) {
+  const int NSB = W / 16, NKB = W / 32, dp = kOb16Depth;
+  int n = ob16_layer_slabs(NSB, cpk * 2, dp);
+  for (int l = 1; l < D; ++l) n += ob16_layer_slabs(NSB, cpk * (((skip_mask >> (l - 1)) & 1u) ? NKB + 2 : NKB), dp);
+  if (use_viewdirs) n += ob16_layer_slabs(NSB / 2 + 1, cpk * (NKB + 1), dp) + ob16_layer_slabs(1, cpk * (NKB / 2), dp);
+  else n += ob16_layer_slabs(1, cpk * NKB, dp);
+  return n;
 }
 
 // dword J (0..1) of the finished sub-block SB of one tile goes to dword 2 (SB & 1) + J of K-block SB >> 1.

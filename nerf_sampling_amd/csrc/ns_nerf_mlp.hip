@@ -12,38 +12,23 @@ namespace {
 using namespace nsmlp;
 
 
-struct NerfArgs {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
-  int D;
-  uint32_t skip_mask;     // bit i: layer i + 1 sees cat[x, h]
-  int use_viewdirs, out_ch, x_stride;   // x_stride: row length of the pre-embedded input (90, or 63 without view directions)
-  // inputs: either pts [S,3] or (o,d [R,3], z [S]); or x [S,90] pre-embedded
-  const float* pts;
-  const float* o;
-  const float* d;
-  const float* z;
-  const float* viewdirs;  // [R,3]
-  const float* x90;
-  int64_t S;              // total samples R*N
-  int N;                  // samples per ray
-  float* raw;             // [S,4]
-};
+constexpr int kWaves = 4;   // one wave per SIMD
 
-template <class M, int NB, int NWAVES, int LAG, bool PRECISE_TRIG, bool EMBEDDED>
-__global__ void __launch_bounds__(NWAVES * 64)
-nerf_mlp_kernel(NerfArgs a) {
+// the exact-fp32 path: Trig<true>, the polynomial sine
+template <class M, int NB, bool EMBEDDED>
+__global__ void __launch_bounds__(kWaves * 64)
+nerf_mlp_kernel(FieldArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NWAVES = kWaves;
+  constexpr bool PRECISE_TRIG = true;
   using Block = typename M::Block;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5;
 
-  using PipeT = Pipe<M, NWAVES, LAG>;
-  // LDS image: [ring: PipeT::RING x 16 KiB][bias floats]
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using PipeT = Pipe<M, NWAVES>;
+  constexpr uint32_t kBiasAt = KMajorLds<PipeT>(0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
 
@@ -148,45 +133,29 @@ int nerf_program_slabs(int cpb, int NB, int D, uint32_t skip_mask, int use_viewd
   return n;
 }
 
-template <class M, int NB, int NWAVES, int LAG, bool PRECISE, bool EMB>
-int launch(const ns_weights* net, NerfArgs& a, hipStream_t stream) {
-  const size_t lds = static_cast<size_t>(Pipe<M, NWAVES, LAG>::kLdsBytes) + static_cast<size_t>(a.bias_floats) * 4;
-  auto kern = nerf_mlp_kernel<M, NB, NWAVES, LAG, PRECISE, EMB>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+template <class M, int NB, bool EMB>
+int launch(FieldArgs& a, hipStream_t stream) {
   const int64_t n_tiles = (a.S + 31) / 32;
-  const int64_t n_groups = (n_tiles + NWAVES - 1) / NWAVES;
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
-  const int grid = static_cast<int>(n_groups < cus ? n_groups : cus);
-  kern<<<grid, NWAVES * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  (void)net;
-  return NS_OK;
+  const int64_t n_groups = (n_tiles + kWaves - 1) / kWaves;
+  // (at the packer's limits, W <= 256 and D <= 32, the ring's 64 KiB and at most 33536 bytes of biases: never refused)
+  return ns::launch_persistent("ns_nerf_forward", nerf_mlp_kernel<M, NB, EMB>, a, kWaves * 64,
+                               KMajorLds<Pipe<M, kWaves>>(a.bias_floats).end, n_groups, stream);
 }
 
+// k-major streams are fp32 only: 16-bit and f16x3 handles are packed for, and run in, ns_nerf_mlp_ob16.hip
 template <bool EMB>
-int dispatch(const ns_weights* net, NerfArgs& a, hipStream_t stream) {
+int dispatch(const ns_weights* net, FieldArgs& a, hipStream_t stream) {
+  if (net->dtype != NS_DTYPE_F32) return NS_E_UNSUPPORTED;
   const int NB = net->width / 32;
-  const int cpb = net->dtype == NS_DTYPE_F32 ? 4 : 2;
-  if (nerf_program_slabs(cpb, NB, net->depth, net->skip_mask, net->use_viewdirs) != static_cast<int>(net->n_slabs)) {
-    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs,
-                  nerf_program_slabs(cpb, NB, net->depth, net->skip_mask, net->use_viewdirs));
+  const int slabs = nerf_program_slabs(MmaF32::CPB, NB, net->depth, net->skip_mask, net->use_viewdirs);
+  if (slabs != static_cast<int>(net->n_slabs)) {
+    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs, slabs);
     return NS_E_INVALID;
   }
-  switch (net->dtype) {
-    case NS_DTYPE_F32:
-      return NB == 8 ? launch<MmaF32, 8, 4, 0, true, EMB>(net, a, stream) : launch<MmaF32, 4, 4, 0, true, EMB>(net, a, stream);
-    default:   // 16-bit handles are packed for, and run in, ns_nerf_mlp_ob16.hip
-      break;
-  }
-  return NS_E_UNSUPPORTED;
+  return NB == 8 ? launch<MmaF32, 8, EMB>(a, stream) : launch<MmaF32, 4, EMB>(a, stream);
 }
 
 }  // namespace
-
-int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
-                         const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                         float* raw_dev, hipStream_t stream, const ns_composite_args* comp);
 
 extern "C" {
 
@@ -206,12 +175,8 @@ int ns_nerf_forward(const ns_weights* net, const float* pts_dev, const float* o_
   if (net->layout == 16)
     return ns_nerf_forward_ob16(net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, nullptr, R * N, N, raw_dev,
                                 ns::as_stream(stream), nullptr);
-  NerfArgs a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.D = net->depth; a.skip_mask = net->skip_mask; a.use_viewdirs = net->use_viewdirs; a.out_ch = net->out_ch;
-  a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = nullptr;
-  a.S = R * N; a.N = N; a.raw = raw_dev;
+  FieldArgs a{};
+  set_field_args(a, net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, nullptr, R * N, N, raw_dev);
   return dispatch<false>(net, a, ns::as_stream(stream));
 }
 
@@ -225,12 +190,8 @@ int ns_nerf_forward_embedded(const ns_weights* net, const float* x_dev, int64_t 
   if (net->layout == 16)
     return ns_nerf_forward_ob16(net, nullptr, nullptr, nullptr, nullptr, nullptr, x_dev, M, 1, raw_dev,
                                 ns::as_stream(stream), nullptr);
-  NerfArgs a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.D = net->depth; a.skip_mask = net->skip_mask; a.use_viewdirs = net->use_viewdirs; a.out_ch = net->out_ch;
-  a.x_stride = net->use_viewdirs ? 90 : 63;
-  a.x90 = x_dev; a.S = M; a.N = 1; a.raw = raw_dev;
+  FieldArgs a{};
+  set_field_args(a, net, nullptr, nullptr, nullptr, nullptr, nullptr, x_dev, M, 1, raw_dev);
   return dispatch<true>(net, a, ns::as_stream(stream));
 }
 

@@ -13,61 +13,8 @@
 // This file is compiled twice: as itself, and with -DNS_OB16_TU_T5 as a second translation unit that holds only the
 // five-tile production kernels (the two units build in parallel; each is minutes of register allocation).
 namespace nsob16 {
-struct Nerf16Args {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
-  int D;
-  uint32_t skip_mask;     // bit i: layer i + 1 sees cat[x, h]
-  int use_viewdirs, out_ch, x_stride;   // x_stride: row length of the pre-embedded input (90, or 63 without view directions)
-  // inputs: either pts [S,3] or (o,d [R,3], z [S]); or x [S,90] pre-embedded
-  const float* pts;
-  const float* o;
-  const float* d;
-  const float* z;
-  const float* viewdirs;
-  const float* x90;
-  int64_t S;
-  int N;
-  float* raw;
-  // In-kernel compositing (the DepthNet branch of render_rays_test as ONE kernel, nerf_utils.py:836-865): comp != 0 runs
-  // raw2outputs (sampling_trainer.py:153-230) on the wave scan of ns_composite_ray.h in the epilogue -- raw then never
-  // leaves the CU (raw may be NULL).  comp == 1: depths from the array z [S];  comp == 2: sample_points_around_mean
-  // ("uniform", utils.py:231-241) evaluated in-kernel from the DepthNet depth mean [R] -- no z array exists.
-  // N is a power of two <= 64 (whole rays per 64-sample chunk) or a multiple of 64 up to 512 (whole chunks per ray).
-  int comp;
-  int n_shift;             // log2 N when N is a power of two, else -1
-  const float* mean;
-  float std_, lin_step;    // the grid linspace(-std, std, N - 1) and its step (correctly rounded on the host)
-  int white_bkgd;
-  float* rgb; int64_t rgb_stride;
-  float* disp; int64_t disp_stride;
-  float* weights;          // [S] or NULL
-  float* z_out;            // [S] or NULL (comp == 2: the depths the kernel placed)
-  float* pts_out;          // [S,3] or NULL
-  const float* sig_last;   // NULL, or [R,4]: element 3 of row r replaces sigma of ray r's last sample (the guard pass)
-  // rays longer than a 64-sample chunk (N = 64 m, m = m_chunks >= 2; 0 otherwise): a workgroup then walks sg_groups CONSECUTIVE
-  // groups -- lcm(group samples, N) samples, whole rays -- before it jumps, so that a ray's chunks meet in one workgroup and
-  // the transmittance / sums of the ray that is open at a group boundary carry over in LDS
-  int m_chunks, sg_groups;
-  // the selective guard: a ray whose own sigma of the last sample is within fix_thr of zero -- where the step
-  // alpha = step(sigma) could flip under the 16-bit rounding -- leaves a record at slot atomicAdd(fix_count) of fix_rec.  Rays of
-  // one chunk: 16 floats {tree sums r g b depth acc, T, raw rgb of the last sample, its z and dist, ray index lo / hi}
-  // (ns_fix_last_sample re-evaluates sigma through the fp32-grade handle and repeats the last addition).  Rays of several chunks:
-  // nsepi::kFixLongFloats floats, the operands of the last chunk's additions as well (ns_comp_epilogue.h, ns_fix_last_sample_long)
-  float fix_thr;
-  uint32_t* fix_count;
-  float* fix_rec;
-  // the max-weight sample of every ray (nerf_utils.py:813-819), all three or none: max_z, max_w [R] and max_rgb [R,3] get the z,
-  // the weight and sigmoid(raw rgb) of the sample argmax(weights) picks (ns_comp_epilogue.h)
-  float* max_z;
-  float* max_w;
-  float* max_rgb;
-  // the per-ray expected depth and opacity sums (ns_composite_args::depth_dev / acc_dev): [R] each, or NULL
-  float* depth;
-  float* acc;
-};
+// the field inputs, and what in-kernel placement and compositing takes (ns_comp_epilogue.h)
+struct Nerf16Args : nsmlp::FieldArgs, nsepi::CompFields {};
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
 }  // namespace nsob16
@@ -88,6 +35,11 @@ using namespace nsmlp;
 constexpr int kT = NS_NERF16_T;          // 16-sample tiles per wave
 constexpr int kWaves = NS_NERF16_WAVES;  // 4: one wave per SIMD, ~256 AGPRs of activations + accumulators per wave
                                          // (8 waves x T = 2, two per SIMD in 256 registers each: measured slower)
+// dynamic LDS (FieldLds): embedding stash per wave T x 3 blocks x 1 KiB, input staging per wave 11 rows of 16 T floats, and when
+// the launch composites: raw float4 per sample of the group | {z, dist} float2 per sample, two group parities | sigma of a ray's
+// last sample from the guard pass, one float per ray of the group, two parities (nsepi::Records)
+template <int T>
+using Ob16Lds = FieldLds<kWaves, T * 3 * 1024, 11 * (T * 64)>;
 
 }  // namespace
 #ifndef NS_OB16_ASM_INC
@@ -175,22 +127,21 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int T = TT, NWAVES = kWaves, NSB = 2 * NKB;   // 16-row output sub-blocks of a hidden layer
   using Block = typename M::Block;
-  using PipeT = Pipe<M, NWAVES, 0, kOb16Depth, kOb16Ahead>;
+  using PipeT = Pipe<M, NWAVES, kOb16Depth, kOb16Ahead>;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
 
-  // LDS: [weight ring][bias image][embedding stash: per wave T x 3 blocks x 1 KiB][input staging: per wave 11 rows of 16 T floats]
-  //      [compositing records (a.comp): raw float4 per sample of the group | {z, dist} float2 per sample, two group parities
-  //       | sigma of a ray's last sample from the guard pass, one float per ray of the group, two parities]
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using Lds = Ob16Lds<T>;
+  constexpr uint32_t kBiasAt = Lds(0, 0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
 
-  typedef typename M::AFrag __attribute__((address_space(3))) * StashPtr;
   const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NS_LDS_PTR(smem)));
-  const uint32_t stash_region = lds0 + PipeT::kLdsBytes + ((static_cast<uint32_t>(a.bias_floats) * 4u + 15u) & ~15u);
-  const uint32_t stash_base = stash_region + static_cast<uint32_t>(wave) * (T * 3 * 1024) + static_cast<uint32_t>(lane) * 16u;
+  const Lds lm(a.bias_floats, 0);   // (the records, when the launch asked for them, are the last region: no offset depends on them)
+  typedef typename M::AFrag __attribute__((address_space(3))) * StashPtr;
+  const uint32_t stash_base = lds0 + lm.stash + static_cast<uint32_t>(wave) * Lds::kWaveStash + static_cast<uint32_t>(lane) * 16u;
   auto stash_at = [&](int t, int b) -> StashPtr {
     return reinterpret_cast<StashPtr>(static_cast<uintptr_t>(stash_base + (t * 3 + b) * 1024));
   };
@@ -198,9 +149,10 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
   auto stash_get = [&](int t, int b) -> Block { Block v; v.v = *stash_at(t, b); return v; };
   // staging: value slot k (0..10) of sample j (0 .. 16 T - 1) of this wave's group at stage_base + k * kStageRow + j * 4
   constexpr uint32_t kStageRow = T * 64, kStageRows = 11;
-  const uint32_t stage_base = stash_region + NWAVES * (T * 3 * 1024) + static_cast<uint32_t>(wave) * (kStageRows * kStageRow);
+  static_assert(kStageRows * kStageRow == Lds::kWaveStage, "a wave's staging rows");
+  const uint32_t stage_base = lds0 + lm.stage + static_cast<uint32_t>(wave) * Lds::kWaveStage;
   // compositing records (only allocated when a.comp): ns_comp_epilogue.h
-  const nsepi::Records<T, NWAVES> rec{stash_region + NWAVES * (T * 3 * 1024) + NWAVES * (kStageRows * kStageRow)};
+  const nsepi::Records<T, NWAVES> rec{lds0 + lm.rec};
   using nsepi::v4f;
 
   PipeT ring;
@@ -472,37 +424,14 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
   ring.finish();
 }
 
-int ob16_program_slabs(int W, int D, uint32_t skip_mask, int use_viewdirs) {
-  const int NSB = W / 16, NKB = W / 32, dp = kOb16Depth;
-  int n = ob16_layer_slabs(NSB, 2, dp);
-  for (int l = 1; l < D; ++l) n += ob16_layer_slabs(NSB, ((skip_mask >> (l - 1)) & 1u) ? NKB + 2 : NKB, dp);
-  if (use_viewdirs) n += ob16_layer_slabs(NSB / 2 + 1, NKB + 1, dp) + ob16_layer_slabs(1, NKB / 2, dp);
-  else n += ob16_layer_slabs(1, NKB, dp);
-  return n;
-}
-
 template <class M, int NKB, bool EMB, bool PROD = false, int TT = kT>
 int launch(Nerf16Args& a, hipStream_t stream) {
-  const size_t lds = static_cast<size_t>(Pipe<M, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
-                     ((static_cast<size_t>(a.bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * TT * 3 * 1024 +
-                     static_cast<size_t>(kWaves) * 11 * (TT * 64) +      // ring | bias | embedding stash | input staging
-                     (a.comp && !EMB ? static_cast<size_t>(nsepi::Records<TT, kWaves>::kBytes) : 0);   // | compositing records
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_nerf_forward: %zu bytes of LDS needed (too deep a network for the resident bias image)", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  auto kern = nerf_mlp_ob16_kernel<M, NKB, EMB, PROD, TT>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t n_tiles = (a.S + 15) / 16;
   const int64_t n_groups = (n_tiles + kWaves * TT - 1) / (kWaves * TT);
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
   a.sg_groups = nsepi::run_groups(kWaves * TT * 16, a.m_chunks, a.N);
   const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
-  const int grid = static_cast<int>(n_runs < cus ? n_runs : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  const Ob16Lds<TT> lm(a.bias_floats, a.comp && !EMB ? nsepi::Records<TT, kWaves>::kBytes : 0);
+  return ns::launch_persistent("ns_nerf_forward", nerf_mlp_ob16_kernel<M, NKB, EMB, PROD, TT>, a, kWaves * 64, lm.end, n_runs, stream);
 }
 
 #ifndef NS_OB16_TU_T5
@@ -537,11 +466,7 @@ int nsob16::launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t 
   return embedded ? launch<Mma16F16, 8, true, true, 5>(a, stream) : launch<Mma16F16, 8, false, true, 5>(a, stream);
 }
 #else
-int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
-                       const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
-
-// which (network, sample count) pairs the kernel composites itself (see Nerf16Args::comp): the 16-bit fields here, the split-fp16
+// which (network, sample count) pairs the kernel composites itself (see nsepi::CompFields::comp): the 16-bit fields here, the split-fp16
 // (f16x3) fields in ns_nerf_mlp_x3.hip
 bool ns_nerf_can_composite(const ns_weights* net, int N) {
   return net && net->kind == NS_KIND_NERF && net->layout == 16 &&
@@ -567,18 +492,13 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
   }
   if (net->dtype == NS_DTYPE_F16X3)   // split fp16 operands: ns_nerf_mlp_x3.hip
     return ns_nerf_forward_x3(net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, x90_dev, S, N, raw_dev, stream, nullptr, comp);
-  if (ob16_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs) != static_cast<int>(net->n_slabs)) {
-    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs,
-                  ob16_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs));
+  const int slabs = ob16_field_slabs(1, net->width, net->depth, net->skip_mask, net->use_viewdirs);
+  if (slabs != static_cast<int>(net->n_slabs)) {
+    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs, slabs);
     return NS_E_INVALID;
   }
   Nerf16Args a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.D = net->depth; a.skip_mask = net->skip_mask; a.use_viewdirs = net->use_viewdirs; a.out_ch = net->out_ch;
-  a.x_stride = net->use_viewdirs ? 90 : 63;
-  a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = x90_dev;
-  a.S = S; a.N = N; a.raw = raw_dev;
+  set_field_args(a, net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, x90_dev, S, N, raw_dev);
   if (comp) {
     nsepi::set_comp_args(a, comp, N);
     if (comp->fix_rec_dev) {

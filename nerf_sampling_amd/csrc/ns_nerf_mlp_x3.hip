@@ -54,31 +54,18 @@ __device__ __forceinline__ void hidden_layer_asm_x3(PipeT& ring, const float* bi
   });
 }
 
-struct NerfX3Args {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
-  int D;
-  uint32_t skip_mask;     // bit i: layer i + 1 sees cat[x, h]
-  int use_viewdirs, out_ch, x_stride;   // x_stride: row length of the pre-embedded input (90, or 63 without view directions)
-  // inputs: either pts [S,3] or (o,d [R,3], z [S]); or x [S,90] pre-embedded
-  const float* pts;
-  const float* o;
-  const float* d;
-  const float* z;
-  const float* viewdirs;
-  const float* x90;
-  int64_t S;
-  int N;
-  float* raw;
+struct NerfX3Args : FieldArgs {
   const uint32_t* count_dev;   // NULL, or the number of samples to evaluate, read by the kernel (<= S: the selective guard pass
                                // launches for its capacity and the device knows how many rays were flagged)
 };
-// ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): nsepi::CompFields, the fields
-// of Nerf16Args::comp .. acc (ns_nerf_mlp_ob16.hip), the same meaning.  The host leaves the selective guard's fields NULL:
-// that form serves 16-bit fields only.
+// ... and with in-kernel placement and compositing (the one-kernel renderer on an f16x3 field): nsepi::CompFields.  The host
+// leaves the selective guard's fields NULL: that form serves 16-bit fields only.
 struct NerfX3CompArgs : NerfX3Args, nsepi::CompFields {};
+
+// dynamic LDS (FieldLds): embedding stash per wave T x 3 blocks x 2 KiB (hi, lo), input staging per wave 10 (COMP: 11) x 256 B,
+// and for COMP the compositing records (nsepi::Records)
+template <bool COMP>
+using X3Lds = FieldLds<kWaves, kT * 3 * 2048, (COMP ? 11 : 10) * 256>;
 
 // PROD: the production network (8 x 256, skips = [4], view directions) as straight-line code over the generated layer
 // statements, as in ns_nerf_mlp_ob16.hip.  COMP (Args = NerfX3CompArgs, rays (o, d) in): the samples are placed and composited
@@ -90,7 +77,7 @@ __device__ __forceinline__ void nerf_x3_body(const Args& a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int T = kT, NWAVES = kWaves, NSB = 2 * NKB;   // 16-row output sub-blocks of a hidden layer
   using Block = typename M::Block;
-  using PipeT = Pipe<M, NWAVES, 0, kOb16Depth, kOb16Ahead>;
+  using PipeT = Pipe<M, NWAVES, kOb16Depth, kOb16Ahead>;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
@@ -101,26 +88,25 @@ __device__ __forceinline__ void nerf_x3_body(const Args& a) {
   }
   if (S_ <= 0) return;
 
-  // LDS: [weight ring][bias image][embedding stash: per wave T x 3 blocks x 2 KiB][input staging: per wave 10 (COMP: 11) x 256 B]
-  //      [COMP: compositing records, nsepi::Records]
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using Lds = X3Lds<COMP>;
+  constexpr uint32_t kBiasAt = Lds(0, 0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
 
-  typedef typename M::AFrag __attribute__((address_space(3))) * StashPtr;
   const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NS_LDS_PTR(smem)));
-  const uint32_t stash_region = lds0 + PipeT::kLdsBytes + ((static_cast<uint32_t>(a.bias_floats) * 4u + 15u) & ~15u);
+  const Lds lm(a.bias_floats, 0);   // (the records are the last region: no offset depends on their size)
+  typedef typename M::AFrag __attribute__((address_space(3))) * StashPtr;
   // per wave T x 3 blocks x (hi 1 KiB, lo 1 KiB)
-  const uint32_t stash_base = stash_region + static_cast<uint32_t>(wave) * (T * 3 * 2048) + static_cast<uint32_t>(lane) * 16u;
+  const uint32_t stash_base = lds0 + lm.stash + static_cast<uint32_t>(wave) * Lds::kWaveStash + static_cast<uint32_t>(lane) * 16u;
   auto stash_at = [&](int t, int b, int half) -> StashPtr {
     return reinterpret_cast<StashPtr>(static_cast<uintptr_t>(stash_base + ((t * 3 + b) * 2 + half) * 1024));
   };
   auto stash_put = [&](int t, int b, const Block& v) { *stash_at(t, b, 0) = v.hi; *stash_at(t, b, 1) = v.lo; };
   auto stash_get = [&](int t, int b) -> Block { Block v; v.hi = *stash_at(t, b, 0); v.lo = *stash_at(t, b, 1); return v; };
   // staging: value slot k (0..9; COMP: 0..10) of sample j (0..63) of this wave's group at stage_base + k * 256 + j * 4
-  constexpr uint32_t kStageRows = COMP ? 11 : 10;
-  const uint32_t stage_base = stash_region + NWAVES * (T * 3 * 2048) + static_cast<uint32_t>(wave) * (kStageRows * 256);
-  const nsepi::Records<T, NWAVES> rec{stash_region + NWAVES * (T * 3 * 2048) + NWAVES * (kStageRows * 256)};
+  const uint32_t stage_base = lds0 + lm.stage + static_cast<uint32_t>(wave) * Lds::kWaveStage;
+  const nsepi::Records<T, NWAVES> rec{lds0 + lm.rec};
   (void)rec;
 
   PipeT ring;
@@ -174,7 +160,7 @@ if (a.use_viewdirs) {
   };
 
   // group order of a workgroup: a grid stride; COMP: runs of sg consecutive groups (rays of several chunks meet in one workgroup,
-  // see Nerf16Args::m_chunks), then a jump of gridDim.x such runs
+  // see nsepi::CompFields::m_chunks), then a jump of gridDim.x such runs
   int sg = 1;
   if constexpr (COMP) sg = a.sg_groups > 1 ? a.sg_groups : 1;
   auto group_after = [&](int64_t grp_, int gi_) -> int64_t {
@@ -366,59 +352,23 @@ nerf_mlp_x3_comp_kernel(NerfX3CompArgs a) {
   nerf_x3_body<NKB, false, PROD, true>(a);
 }
 
-int x3_program_slabs(int W, int D, uint32_t skip_mask, int use_viewdirs) {   // two stream chunks (W_hi, W_lo) per K-block
-  const int NSB = W / 16, NKB = W / 32, dp = kOb16Depth;
-  int n = ob16_layer_slabs(NSB, 2 * 2, dp);
-  for (int l = 1; l < D; ++l) n += ob16_layer_slabs(NSB, 2 * (((skip_mask >> (l - 1)) & 1u) ? NKB + 2 : NKB), dp);
-  if (use_viewdirs) n += ob16_layer_slabs(NSB / 2 + 1, 2 * (NKB + 1), dp) + ob16_layer_slabs(1, 2 * (NKB / 2), dp);
-  else n += ob16_layer_slabs(1, 2 * NKB, dp);
-  return n;
-}
-
 template <int NKB, bool EMB, bool PROD = false>
 int launch(NerfX3Args& a, hipStream_t stream) {
-  using M = Mma16F16x3;
-  const size_t lds = static_cast<size_t>(Pipe<M, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
-                     ((static_cast<size_t>(a.bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * kT * 3 * 2048 +
-                     static_cast<size_t>(kWaves) * 10 * 256;   // ring | bias | embedding stash (hi, lo) | input staging
-  auto kern = nerf_mlp_x3_kernel<NKB, EMB, PROD>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t n_tiles = (a.S + 15) / 16;
   const int64_t n_groups = (n_tiles + kWaves * kT - 1) / (kWaves * kT);
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
-  const int grid = static_cast<int>(n_groups < cus ? n_groups : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
-}
-
-// dynamic LDS of the compositing form: ring | bias | embedding stash (hi, lo) | input staging (11 slots) | compositing records
-size_t comp_lds_bytes(int bias_floats) {
-  return static_cast<size_t>(Pipe<Mma16F16x3, kWaves, 0, kOb16Depth, kOb16Ahead>::kLdsBytes) +
-         ((static_cast<size_t>(bias_floats) * 4 + 15) & ~size_t(15)) + static_cast<size_t>(kWaves) * kT * 3 * 2048 +
-         static_cast<size_t>(kWaves) * 11 * 256 + nsepi::Records<kT, kWaves>::kBytes;
+  // (at the packer's limits, W <= 256 and D <= 32, 33408 bytes of biases: 158336 bytes in all, never refused)
+  return ns::launch_persistent("ns_nerf_forward", nerf_mlp_x3_kernel<NKB, EMB, PROD>, a, kWaves * 64,
+                               X3Lds<false>(a.bias_floats, 0).end, n_groups, stream);
 }
 
 template <int NKB, bool PROD>
 int launch_comp(NerfX3CompArgs& a, hipStream_t stream) {
-  const size_t lds = comp_lds_bytes(a.bias_floats);
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_nerf_forward: %zu bytes of LDS needed (too deep a network for the resident bias image)", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  auto kern = nerf_mlp_x3_comp_kernel<NKB, PROD>;
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t n_tiles = (a.S + 15) / 16;
   const int64_t n_groups = (n_tiles + kWaves * kT - 1) / (kWaves * kT);
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
   a.sg_groups = nsepi::run_groups(kWaves * kT * 16, a.m_chunks, a.N);
   const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
-  const int grid = static_cast<int>(n_runs < cus ? n_runs : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  return ns::launch_persistent("ns_nerf_forward", nerf_mlp_x3_comp_kernel<NKB, PROD>, a, kWaves * 64,
+                               X3Lds<true>(a.bias_floats, nsepi::Records<kT, kWaves>::kBytes).end, n_runs, stream);
 }
 
 }  // namespace
@@ -428,18 +378,14 @@ int launch_comp(NerfX3CompArgs& a, hipStream_t stream) {
 int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
                        const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
                        float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp) {
-  if (x3_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs) != static_cast<int>(net->n_slabs)) {
-    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs,
-                  x3_program_slabs(net->width, net->depth, net->skip_mask, net->use_viewdirs));
+  const int slabs = ob16_field_slabs(2, net->width, net->depth, net->skip_mask, net->use_viewdirs);   // (W_hi, W_lo) per K-block
+  if (slabs != static_cast<int>(net->n_slabs)) {
+    ns::set_error("ns_nerf_forward: packed stream has %u slabs, kernel program expects %d", net->n_slabs, slabs);
     return NS_E_INVALID;
   }
   NerfX3Args a{};
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
-  a.D = net->depth; a.skip_mask = net->skip_mask; a.use_viewdirs = net->use_viewdirs; a.out_ch = net->out_ch;
-  a.x_stride = net->use_viewdirs ? 90 : 63;
-  a.pts = pts_dev; a.o = o_dev; a.d = d_dev; a.z = z_dev; a.viewdirs = viewdirs_dev; a.x90 = x90_dev;
-  a.S = S; a.N = N; a.raw = raw_dev; a.count_dev = count_dev;
+  set_field_args(a, net, pts_dev, o_dev, d_dev, z_dev, viewdirs_dev, x90_dev, S, N, raw_dev);
+  a.count_dev = count_dev;
   const bool emb = x90_dev != nullptr, wide = net->width == 256;
   const bool prod = wide && net->depth == 8 && net->skip_mask == (1u << 4) && net->use_viewdirs && !ns::debug_flags().generic_kernels;
   if (comp) {

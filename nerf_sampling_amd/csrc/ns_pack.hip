@@ -301,10 +301,6 @@ int finish(Builder& b, ns_weights* w) {
 
 }  // namespace
 
-namespace ns {
-// build the host images only (used by the CPU-side layout test through ns_pack_*_host)
-}
-
 extern "C" {
 
 int ns_pack_nerf(int D, int W, int skip, const float* const* w, const float* const* b, int dtype,

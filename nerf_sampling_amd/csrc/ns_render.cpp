@@ -3,19 +3,6 @@
 #include "ns_common.h"
 #include "ns_weights.h"
 
-int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
-                         const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                         float* raw_dev, hipStream_t stream, const ns_composite_args* comp);
-int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
-                       const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
-                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
-int ns_nerf_forward_x3_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev, int64_t R,
-                               int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth, float* d_acc,
-                               hipStream_t stream);
-int ns_nerf_forward_ob16_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev,
-                                 int64_t R, int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth,
-                                 float* d_acc, hipStream_t stream);
-
 namespace {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~static_cast<int64_t>(255); }
@@ -378,7 +365,7 @@ int ns_render_rays_hierarchical(const ns_hier_args* a, void* stream) {
   rc = ns_coarse_z_scalar(a->near_, a->far_, R, Nc, a->lindisp, a->t_rand_dev, l.z_c, stream);
   if (rc != NS_OK) return rc;
   if ((rc = record(a->ev_coarse_begin, stream)) != NS_OK) return rc;
-  // A bf16 / f16 / f16x3 field composites in its own epilogue (Nerf16Args::comp == 1: depths from the z array): raw [R,N,4] -- 16 bytes
+  // A bf16 / f16 / f16x3 field composites in its own epilogue (nsepi::CompFields::comp == 1: depths from the z array): raw [R,N,4] -- 16 bytes
   // per sample written and read back, 2.6 GB per 800 x 800 frame at 64 + 192 samples -- then never exists.  The coarse
   // pass only yields its weights (its colour goes to a scratch corner of the unused raw_c block).
   const bool chain = ns::debug_flags().hier_chain != 0;

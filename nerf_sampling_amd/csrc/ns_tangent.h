@@ -123,16 +123,12 @@ struct TanOps<Mma16F16> {
 template <class M>
 constexpr int kGroupSamples = kWaves * TanOps<M>::kTiles * 16;
 template <class M>
-using PipeOf = Pipe<M, kWaves, 0, kOb16Depth, kOb16Ahead>;
+using PipeOf = Pipe<M, kWaves, kOb16Depth, kOb16Ahead>;
 template <int GS>
 using RecOf = nsepi::Records<GS / (kWaves * 16), kWaves>;
 
 // the compositing fields place_wave / composite_group read, the network and the rays, the tangent outputs
-struct TanArgs : nsepi::CompFields {
-  const char* stream;
-  const float* bias;
-  uint32_t n_slabs;
-  int bias_floats;
+struct TanArgs : nsepi::CompFields, StreamArgs {
   int D;
   uint32_t skip_mask;
   const float* o;
@@ -279,7 +275,7 @@ __device__ __forceinline__ void convert_last_tan(OutT& out, const f32x4a (&last)
   });
 }
 
-// LDS records of the tangent pass beyond nsepi::Records, from byte address `base`, for a group of GS samples:
+// LDS records of the tangent pass beyond nsepi::Records, from byte address `base` (at TanLds::tan), for a group of GS samples:
 //   float4 per sample of the group {d raw r, g, b, d sigma} | float2 per sample {dz, d dist}, two parities | the walk state of
 //   the ray that is open at a group's end (rays of several chunks), kState floats
 template <int GS>
@@ -297,6 +293,15 @@ struct TanRecords {
     return reinterpret_cast<nsepi::CsigPtr>(static_cast<uintptr_t>(base + GS * 32u + static_cast<uint32_t>(k) * 4u));
   }
 };
+
+// dynamic LDS (FieldLds): embedding stash per wave 2 kTiles register tiles x 3 blocks of kStashBytes, input staging per wave 11
+// rows of 16 kTiles floats (a row is one LDS-DMA of the 64 lanes: 256 bytes), nsepi::Records, TanRecords
+template <class M>
+using TanLds = FieldLds<kWaves, 2 * TanOps<M>::kTiles * 3 * TanOps<M>::kStashBytes, 11 * 256>;
+template <class M>
+__host__ __device__ constexpr TanLds<M> tan_lds(int bias_floats) {
+  return TanLds<M>(bias_floats, RecOf<kGroupSamples<M>>::kBytes, TanRecords<kGroupSamples<M>>::kBytes);
+}
 
 // a ray's forward quantities and their tangents along the walk
 struct Walk {
@@ -449,24 +454,23 @@ __device__ __forceinline__ void tangent_body(const TanArgs& a) {
   const int64_t S_ = a.S;
   if (S_ <= 0) return;
 
-  // LDS: [weight ring][bias image][embedding stash: per wave kRT register tiles x 3 blocks of kStashBytes][input staging: per
-  //      wave 11 rows of 16 kTiles floats][nsepi::Records][TanRecords]: tan_lds_bytes
-  float* bias_lds = reinterpret_cast<float*>(smem + PipeT::kLdsBytes);
+  using Lds = TanLds<M>;
+  constexpr uint32_t kBiasAt = tan_lds<M>(0).bias;
+  float* bias_lds = reinterpret_cast<float*>(smem + kBiasAt);
   for (int i = threadIdx.x; i < a.bias_floats; i += NWAVES * 64) bias_lds[i] = a.bias[i];
   __syncthreads();
 
-  constexpr uint32_t kWaveStash = kRT * 3 * Ops::kStashBytes;
   const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(NS_LDS_PTR(smem)));
-  const uint32_t stash_region = lds0 + PipeT::kLdsBytes + ((static_cast<uint32_t>(a.bias_floats) * 4u + 15u) & ~15u);
-  const uint32_t stash_base = stash_region + static_cast<uint32_t>(wave) * kWaveStash + static_cast<uint32_t>(lane) * 16u;
+  const Lds lm = tan_lds<M>(a.bias_floats);
+  const uint32_t stash_base = lds0 + lm.stash + static_cast<uint32_t>(wave) * Lds::kWaveStash + static_cast<uint32_t>(lane) * 16u;
   auto stash_put = [&](int t, int b, const Block& v) { Ops::stash_put(stash_base + (t * 3 + b) * Ops::kStashBytes, v); };
   auto stash_get = [&](int t, int b) -> Block { return Ops::stash_get(stash_base + (t * 3 + b) * Ops::kStashBytes); };
   // staging: value slot k (0..10) of sample j (0 .. 16 kTiles - 1) of this wave's group at stage_base + k * kStageRow + j * 4 (a
   // row is one LDS-DMA of the 64 lanes: 4 bytes each)
-  constexpr uint32_t kStageRow = 256, kStageRows = 11;
-  const uint32_t stage_base = stash_region + NWAVES * kWaveStash + static_cast<uint32_t>(wave) * (kStageRows * kStageRow);
-  const Rec rec{stash_region + NWAVES * kWaveStash + NWAVES * (kStageRows * kStageRow)};
-  const TanRecords<kGS> tr{rec.base + Rec::kBytes};
+  constexpr uint32_t kStageRow = 256;
+  const uint32_t stage_base = lds0 + lm.stage + static_cast<uint32_t>(wave) * Lds::kWaveStage;
+  const Rec rec{lds0 + lm.rec};
+  const TanRecords<kGS> tr{lds0 + lm.tan};
 
   PipeT ring;
   ring.init(a.stream, smem, a.n_slabs, wave, lane);
@@ -648,37 +652,18 @@ __device__ __forceinline__ void tangent_body(const TanArgs& a) {
   ring.finish();
 }
 
-// slabs of the kernel's layer program, with view directions (the forward's program on the same stream)
-template <class M>
-inline int tan_program_slabs(int W, int D, uint32_t skip_mask) {
-  constexpr int parts = TanOps<M>::kParts;
-  const int NSB = W / 16, NKB = W / 32, dp = kOb16Depth;
-  int n = ob16_layer_slabs(NSB, parts * 2, dp);
-  for (int l = 1; l < D; ++l) n += ob16_layer_slabs(NSB, parts * (((skip_mask >> (l - 1)) & 1u) ? NKB + 2 : NKB), dp);
-  return n + ob16_layer_slabs(NSB / 2 + 1, parts * (NKB + 1), dp) + ob16_layer_slabs(1, parts * (NKB / 2), dp);
-}
-
-template <class M>
-inline size_t tan_lds_bytes(int bias_floats) {
-  constexpr int GS = kGroupSamples<M>;
-  return static_cast<size_t>(PipeOf<M>::kLdsBytes) + ((static_cast<size_t>(bias_floats) * 4 + 15) & ~size_t(15)) +
-         static_cast<size_t>(kWaves) * 2 * TanOps<M>::kTiles * 3 * TanOps<M>::kStashBytes + static_cast<size_t>(kWaves) * 11 * 256 +
-         RecOf<GS>::kBytes + TanRecords<GS>::kBytes;
-}
-
 // The host side of an entry point: the arguments of a launch from what ns_render_rays_fused_tangent (ns_render.cpp) passes, which
 // has checked the handle (ns_render_tangent_supported) and the outputs: rays (o, d, view), the DepthNet depth of every ray in
 // comp->mean_dev, the forward's per-ray outputs in comp
 template <class M>
 inline int fill_tan_args(TanArgs& a, const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev,
                          int64_t R, int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth, float* d_acc) {
-  const int slabs = tan_program_slabs<M>(net->width, net->depth, net->skip_mask);
+  const int slabs = ob16_field_slabs(TanOps<M>::kParts, net->width, net->depth, net->skip_mask, 1);   // (the forward's program)
   if (slabs != static_cast<int>(net->n_slabs)) {
     ns::set_error("ns_render_rays_fused_tangent: packed stream has %u slabs, kernel program expects %d", net->n_slabs, slabs);
     return NS_E_INVALID;
   }
-  a.stream = static_cast<const char*>(net->stream_dev);
-  a.bias = net->bias_dev; a.n_slabs = net->n_slabs; a.bias_floats = net->bias_floats;
+  set_stream_args(a, net);
   a.D = net->depth; a.skip_mask = net->skip_mask;
   a.o = o_dev; a.d = d_dev; a.viewdirs = viewdirs_dev;
   a.S = R * N; a.N = N;
@@ -691,21 +676,10 @@ inline int fill_tan_args(TanArgs& a, const ns_weights* net, const float* o_dev, 
 template <class M>
 inline int launch_tan(void (*kern)(TanArgs), TanArgs& a, hipStream_t stream) {
   constexpr int GS = kGroupSamples<M>;
-  const size_t lds = tan_lds_bytes<M>(a.bias_floats);
-  if (lds > 160 * 1024) {
-    ns::set_error("ns_render_rays_fused_tangent: %zu bytes of LDS needed (too deep a network for the resident bias image)", lds);
-    return NS_E_UNSUPPORTED;
-  }
-  NS_HIP(ns::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t n_groups = (a.S + GS - 1) / GS;
-  int cus = ns::cu_count();
-  if (cus <= 0) cus = 256;
   a.sg_groups = nsepi::run_groups(GS, a.m_chunks, a.N);
   const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
-  const int grid = static_cast<int>(n_runs < cus ? n_runs : cus);
-  kern<<<grid, kWaves * 64, lds, stream>>>(a);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
+  return ns::launch_persistent("ns_render_rays_fused_tangent", kern, a, kWaves * 64, tan_lds<M>(a.bias_floats).end, n_runs, stream);
 }
 
 }  // namespace nstan

@@ -1,5 +1,7 @@
-// Internal layout of the opaque ns_weights handle (host side).
+// Internal layout of the opaque ns_weights handle (host side) and the entry points the library's files call in one another.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstddef>
 #include <cstdint>
 
@@ -36,7 +38,7 @@ struct ns_composite_args {
   const float* sigma_last_dev;   // NULL, or [R,4] raw of every ray's LAST sample from the guard pass: its sigma (element 3)
                                  // replaces the kernel's own for that sample (ns_render_args::nerf_guard)
   // the selective guard (ns_render_args::guard_threshold > 0): records of the rays whose own |sigma_last| < fix_thr (16 floats
-  // each for N <= 64, NS_FIX_LONG_FLOATS for rays of several chunks: Nerf16Args::fix_rec), counted in *fix_count_dev (zeroed by
+  // each for N <= 64, NS_FIX_LONG_FLOATS for rays of several chunks: nsepi::CompFields::fix_rec), counted in *fix_count_dev (zeroed by
   // the caller)
   float fix_thr;
   uint32_t* fix_count_dev;
@@ -67,3 +69,23 @@ int ns_fix_last_sample_long(const float* rec_dev, const uint32_t* count_dev, int
 int ns_place_last_sample(const float* mean_dev, int64_t R, int N, float std_, float* z_last_dev, void* stream);
 int ns_patch_sigma_last(float* raw_dev, const float* raw_last_dev, int64_t R, int N, void* stream);
 bool ns_nerf_can_composite(const ns_weights* net, int N);
+
+// The layout-16 kernels behind the public forwards and the one-call renderers (arguments validated by the callers).
+// ns_nerf_forward / ns_nerf_forward_embedded on a layout-16 handle; comp: composite (and place) in the kernel (ns_nerf_mlp_ob16.hip)
+int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
+                         const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
+                         float* raw_dev, hipStream_t stream, const ns_composite_args* comp);
+// ... on an NS_DTYPE_F16X3 handle; count_dev: the selective guard's fix-up (ns_nerf_mlp_x3.hip)
+int ns_nerf_forward_x3(const ns_weights* net, const float* pts_dev, const float* o_dev, const float* d_dev,
+                       const float* z_dev, const float* viewdirs_dev, const float* x90_dev, int64_t S, int N,
+                       float* raw_dev, hipStream_t stream, const uint32_t* count_dev, const ns_composite_args* comp);
+// ns_render_rays_fused_tangent on an f16x3 / an f16 field (ns_nerf_mlp_x3_tan.hip, ns_nerf_mlp_ob16_tan.hip)
+int ns_nerf_forward_x3_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev, int64_t R,
+                               int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth, float* d_acc,
+                               hipStream_t stream);
+int ns_nerf_forward_ob16_tangent(const ns_weights* net, const float* o_dev, const float* d_dev, const float* viewdirs_dev,
+                                 int64_t R, int N, const ns_composite_args* comp, float* d_rgb, float* d_disp, float* d_depth,
+                                 float* d_acc, hipStream_t stream);
+// ns_depthnet_forward on a layout-16 handle (ns_depthnet_ob16.hip)
+int ns_depthnet_forward_ob16(const ns_weights* net, const float* o_dev, const float* d_dev, int64_t R, float near_,
+                             float far_, float sphere_radius, float* z_dev, hipStream_t stream);
