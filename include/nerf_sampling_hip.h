@@ -111,6 +111,22 @@ int ns_ray_batch_draw(const ns_ray_dataset* ds, const int* train_idx_dev, int n_
                       int* pixel_out_dev, float* rays_o_dev, float* rays_d_dev, float* viewdirs_dev, float* target_dev,
                       void* stream);
 
+/* ---- frame PSNR against a dataset image  (nerf_utils.py:303-336 render_path's per-frame PSNR, Trainer.py:289-316 the test-set
+ * log) ----  *sum_dev = sum over the pixels of rows [row0,row1) of image image_idx and the three colour channels of
+ * (double)(fl32(rgb - target))^2: ONE fp32 subtraction (numpy's rgbs - gt on fp32 arrays), squared and accumulated in double.
+ * target is the ray-batch kernels' target, bit for bit (the white-background blend included).  Ray r = (row - row0) * W + col
+ * reads rgb_dev[r * rgb_stride + c]; rgb_stride is in floats, 0 = packed 3, 4 = the interleaved [R,4] shard
+ * parallel.FrameRenderer all-gathers.  sum_dev is one double in device memory (a slot of a longer array: a test split is read
+ * back once); PSNR = -10 log10(sum / (3 * pixels)) is the host's.  Deterministic: the partition of pixels over threads and
+ * the order of every addition depend on (row1 - row0) * W alone -- per-thread doubles, a wave tree, per-workgroup partials
+ * in workspace_dev (ns_image_sqerr_workspace_bytes(pixels) bytes) and a second launch that adds them in index order; no
+ * atomics.  A NaN pixel makes the sum NaN, as numpy's mean does.  Checked before any launch (NS_E_INVALID): image_idx
+ * outside [0, n_images), an empty row band or one outside the frame, images_dev / rgb_dev / sum_dev / workspace_dev NULL,
+ * a stride other than 0, 3 or 4.                                                                                          */
+int64_t ns_image_sqerr_workspace_bytes(int64_t n_pixels);
+int ns_image_sqerr(const ns_ray_dataset* ds, int image_idx, int row0, int row1, const float* rgb_dev, int64_t rgb_stride,
+                   double* sum_dev, void* workspace_dev, void* stream);
+
 /* ---- a2  find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

@@ -115,6 +115,8 @@ SIGNATURES = {
     "ns_ray_batch_gather": (_i, [C.POINTER(RayDataset), _p, _i, _p, _i64, _p, _p, _p, _p, _p]),
     "ns_ray_batch_draw": (_i, [C.POINTER(RayDataset), _p, _i, _i, _p, C.POINTER(RayDrawParams), C.c_uint64, _i64, _p, _p,
                                _p, _p, _p, _p, _p]),
+    "ns_image_sqerr_workspace_bytes": (_i64, [_i64]),
+    "ns_image_sqerr": (_i, [C.POINTER(RayDataset), _i, _i, _i, _p, _i64, _p, _p, _p]),
     "ns_sphere_intersect": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "ns_solve_quadratic": (_i, [_p, _p, _p, _i64, _p, _p]),
     "ns_posenc": (_i, [_p, _i64, _i, _i, _p, _p]),

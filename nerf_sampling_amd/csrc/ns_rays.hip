@@ -69,6 +69,19 @@ struct BatchOut {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The target colour of pixel `pix` of image `img` (both in range): the ONE statement of it, shared by the ray-batch kernels and
+// image_sqerr_kernel (same bits from all of them).
+__device__ __forceinline__ void dataset_target(const ns_ray_dataset& ds, int img, int pix, float rgb[3]) {
+  const float* px = ds.images_dev + (static_cast<int64_t>(img) * (ds.H * ds.W) + pix) * ds.C;
+  rgb[0] = px[0]; rgb[1] = px[1]; rgb[2] = px[2];
+  if (ds.C == 4 && ds.white_bkgd) {            // BlenderTrainer.load_data: rgb * a + (1 - a), three separate roundings
+    const float a = px[3];
+    const float inv = 1.0f - a;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] * a + inv;
+  }
+}
+
 // Ray b of a batch: pixel `pix` (flat row * W + col) of image `img`, both clamped into range (no index reads out of bounds).
 __device__ __forceinline__ void emit_batch_ray(const ns_ray_dataset& ds, int img, int pix, int64_t b, const BatchOut& out) {
   img = clampi(img, 0, ds.n_images - 1);
@@ -96,14 +109,8 @@ __device__ __forceinline__ void emit_batch_ray(const ns_ray_dataset& ds, int img
     }
   }
   if (out.target) {
-    const float* px = ds.images_dev + (static_cast<int64_t>(img) * (ds.H * ds.W) + pix) * ds.C;
-    float rgb[3] = {px[0], px[1], px[2]};
-    if (ds.C == 4 && ds.white_bkgd) {          // BlenderTrainer.load_data: rgb * a + (1 - a), three separate roundings
-      const float a = px[3];
-      const float inv = 1.0f - a;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] * a + inv;
-    }
+    float rgb[3];
+    dataset_target(ds, img, pix, rgb);
     out.target[b * 3 + 0] = rgb[0]; out.target[b * 3 + 1] = rgb[1]; out.target[b * 3 + 2] = rgb[2];
   }
 }
@@ -190,6 +197,60 @@ ray_batch_draw_kernel(ns_ray_dataset ds, const int* __restrict__ train_idx, int 
     if (pixel_out) pixel_out[b] = pix;
     emit_batch_ray(ds, img, pix, b, out);
   }
+}
+
+// ---- frame PSNR on the device (ns_image_sqerr) ----------------------------------------------------------------------
+// sum over the pixels of a row band and the three channels of (double)(fl32(rgb - target))^2.  Workgroup g owns pixels
+// [g * kSqerrShare, (g + 1) * kSqerrShare); thread t adds its pixels g * kSqerrShare + k * kBlock + t in the order of k, the
+// lanes of a wave are combined by a fixed xor tree, the waves in index order by thread 0 -> partial[g].  A second launch of
+// ONE workgroup adds the partials the same way (thread t: partials t, t + kBlock, ... in order).  Every addition is fixed
+// by the pixel count alone -- no atomics, nothing that depends on the CU count; a NaN term makes the sum NaN.
+constexpr int kSqerrPerThread = 8;
+constexpr int kSqerrShare = kBlock * kSqerrPerThread;
+
+__device__ __forceinline__ double block_sum_ordered(double v, double* wave_sums) {   // valid in thread 0
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) wave_sums[wave] = v;
+  __syncthreads();
+  double s = wave_sums[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / 64; ++w) s += wave_sums[w];
+  return s;
+}
+
+__global__ void __launch_bounds__(kBlock)
+image_sqerr_kernel(ns_ray_dataset ds, int img, int pix0, int n, const float* __restrict__ rgb, int stride,
+                   double* __restrict__ partial) {
+  __shared__ double wave_sums[kBlock / 64];
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kSqerrShare + threadIdx.x;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < kSqerrPerThread; ++k) {
+    const int64_t r = base + k * kBlock;
+    if (r < n) {
+      float t[3];
+      dataset_target(ds, img, pix0 + static_cast<int>(r), t);
+      const float* p = rgb + r * stride;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double d = static_cast<double>(p[c] - t[c]);   // one fp32 subtraction, as numpy's rgbs - gt
+        acc += d * d;                                        // the square of an fp32 value is exact in double
+      }
+    }
+  }
+  const double s = block_sum_ordered(acc, wave_sums);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(kBlock)
+image_sqerr_combine_kernel(const double* __restrict__ partial, int n_partial, double* __restrict__ sum) {
+  __shared__ double wave_sums[kBlock / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partial; i += kBlock) acc += partial[i];
+  const double s = block_sum_ordered(acc, wave_sums);
+  if (threadIdx.x == 0) *sum = s;
 }
 
 // a2: utils.py:159-217.  t[.,0] is the minus-sqrt root.
@@ -443,6 +504,34 @@ int ns_ray_batch_draw(const ns_ray_dataset* ds, const int* train_idx_dev, int n_
   ray_batch_draw_kernel<<<ns::ew_grid(B, kBlock), kBlock, 0, ns::as_stream(stream)>>>(
       *ds, train_idx_dev, n_train, scope, params_dev, host, seed, B, image_idx_out_dev, pixel_out_dev,
       BatchOut{rays_o_dev, rays_d_dev, viewdirs_dev, target_dev});
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+static int64_t image_sqerr_groups(int64_t n_pixels) { return (n_pixels + kSqerrShare - 1) / kSqerrShare; }
+
+int64_t ns_image_sqerr_workspace_bytes(int64_t n_pixels) {
+  if (n_pixels <= 0) return 0;
+  return (image_sqerr_groups(n_pixels) * static_cast<int64_t>(sizeof(double)) + 255) / 256 * 256;
+}
+
+int ns_image_sqerr(const ns_ray_dataset* ds, int image_idx, int row0, int row1, const float* rgb_dev, int64_t rgb_stride,
+                   double* sum_dev, void* workspace_dev, void* stream) {
+  const int rc = check_ray_dataset(ds, 0, false, true, __func__);
+  if (rc != NS_OK) return rc;
+  NS_REQUIRE(image_idx >= 0 && image_idx < ds->n_images, "image index out of range");
+  NS_REQUIRE(row0 >= 0 && row1 <= ds->H, "row band outside the frame");
+  NS_REQUIRE(row0 < row1, "empty row band");
+  NS_REQUIRE(rgb_stride == 0 || rgb_stride == 3 || rgb_stride == 4, "rgb_stride is 0 (packed), 3 or 4 floats");
+  NS_REQUIRE(rgb_dev && sum_dev && workspace_dev, "null pointer");
+  const int n = (row1 - row0) * ds->W;                       // below 2^31: check_ray_dataset bounds n_images * H * W
+  const int groups = static_cast<int>(image_sqerr_groups(n));
+  double* partial = static_cast<double*>(workspace_dev);
+  hipStream_t s = ns::as_stream(stream);
+  image_sqerr_kernel<<<groups, kBlock, 0, s>>>(*ds, image_idx, row0 * ds->W, n, rgb_dev,
+                                               rgb_stride == 0 ? 3 : static_cast<int>(rgb_stride), partial);
+  NS_LAUNCH_CHECK();
+  image_sqerr_combine_kernel<<<1, kBlock, 0, s>>>(partial, groups, sum_dev);
   NS_LAUNCH_CHECK();
   return NS_OK;
 }

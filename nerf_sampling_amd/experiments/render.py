@@ -43,6 +43,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                    "fp32-grade split-fp16 operands (ops.set_psnr_guard; ~4.5 % of the frame).  Per-image PSNR then stays within "
                    "0.03 dB of the fp32 arithmetic on a 28-30 dB scene; without it the 16-bit paths sit at 0.03-0.26 dB "
                    "(tools/guard_experiment.py).")
+@click.option("--device-psnr", "device_psnr", is_flag=True, default=False,
+              help="(not in the reference) Score the test views on the device (Trainer(device_eval=True), "
+                   "nerf_utils.evaluate_views): the same psnr.txt, no frame copied to the host and no PNG written.  Serves "
+                   "single runs and the -e sweep; not with -nc / -nm.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -53,6 +57,8 @@ def main(**kw):
     k.update(single_image=kw["single_image"], single_ray=kw["single_ray"], save_scene_data=kw["save_scene_data"],
              i_print=kw["i_print"], compare_nerf=kw["nerf_compare"], use_nerf_max_pts=kw["nerf_max"],
              use_full_nerf=kw["nerf_full"], render_only=True, render_test=True)
+    if kw["device_psnr"]:
+        k["device_eval"] = True
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

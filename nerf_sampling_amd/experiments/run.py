@@ -43,6 +43,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="Make the training ray batches from a dataset resident on the device (Trainer(device_batches=...), not in the "
                    "reference): 'gather' uploads the host's np.random draws as indices (the same batches), 'draw' draws them "
                    "in the kernel with its own generator (other batches than np.random's).")
+@click.option("--device-eval", "device_eval", is_flag=True, default=False,
+              help="Score the test views on the device every i_testset iterations (Trainer(device_eval=True), not in the "
+                   "reference's form: its Trainer.log renders them to the host); with --fit-field the fit's held-out PSNR "
+                   "(FieldFitter.fit(i_testset=...)).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -68,6 +72,8 @@ def main(**kw):
         k["fused_step"] = True
     if kw["device_batches"]:
         k["device_batches"] = kw["device_batches"]
+    if kw["device_eval"]:
+        k["device_eval"] = True
     if kw["fit_field"]:
         k.update(ft_path=None)
         return fit_field(load_obj_from_config(cfg=config), kw["iters"], gemm_engine=kw["gemm_engine"])
@@ -83,7 +89,7 @@ def fit_field(trainer, n_iters, gemm_engine="tile"):
     from nerf_sampling_amd.trainers import FieldFitter
     from nerf_sampling_amd.utils import unfreeze_model
 
-    hwf, poses, _i_test, _i_val, i_train, images, _render_poses = trainer.load_data()
+    hwf, poses, i_test, _i_val, i_train, images, _render_poses = trainer.load_data()
     trainer.cast_intrinsics_to_right_types(hwf=hwf)
     trainer.no_reload = True
     kw_train, _kw_test, _start, _grad_vars, _optimizer = nerf_utils.create_nerf(trainer, NeRF)
@@ -94,10 +100,10 @@ def fit_field(trainer, n_iters, gemm_engine="tile"):
                          N_importance=trainer.N_importance, lrate=trainer.lrate, lrate_decay=trainer.lrate_decay,
                          white_bkgd=trainer.white_bkgd, raw_noise_std=trainer.raw_noise_std, perturb=trainer.perturb,
                          lindisp=trainer.lindisp, near=trainer.near, far=trainer.far, gemm_engine=gemm_engine)
-    split = dict(images=images, poses=poses, hwf=hwf, i_train=i_train)
+    split = dict(images=images, poses=poses, hwf=hwf, i_train=i_train, i_test=i_test)
     return fitter.fit(split, n_iters, N_rand=trainer.N_rand, basedir=trainer.basedir, expname=f"{trainer.expname}_field",
                       i_weights=trainer.i_weights, i_print=trainer.i_print, device_batches=trainer.device_batches,
-                      batch_seed=trainer.batch_seed)
+                      batch_seed=trainer.batch_seed, i_testset=trainer.i_testset if trainer.device_eval else 0)
 
 
 if __name__ == "__main__":

@@ -358,6 +358,153 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, step, wandb_log=Fals
     return np.stack(rgbs, 0), np.stack(disps, 0), total_psnr / n_render_poses
 
 
+# ---- held-out views scored on the device (not in the reference: its Trainer.log / render_path score on the host) ---------
+def format_psnr_txt(psnrs, avg) -> str:
+    """psnr.txt of a set of views in render_path's format (nerf_utils.py:318-336): one "NNN.png, PSNR: x" line per view, then
+    the average."""
+    lines = [f"{i:03d}.png, PSNR: {p}\n" for i, p in enumerate(psnrs)]
+    return "".join(lines) + f"Avg of {len(lines)} images:\nPSNR: {avg}\n"
+
+
+def _write_psnr_txt(savedir, psnrs, avg):
+    os.makedirs(savedir, exist_ok=True)
+    with open(os.path.join(savedir, "psnr.txt"), "a") as file:      # appended to, as render_path does
+        file.write(format_psnr_txt(psnrs, avg))
+
+
+def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_frames=False):
+    """The loop of evaluate_views over any whole-frame renderer: ``render_frame(c2w [3,4], workspace)`` returns the view's rgb
+    [H*W,3] on the device (or the [:, :3] view of a [H*W,4] shard), which is scored against image ``image_ids[k]`` into slot
+    k of one float64 device array (DeviceRayDataset.image_sqerr).  The workspace is this call's own, and the sums are read back
+    once, after the last frame.  -> (psnr per view [n] float64, their mean[, the frames])."""
+    import numpy as np
+
+    ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
+    if len(ids) == 0 or len(ids) != len(poses):
+        raise ValueError(f"{len(ids)} image ids for {len(poses)} poses (at least one view)")
+    workspace = ops.RenderWorkspace()
+    sums = torch.empty((len(ids),), dtype=torch.float64, device=dataset.device)
+    frames = []
+    with torch.no_grad():
+        for k, (img, c2w) in enumerate(zip(ids, poses)):
+            rgb = render_frame(c2w[:3, :4], workspace)
+            dataset.image_sqerr(img, rgb, out=sums, slot=k)
+            if return_frames:
+                frames.append(rgb)
+    psnrs = dataset.psnr_from_sqerr(sums, 3 * dataset.H * dataset.W)          # the one device-to-host copy
+    avg = float(np.mean(psnrs))                                               # the mean of the dB values, as the reference's
+    if savedir is not None:
+        _write_psnr_txt(savedir, psnrs, avg)
+    return (psnrs, avg, frames) if return_frames else (psnrs, avg)
+
+
+def hierarchical_frame_renderer(network_fn, network_fine, H, W, K, N_samples, N_importance, lindisp, white_bkgd, near, far,
+                                perturb=0.0, device="cuda"):
+    """``render_frame`` of score_views through ops.render_rays_hierarchical: the vanilla coarse + fine pass of a whole view from
+    its camera, one call, no per-sample outputs.  The random draws of ``perturb`` > 0 come from a generator of this renderer's
+    own, in _vanilla_one_call's order."""
+    gen = None
+
+    def draw(n):
+        nonlocal gen
+        if gen is None:
+            gen = torch.Generator(device=device)
+            gen.manual_seed(0)
+        return torch.rand([H * W, n], device=device, generator=gen)
+
+    def render_frame(c2w, workspace):
+        t_rand = draw(int(N_samples)) if perturb > 0.0 else None
+        u = draw(int(N_importance)) if perturb != 0.0 and int(N_importance) > 0 else None
+        fine = network_fine.packed() if (network_fine is not None and int(N_importance) > 0) else None
+        return ops.render_rays_hierarchical(network_fn.packed(), fine, camera=(H, W, K, c2w, 0, H), n_coarse=int(N_samples),
+                                            n_importance=int(N_importance), lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
+                                            near=float(near), far=float(far), t_rand=t_rand, u=u, extras=False, device=device,
+                                            workspace=workspace)["rgb"]
+
+    return render_frame
+
+
+def _dataset_targets_host(dataset, image_ids):
+    """the ground truth of the named views as host arrays [n,H,W,3], blended as the dataset's kernels blend it"""
+    import numpy as np
+
+    img = dataset.images[torch.as_tensor(np.asarray(image_ids, dtype=np.int64), device=dataset.device)].cpu().numpy()
+    if dataset.C == 4 and dataset.white_bkgd:
+        a = img[..., 3:]
+        return img[..., :3] * a + (np.float32(1.0) - a)
+    return img[..., :3]
+
+
+_evaluate_fallback_warned = False
+
+
+def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=None, return_frames=False):
+    """The device counterpart of render_path(gt_imgs=...): the PSNR of view ``poses[k]`` against image ``image_ids[k]`` of
+    ``dataset`` (a ray_batches.DeviceRayDataset, whose images are already on the device), nothing per pixel leaving it.  Every
+    view is rendered from its camera in ONE call without per-sample outputs -- ops.render_rays_depthnet with the choices of
+    render_rays_test's one-call branch, or ops.render_rays_hierarchical under trainer.use_full_nerf -- and scored by
+    ns_image_sqerr (score_views).  Returns (psnr per view as a float64 array, their mean[, the rgb frames as device tensors with
+    ``return_frames``]); with ``savedir``, psnr.txt in render_path's format and no PNG.  A configuration the one-call renderers
+    do not take falls back to render_path (PNGs included), with one warning.  The reports of compare_nerf / use_nerf_max_pts are
+    more than a PSNR: ValueError."""
+    global _evaluate_fallback_warned
+    import numpy as np
+
+    kw = render_kwargs
+    trainer = kw["trainer"]
+    if trainer.compare_nerf or trainer.use_nerf_max_pts:
+        raise ValueError("evaluate_views reports a PSNR only: compare_nerf / use_nerf_max_pts go through render_path")
+    H, W = int(hwf[0]), int(hwf[1])
+    if (H, W) != (dataset.H, dataset.W):
+        raise ValueError(f"hwf says {H} x {W}, the dataset's images are {dataset.H} x {dataset.W}")
+    dev = dataset.device
+    net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
+    with torch.no_grad():
+        basics = bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)
+        if trainer.use_full_nerf:
+            eligible = basics and _hier_one_call_eligible(kw["network_fn"], kw.get("network_fine"), kw["network_query_fn"],
+                                                          trainer, True, kw["N_samples"], kw.get("raw_noise_std", 0.0), False)
+        else:
+            eligible = basics and _one_call_eligible(kw.get("depth_network"), net, kw["network_query_fn"], trainer, True)
+    if not eligible:
+        if not _evaluate_fallback_warned:
+            import warnings
+
+            warnings.warn("evaluate_views: this configuration is not one of the one-call renderers'; the views go through "
+                          "render_path")
+            _evaluate_fallback_warned = True
+        gt = _dataset_targets_host(dataset, image_ids)
+        if savedir is not None:
+            os.makedirs(savedir, exist_ok=True)
+        with torch.no_grad():
+            rgbs, _disps, avg = render_path(poses, hwf, K, trainer.chunk, kw, step=0, gt_imgs=gt, savedir=savedir)
+        psnrs = np.array([-10.0 * np.log10(np.mean(np.square(r - g))) for r, g in zip(rgbs, gt)], dtype=np.float64)
+        if return_frames:
+            return psnrs, float(avg), [torch.from_numpy(r).reshape(-1, 3).to(dev) for r in rgbs]
+        return psnrs, float(avg)
+    if trainer.use_full_nerf:
+        render_frame = hierarchical_frame_renderer(kw["network_fn"], kw.get("network_fine"), H, W, K, kw["N_samples"],
+                                                   trainer.N_importance, kw.get("lindisp", False), kw["white_bkgd"],
+                                                   kw["near"], kw["far"], perturb=float(kw.get("perturb", 0.0)), device=dev)
+    else:
+        dn = kw["depth_network"]
+        gen = None
+
+        def render_frame(c2w, workspace):
+            nonlocal gen
+            noise = None
+            if trainer.sampling_mode == "gaussian" and int(trainer.n_depth_samples) > 1:
+                # the draws come from a generator of the evaluation's own: the global one belongs to the training step
+                if gen is None:
+                    gen = torch.Generator(device=dev)
+                    gen.manual_seed(0)
+                noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=gen)
+            return _depthnet_one_call(dn, net, trainer, camera=(H, W, K, c2w, 0, H), extras=False, device=dev, noise=noise,
+                                      workspace=workspace)["rgb"]
+
+    return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames)
+
+
 def create_nerf(args, model):
     """(render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer) -- nerf_utils.py:393-494."""
     embed_fn, input_ch = run_nerf_helpers.get_embedder(args.multires, args.i_embed, args.input_dims_embed)
@@ -585,6 +732,19 @@ def _vanilla_one_call(rays_o, rays_d, viewdirs, network_fn, network_fine, N_samp
     return out
 
 
+def _depthnet_one_call(dn, net, trainer, **source):
+    """The DepthNet-guided render of the standard configuration as one ops.render_rays_depthnet call, with the choices that are
+    the trainer's and the module's to make: the handles of the current compute dtype and their PSNR guard, the renderer (the
+    one-kernel renderer wherever it is supported), the trainer's mode / n_samples / std and the DepthNet's bounds.  ``source``:
+    the ray source (rays= or camera=), the extras, the device and what else the call takes.  render_rays_test's one-call
+    branch and evaluate_views both render through here."""
+    dn_w, net_w, guard_w = ops.psnr_guard_handles(dn, net, mode=trainer.sampling_mode, n_samples=trainer.n_depth_samples)
+    return ops.render_rays_depthnet(dn_w, net_w, n_samples=trainer.n_depth_samples, mode=trainer.sampling_mode,
+                                    std=trainer.distance, near=dn.near, far=dn.far,
+                                    sphere_radius=float(dn.sphere_radius.reshape(-1)[0]), white_bkgd=True, guard=guard_w,
+                                    guard_long_rays=ops.guard_long_rays(), **source)
+
+
 def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer, retraw=True, lindisp=False,
                      perturb=0.0, N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0.0,
                      verbose=False, pytest=False, **kwargs):
@@ -631,12 +791,8 @@ def render_rays_test(ray_batch, network_fn, network_query_fn, N_samples, trainer
         net = network_fine if network_fine is not None else network_fn
         ev = sink.new_event_pair() if sink is not None else None
         held = _held_sink
-        dn_w, net_w, guard_w = ops.psnr_guard_handles(dn, net, mode=trainer.sampling_mode, n_samples=trainer.n_depth_samples)
-        out = ops.render_rays_depthnet(dn_w, net_w, rays=(rays_o, rays_d, viewdirs),
-                                       n_samples=trainer.n_depth_samples, mode=trainer.sampling_mode, std=trainer.distance,
-                                       near=dn.near, far=dn.far, sphere_radius=float(dn.sphere_radius.reshape(-1)[0]),
-                                       white_bkgd=True, extras=True, device=rays_o.device, mlp_events=ev, guard=guard_w,
-                                       guard_long_rays=ops.guard_long_rays())
+        out = _depthnet_one_call(dn, net, trainer, rays=(rays_o, rays_d, viewdirs), extras=True, device=rays_o.device,
+                                 mlp_events=ev)
         if sink is not None:
             sink.release(after=ev[0])    # the PREVIOUS chunk's host copies start with this chunk's MLP kernel
             if held is not None and held is not sink:

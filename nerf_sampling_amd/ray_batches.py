@@ -267,6 +267,71 @@ class DeviceRayDataset:
         res = (rays, target) + ((view,) if want_viewdirs else ()) + (((idx[0], idx[1]),) if want_indices else ())
         return res
 
+    @staticmethod
+    def sqerr_workspace_bytes(n_pixels: int) -> int:
+        """ns_image_sqerr_workspace_bytes: the partial sums ``image_sqerr`` needs for a band of ``n_pixels`` pixels"""
+        from . import _lib
+
+        return int(_lib.load().ns_image_sqerr_workspace_bytes(int(n_pixels)))
+
+    def image_sqerr(self, image_idx: int, rgb, rows=None, out=None, slot: int = 0, workspace=None):
+        """ns_image_sqerr: the squared error of a rendered frame -- or of its rows ``rows`` = (row0, row1) -- against image
+        ``image_idx``, summed over pixels and the three channels in double on the device: sum (double)(fl32(rgb - target))^2,
+        target as ``gather`` returns it.  ``rgb``: fp32 [R,3] on the device, R = (row1 - row0) * W, contiguous or the
+        ``[:, :3]`` view of a contiguous [R,4] shard.  Returns a 1-element float64 device tensor, or writes ``out[slot]``
+        (``out``: a contiguous 1-d float64 device tensor) and returns ``out``.  ``workspace``: a contiguous device tensor of
+        at least ``sqerr_workspace_bytes(R)`` bytes (None: allocated for the call).  Nothing is read back: see
+        ``psnr_from_sqerr``.  What is wrong with the arguments raises ValueError before any launch."""
+        import torch
+
+        from . import _lib, ops
+
+        lib = _lib.load()
+        if not isinstance(image_idx, (int, np.integer)) or not 0 <= int(image_idx) < self.n_images:
+            raise ValueError(f"image_idx {image_idx!r} out of range [0, {self.n_images})")
+        r0, r1 = (0, self.H) if rows is None else (int(rows[0]), int(rows[1]))
+        if r0 < 0 or r1 > self.H:
+            raise ValueError(f"rows {(r0, r1)} lie outside the {self.H} x {self.W} frame")
+        if r0 >= r1:
+            raise ValueError(f"rows {(r0, r1)} are empty")
+        R = (r1 - r0) * self.W
+        if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.float32 and tuple(rgb.shape) == (R, 3)):
+            raise ValueError(f"rgb: a float32 device tensor of shape ({R}, 3)")
+        if rgb.is_contiguous():
+            stride = 3
+        elif tuple(rgb.stride()) == (4, 1):
+            stride = 4
+        else:
+            raise ValueError("rgb: contiguous [R,3], or the [:, :3] view of a contiguous [R,4] shard")
+        if out is None:
+            out, slot = torch.empty((1,), dtype=torch.float64, device=self.device), 0
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
+                  and out.is_contiguous()):
+            raise ValueError("out: a contiguous 1-d float64 device tensor")
+        slot = int(slot)
+        if not 0 <= slot < out.numel():
+            raise ValueError(f"slot {slot} out of range [0, {out.numel()})")
+        need = self.sqerr_workspace_bytes(R)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous()
+                  and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
+            raise ValueError(f"workspace: a contiguous 8-byte-aligned device tensor of at least {need} bytes")
+        _lib.check(lib.ns_image_sqerr(C.byref(self.desc), int(image_idx), r0, r1, ops._ptr(rgb), stride,
+                                      C.c_void_p(out.data_ptr() + 8 * slot), ops._ptr(workspace), ops._stream(self.device)),
+                   "ns_image_sqerr")
+        return out
+
+    @staticmethod
+    def psnr_from_sqerr(sums, n_values):
+        """-10 log10(sum / n_values) in float64, on the host: the PSNR of frames whose ``image_sqerr`` sums are ``sums`` (a
+        device or host tensor, an array or a number) over ``n_values`` = 3 * pixels values each.  A device tensor is read back
+        here, once."""
+        if hasattr(sums, "detach"):
+            sums = sums.detach().cpu().numpy()
+        with np.errstate(divide="ignore"):
+            return -10.0 * np.log10(np.asarray(sums, dtype=np.float64) / np.asarray(n_values, dtype=np.float64))
+
 
 class DrawBatchSource:
     """``DeviceRayDataset.draw`` with the step counter and the window in device memory: ``launch`` is the draw kernel and the

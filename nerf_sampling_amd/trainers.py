@@ -33,7 +33,7 @@ class Trainer:
                  input_dims_embed: int = 1, save_train_set_render: bool = True, depth_net_lr: float = 0.0001,
                  train_depth_net_only: bool = False, trial=None, single_image=False, single_ray=False,
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
-                 hip_graph: bool = True, device_batches=False, batch_seed: int = 0):
+                 hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -49,6 +49,12 @@ class Trainer:
         if self.device_batches == "draw" and single_ray:
             raise ValueError("single_ray names its ray on the host: use device_batches='gather'")
         self._ray_dataset = self._draw_source = None
+        # device_eval (not in the reference; default off): held-out views are scored on the device (nerf_utils.evaluate_views)
+        # -- render(render_test=True) writes its psnr.txt that way, and train() honours i_testset as the reference's
+        # Trainer.log does (Trainer.py:289-316).  Off, i_testset stays unused.
+        self.device_eval = bool(device_eval)
+        if self.device_eval and (compare_nerf or use_nerf_max_pts):
+            raise ValueError("device_eval reports a PSNR only: compare_nerf / use_nerf_max_pts report more (render_path)")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -153,20 +159,41 @@ class Trainer:
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
                 "test" if render_test else "path", self.global_step))
             os.makedirs(testsavedir, exist_ok=True)
+            if self.device_eval and render_test and self.render_factor == 0:
+                ds, ids = self._ray_dataset, i_test
+                if ds is None:          # called on its own: the test views alone go to the device
+                    ds, ids = ops.ray_dataset(np.asarray(images, dtype=np.float32), render_poses, self.K, [0]), range(len(i_test))
+                _, avg_test_psnr = nerf_utils.evaluate_views(ds, ids, render_poses, hwf, self.K, render_kwargs_test,
+                                                             savedir=testsavedir)
+                return avg_test_psnr
             _, _, avg_test_psnr = nerf_utils.render_path(
                 render_poses, hwf, self.K, self.chunk, render_kwargs_test, step=self.global_step,
                 save_scene_data=save_scene_data, gt_imgs=images, savedir=testsavedir, render_factor=self.render_factor)
         return avg_test_psnr
 
+    def evaluate_testset(self, i, i_test, test_poses, hwf, render_kwargs_test):
+        """device_eval: the i_test views into {basedir}/{expname}/testset_{i:06d}/psnr.txt (Trainer.log, Trainer.py:289-316,
+        without its PNGs) -> their average PSNR."""
+        savedir = os.path.join(self.basedir, self.expname, "testset_{:06d}".format(i))
+        _, avg = nerf_utils.evaluate_views(self._ray_dataset, i_test, test_poses, hwf, self.K, render_kwargs_test,
+                                           savedir=savedir)
+        return avg
+
     def train(self, N_iters=200000 + 1):
         """Trainer.train (Trainer.py:712-787): load data, build / reload the networks; render_only: render the test
         (or spiral) poses and return the average PSNR; otherwise the DepthNet optimisation loop (random ray batches from
-        one image, or -- use_batching -- from the shuffled rays of all training images), checkpoints every i_weights."""
+        one image, or -- use_batching -- from the shuffled rays of all training images), checkpoints every i_weights.
+        With device_eval the i_test views are scored every i_testset iterations (evaluate_testset)."""
         hwf, poses, i_test, i_val, i_train, images, render_poses = self.load_data()
         dev = "cuda" if self.device == "cuda" else self.device
         if self.render_test:
             render_poses = torch.tensor(np.array(poses[i_test])).to(dev)
         hwf = self.cast_intrinsics_to_right_types(hwf=hwf)
+        test_poses = None
+        if self.device_eval and dev == "cuda":
+            # all images are in the dataset (device_batches' own, when it uploads one), so the test views are too
+            self.ray_dataset(i_train, np.asarray(images, dtype=np.float32), poses)
+            test_poses = np.asarray(poses, dtype=np.float32)[np.asarray(i_test)]
         os.makedirs(os.path.join(self.basedir, self.expname), exist_ok=True)
         optimizer, sampling_optimizer, render_kwargs_train, render_kwargs_test = self.create_nerf_model()
         if self.train_depth_net_only:
@@ -200,6 +227,10 @@ class Trainer:
                 info = f"Iter: {i} Loss: {float(loss)}, Depth Net Loss: {float(depth_net_loss)}, PSNR: {float(psnr):.5f}"
                 with open(os.path.join(self.basedir, self.expname, "psnr.txt"), "a") as file:
                     file.write(f"{info}\n")
+            if test_poses is not None and self.i_testset and i % self.i_testset == 0 and i > 0:
+                with torch.no_grad():
+                    avg = self.evaluate_testset(i, i_test, test_poses, hwf, render_kwargs_test)
+                print(f"[TRAIN] Iter: {i} test PSNR: {avg}")
             if i % self.i_weights == 0:
                 path = os.path.join(self.basedir, self.expname, "{:06d}.tar".format(i))
                 utils.save_state(self.global_step, render_kwargs_train["network_fn"],
@@ -529,26 +560,32 @@ class FieldFitter:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         utils.save_state(self.global_step, self.network_fn, self.network_fine, self.optimizer, None, None, path)
 
-    def _blender_source(self, split, N_rand, device_batches=False, batch_seed=0):
+    def _blender_source(self, split, N_rand, device_batches=False, batch_seed=0, want_dataset=False):
         """Batches of N_rand rays of a Blender split as Trainer.sample_random_ray_batch draws them (one random training image
         per batch).  ``split``: load_blender_data's (images, poses, render_poses, hwf, i_split), or a dict with images
         [n,H,W,3|4], poses, hwf and i_train.  ``device_batches``: Trainer's option -- the images (all their channels) and poses
-        go to the device once, and the background blend happens per drawn pixel in the batch kernel."""
+        go to the device once, and the background blend happens per drawn pixel in the batch kernel.  ``want_dataset``: upload
+        that dataset whatever makes the batches (fit's held-out evaluation scores against it); the returned callable carries
+        it and what an evaluation needs beside it as ``dataset`` / ``poses`` / ``hwf`` / ``K`` / ``i_test``."""
         if isinstance(split, dict):
             images, poses, hwf, i_train = split["images"], split["poses"], split["hwf"], split["i_train"]
+            i_test = split.get("i_test")
         else:
             images, poses, _render_poses, hwf, i_split = split
-            i_train = i_split[0]
+            i_train, i_test = i_split[0], i_split[2]
         images = np.asarray(images)
         tr = Trainer(dataset_type="blender", basedir="", expname="", no_batching=True, datadir="", N_rand=N_rand, device="cuda",
                      device_batches=device_batches, batch_seed=batch_seed)
         tr.cast_intrinsics_to_right_types(hwf)
         poses_t = torch.tensor(np.asarray(poses), dtype=torch.float32).to("cuda")
-        if device_batches:
+        dataset = None
+        if device_batches or want_dataset:
             from .ray_batches import DeviceRayDataset
 
-            tr._ray_dataset = DeviceRayDataset(images.astype(np.float32, copy=False), poses_t, tr.K, i_train,
-                                               white_bkgd=self.white_bkgd)
+            dataset = DeviceRayDataset(images.astype(np.float32, copy=False), poses_t, tr.K, i_train,
+                                       white_bkgd=self.white_bkgd)
+        if device_batches:
+            tr._ray_dataset = dataset
         elif images.shape[-1] == 4:
             images = (images[..., :3] * images[..., -1:] + (1.0 - images[..., -1:])) if self.white_bkgd else images[..., :3]
 
@@ -556,25 +593,56 @@ class FieldFitter:
             _, _, batch_rays, target = tr.sample_random_ray_batch(None, None, i_train, images, poses_t, i)
             return batch_rays, target
 
+        draw.dataset, draw.poses, draw.hwf, draw.K, draw.i_test = dataset, np.asarray(poses, dtype=np.float32), hwf, tr.K, i_test
         return draw
 
+    def evaluate_views(self, dataset, image_ids, poses, hwf, K, savedir=None, return_frames=False):
+        """The PSNR of held-out views on the device (nerf_utils.score_views): every view through the hierarchical renderer in
+        one call, with this fitter's N_samples / N_importance, white_bkgd / lindisp / bounds and perturb 0, scored against
+        ``dataset``'s images.  Call repack() first if the weights have moved.  -> (psnr per view, their mean[, frames])."""
+        render_frame = nerf_utils.hierarchical_frame_renderer(
+            self.network_fn, self.network_fine, int(hwf[0]), int(hwf[1]), K, self.N_samples, self.N_importance, self.lindisp,
+            self.white_bkgd, self.near, self.far, perturb=0.0, device=dataset.device)
+        return nerf_utils.score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames)
+
     def fit(self, rays_source, n_iters, N_rand=1024, basedir=None, expname="field", i_weights=10000, i_print=100,
-            evaluate=None, device_batches=False, batch_seed=0):
+            evaluate=None, device_batches=False, batch_seed=0, i_testset=0, test_ids=None):
         """``n_iters`` steps on batches from ``rays_source``: a loaded Blender split (see _blender_source) or a callable
         returning (batch_rays [2,B,3], target [B,3]).  With ``basedir`` a checkpoint {basedir}/{expname}/{step:06d}.tar is written
         every ``i_weights`` steps and at the end.  ``evaluate(fitter)``, if given, runs at every ``i_print`` steps after repack().
         Both networks are repacked before the call returns.  ``device_batches`` / ``batch_seed``: how a Blender split's batches
-        are made (_blender_source).  Returns the last (loss, psnr, psnr0)."""
+        are made (_blender_source).  ``i_testset`` > 0 (a Blender split only): every ``i_testset`` steps and at the end the views
+        ``test_ids`` (default: the split's i_test) are scored on the device (``evaluate_views``), "[FIT] Iter: .. test PSNR:
+        .." is printed and, with ``basedir``, {basedir}/{expname}/testset_{step:06d}/psnr.txt written.  Returns the last
+        (loss, psnr, psnr0)."""
+        i_testset = int(i_testset or 0)
         if callable(rays_source):
             if device_batches:
                 raise ValueError("device_batches applies to a Blender split, not to a callable ray source")
+            if i_testset > 0:
+                raise ValueError("i_testset scores a Blender split's held-out views, a callable ray source has none")
             draw = lambda i: rays_source()  # noqa: E731
         else:
-            draw = self._blender_source(rays_source, N_rand, device_batches=device_batches, batch_seed=batch_seed)
+            draw = self._blender_source(rays_source, N_rand, device_batches=device_batches, batch_seed=batch_seed,
+                                        want_dataset=i_testset > 0)
+        if i_testset > 0:
+            test_ids = draw.i_test if test_ids is None else test_ids
+            if test_ids is None or len(test_ids) == 0:
+                raise ValueError("i_testset: the split names no test views (i_test) and test_ids is not given")
+            test_ids = np.asarray(test_ids, dtype=np.int64).reshape(-1)
+
+        def score():
+            self.repack()
+            savedir = None if basedir is None else os.path.join(basedir, expname, "testset_{:06d}".format(self.global_step))
+            _, avg = self.evaluate_views(draw.dataset, test_ids, draw.poses[test_ids], draw.hwf, draw.K, savedir=savedir)
+            print(f"[FIT] Iter: {self.global_step} test PSNR: {avg}")
+
         out = None
         for i in range(1, int(n_iters) + 1):
             batch_rays, target = draw(i)
             out = self.step(batch_rays, target)
+            if i_testset > 0 and (i % i_testset == 0 or i == int(n_iters)):
+                score()
             if i_print and i % i_print == 0:
                 print(f"[FIT] Iter: {self.global_step} Loss: {float(out[0])} PSNR: {float(out[1])}")
                 if evaluate is not None:

@@ -1,0 +1,96 @@
+"""ms per held-out view of render_path(gt_imgs=...) -- the frame and its per-sample arrays copied to the host, the PSNR in numpy,
+a PNG -- against nerf_utils.evaluate_views -- the frame rendered in one call, scored on the device by ns_image_sqerr -- on the
+fitted scene at 800 x 800 x 64, bf16 field with the PSNR guard; and the scoring launch alone at 800 x 800.  Each figure is the
+median of three alternations on one box, with the spread of the first path beside it.
+
+    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64]
+"""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from nerf_sampling_amd import analytic_scene, nerf_utils, ops, synthetic  # noqa: E402
+from nerf_sampling_amd.ray_batches import DeviceRayDataset  # noqa: E402
+from nerf_sampling_amd.run_nerf_helpers import get_embedder  # noqa: E402
+from nerf_sampling_amd.trainers import DepthNetTrainer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--views", type=int, default=6)
+    ap.add_argument("--size", type=int, default=800)
+    ap.add_argument("--samples", type=int, default=64)
+    ap.add_argument("--alternations", type=int, default=3)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    _coarse, fine, dn, _params = bench.build_modules("shapes_fit", dev)
+    H = W = a.size
+    focal, K = synthetic.blender_intrinsics(H, W)
+    poses = synthetic.render_poses(40)[:: 40 // a.views][: a.views].cpu()
+    gt = np.stack([analytic_scene.frame(H, W, K, p[:3, :4], device=dev)[0].float().cpu().numpy() for p in poses])
+    ds = DeviceRayDataset(gt, poses.numpy().astype(np.float32), K, [0])
+    ops.set_compute_dtype("bf16")
+    ops.set_psnr_guard(True)
+    tr = DepthNetTrainer(dataset_type="blender", basedir="/tmp", expname="x", no_batching=True, datadir="", half_res=False,
+                         white_bkgd=True, N_importance=128, N_samples=64, use_viewdirs=True, input_dims_embed=3, device="cuda",
+                         n_depth_samples=a.samples, sampling_mode="uniform", distance=0.1)
+    e1, _ = get_embedder(10, 0, 3)
+    e2, _ = get_embedder(4, 0, 3)
+    q = nerf_utils.standard_query_fn(lambda i, v, f: tr.run_network(i, v, f, embed_fn=e1, embeddirs_fn=e2, netchunk=tr.netchunk))
+    kw = dict(network_query_fn=q, perturb=0.0, N_importance=128, network_fine=fine, N_samples=64, network_fn=fine,
+              use_viewdirs=True, white_bkgd=True, raw_noise_std=0.0, trainer=tr, lindisp=True, depth_network=dn,
+              model_mode="test", near=2.0, far=6.0, ndc=False)
+    ids = list(range(a.views))
+
+    def host_path(savedir):
+        with torch.no_grad():
+            return nerf_utils.render_path(poses, [H, W, focal], K, tr.chunk, kw, step=0, gt_imgs=gt, savedir=savedir)[2]
+
+    def device_path(savedir):
+        return nerf_utils.evaluate_views(ds, ids, poses, [H, W, focal], K, kw, savedir=savedir)[1]
+
+    def timed(fn):
+        with tempfile.TemporaryDirectory() as d:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            psnr = fn(d)
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0) / a.views, float(psnr)
+
+    timed(host_path), timed(device_path)                     # warm-up: pinned buffers, packed streams, workspaces
+    host, device = [], []
+    for _ in range(a.alternations):
+        host.append(timed(host_path))
+        device.append(timed(device_path))
+    h, d = [t for t, _ in host], [t for t, _ in device]
+    print(f"{H} x {W} x {a.samples}, bf16 + PSNR guard, {a.views} views; ms per view, median of {a.alternations} alternations")
+    print(f"  render_path(gt_imgs=...)  {statistics.median(h):8.2f}   (spread {max(h) - min(h):.2f})   avg PSNR {host[-1][1]:.4f}")
+    print(f"  evaluate_views            {statistics.median(d):8.2f}   (spread {max(d) - min(d):.2f})   avg PSNR {device[-1][1]:.4f}")
+    # the scoring launch alone (two kernels: per-workgroup partial sums, their ordered sum)
+    rgb = torch.rand((H * W, 3), device=dev)
+    out = torch.empty((1,), dtype=torch.float64, device=dev)
+    ws = torch.empty((ds.sqerr_workspace_bytes(H * W),), dtype=torch.uint8, device=dev)
+    for _ in range(10):
+        ds.image_sqerr(0, rgb, out=out, workspace=ws)
+    reps, per = 200, []
+    for _ in range(a.alternations):
+        e0, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            ds.image_sqerr(0, rgb, out=out, workspace=ws)
+        e1_.record()
+        torch.cuda.synchronize()
+        per.append(1e3 * e0.elapsed_time(e1_) / reps)
+    print(f"  ns_image_sqerr alone      {statistics.median(per):8.2f} us per {H} x {W} frame   (spread {max(per) - min(per):.2f})")
+
+
+if __name__ == "__main__":
+    main()
