@@ -58,9 +58,16 @@ int ns_device_cu_count(void);
  *                            instead of the generated instruction streams;
  *   "prod_tiles" 0/4/5    -- tiles per wave of the 16-bit production kernel, 0 = chosen per launch;
  *   "hier_chain" 0/1      -- 1: ns_render_rays_hierarchical keeps raw [R,N,4] in HBM and composites with ns_raw2outputs instead
- *                            of in the MLP kernels' epilogues.
+ *                            of in the MLP kernels' epilogues;
+ *   "no_colour_skip" 0/1  -- 1: launches the render kernel would take (a 16-bit production field composited in the kernel,
+ *                            N a power of two <= 64, no raw / max-weight / guard outputs; five tiles) run the production kernel;
+ *   "count_colour_skips" 0/1 -- 1: every render-kernel launch counts the waves that skipped their colour statements.
  * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES), read once at first use.              */
 int ns_debug_set(const char* name, int value);
+/* Waves that skipped the colour layers in the LAST bf16 / f16 radiance-field launch on the current device that ran with
+ * "count_colour_skips" set: 0 when that launch ran another kernel than the render kernel, and before any such launch.
+ * Waits for the device.                                                                                            */
+int ns_colour_skip_count(int64_t* waves_out);
 
 /* ---- a1  get_rays + prepare_rays  (run_nerf_helpers.py:187-202, nerf_utils.py:156-188) ----
  * Pixel rows [row0,row1) of an HxW pinhole camera, row-major.  c2w is 12 HOST floats (3x4,
@@ -183,6 +190,13 @@ int ns_fold_depthnet_front(int n_branch, const int* hidden_sizes, int c0, const 
 /* w_out [W/2, W+27], b_out [W/2] of views_linears[0] o feature_linear (run_nerf_helpers.py:119-125)             */
 int ns_fold_nerf_views(int W, const float* w_feature, const float* b_feature, const float* w_views,
                        const float* b_views, float* w_out, float* b_out);
+/* The weight stream and the bias image ns_pack_nerf_ex builds, into HOST buffers (no device touched; tests compare the two
+ * orders): sigma_first = 0 the stream every kernel walks, 1 the render kernel's sigma-first twin (NS_E_UNSUPPORTED unless
+ * the network is a 16-bit production field: 8 x 256, skips = [4], view directions, bf16 / f16).  The sizes always come back
+ * in *stream_bytes / *bias_floats; stream_out / bias_out may be NULL to ask for them alone.                            */
+int ns_pack_nerf_host_image(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w,
+                            const float* const* b, int dtype, int sigma_first, void* stream_out, int64_t stream_cap,
+                            float* bias_out, int64_t bias_cap, int64_t* stream_bytes, int64_t* bias_floats);
 void ns_weights_destroy(ns_weights* w);
 /* bytes of the device weight stream (for roofline accounting) */
 int64_t ns_weights_stream_bytes(const ns_weights* w);

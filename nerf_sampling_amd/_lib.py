@@ -111,6 +111,7 @@ SIGNATURES = {
     "ns_version": (_i, []),
     "ns_device_cu_count": (_i, []),
     "ns_debug_set": (_i, [C.c_char_p, _i]),
+    "ns_colour_skip_count": (_i, [C.POINTER(_i64)]),
     "ns_get_rays": (_i, [_i, _i, _f, _f, _f, _f, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "ns_ray_batch_gather": (_i, [C.POINTER(RayDataset), _p, _i, _p, _i64, _p, _p, _p, _p, _p]),
     "ns_ray_batch_draw": (_i, [C.POINTER(RayDataset), _p, _i, _i, _p, C.POINTER(RayDrawParams), C.c_uint64, _i64, _p, _p,
@@ -127,6 +128,8 @@ SIGNATURES = {
     "ns_pack_depthnet_ex": (_i, [_i, _p, _i, _p, _p, _p, _i, C.POINTER(_p)]),
     "ns_fold_depthnet_front": (_i, [_i, _p, _i, _p, _p, _p, _p]),
     "ns_fold_nerf_views": (_i, [_i, _p, _p, _p, _p, _p, _p]),
+    "ns_pack_nerf_host_image": (_i, [_i, _i, C.c_uint32, _i, _i, _p, _p, _i, _i, _p, _i64, _p, _i64, C.POINTER(_i64),
+                                     C.POINTER(_i64)]),
     "ns_weights_destroy": (None, [_p]),
     "ns_weights_stream_bytes": (_i64, [_p]),
     "ns_depthnet_forward": (_i, [_p, _p, _p, _i64, _f, _f, _f, _p, _p]),

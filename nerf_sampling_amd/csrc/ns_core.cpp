@@ -79,6 +79,32 @@ DebugFlags& debug_flags() {
   return f;
 }
 
+// The render kernel's skip counter: a diagnostic (ns_debug_set("count_colour_skips", 1)), one uint32 per device.  Allocated with
+// hipMalloc by the first counted launch on a device and kept for the life of the process (four bytes, never freed); neither
+// the allocation nor the host read-back in ns_colour_skip_count belongs in a stream capture -- do not set the switch while capturing.
+static std::map<int, uint32_t*> g_skip_counters;
+static uint32_t* skip_counter_of_device(bool create) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_skip_counters.find(dev);
+  if (it != g_skip_counters.end()) return it->second;
+  if (!create) return nullptr;
+  uint32_t* p = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&p), sizeof(uint32_t)) != hipSuccess) return nullptr;
+  g_skip_counters[dev] = p;
+  return p;
+}
+int colour_skip_counter(uint32_t** counter, hipStream_t stream) {
+  *counter = nullptr;
+  if (!debug_flags().count_colour_skips) return NS_OK;
+  uint32_t* p = skip_counter_of_device(true);
+  if (!p) { set_error("colour_skip_counter: no device memory for the counter"); return NS_E_HIP; }
+  NS_HIP(hipMemsetAsync(p, 0, sizeof(uint32_t), stream));
+  *counter = p;
+  return NS_OK;
+}
+
 int& prod_tiles_hint() {
   static thread_local int hint = 0;
   return hint;
@@ -93,9 +119,22 @@ int ns_debug_set(const char* name, int value) {
   ns::DebugFlags& f = ns::debug_flags();
   if (!std::strcmp(name, "generic_kernels")) { f.generic_kernels = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "hier_chain")) { f.hier_chain = value ? 1 : 0; return NS_OK; }
+  if (!std::strcmp(name, "no_colour_skip")) { f.no_colour_skip = value ? 1 : 0; return NS_OK; }
+  if (!std::strcmp(name, "count_colour_skips")) { f.count_colour_skips = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "prod_tiles") && (value == 0 || value == 4 || value == 5)) { f.prod_tiles = value; return NS_OK; }
   ns::set_error("ns_debug_set: unknown switch or value (%s = %d)", name, value);
   return NS_E_INVALID;
+}
+int ns_colour_skip_count(int64_t* waves_out) {
+  NS_REQUIRE(waves_out, "null pointer");
+  *waves_out = 0;
+  uint32_t* p = ns::skip_counter_of_device(false);
+  if (!p) return NS_OK;   // no counted launch on this device yet
+  uint32_t v = 0;
+  NS_HIP(hipDeviceSynchronize());
+  NS_HIP(hipMemcpy(&v, p, sizeof(v), hipMemcpyDeviceToHost));
+  *waves_out = v;
+  return NS_OK;
 }
 int ns_version(void) { return 1; }
 int ns_device_cu_count(void) { return ns::cu_count(); }

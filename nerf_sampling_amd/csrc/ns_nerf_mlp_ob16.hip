@@ -10,14 +10,46 @@
 #include "ns_mlp_engine.h"
 #include "ns_weights.h"
 
-// This file is compiled twice: as itself, and with -DNS_OB16_TU_T5 as a second translation unit that holds only the
-// five-tile production kernels (the two units build in parallel; each is minutes of register allocation).
+// This file is compiled three times: as itself; with -DNS_OB16_TU_T5 as a second translation unit that holds only the
+// five-tile production kernels; and with -DNS_OB16_TU_RENDER as a third that holds only the five-tile RENDER kernels,
+// nerf_render_ob16_kernel (the units build in parallel; each is minutes of register allocation).
+//
+// The render kernel is the five-tile production kernel on the sigma-first weight stream (ns_weights::stream2_dev: same chunks,
+// the tail re-ordered to sigma sub-block | eight colour sub-blocks | rgb head), for launches that composite in the kernel and
+// hand out nothing that reads raw rgb of a zero-weight sample (render_eligible below).  After the sigma statement every wave
+// decides alone whether its 80 samples can contribute; if none can it runs the DRAIN twins of the colour and the rgb
+// statement (tools/gen_ob16_asm.py --render: the same slabs, vmcnt waits, barriers, refill pieces and read-ahead, no MFMA), so
+// the four waves of the workgroup keep walking the one weight ring in step with no vote and no extra barrier.
+// Why the results are bit-identical to the production kernel's.  A wave skips only if every one of its samples has
+// sigma <= 0 (a NaN compares false; the comparison is IEEE's, so a -0 would count -- the sigma sub-block's zero-padded view
+// K-block adds +0 products, so the accumulator never is -0), none is flagged `bad` and every {z, dist |d|} record is finite.  Then
+// relu(sigma) * dist = +-0, v_exp_f32(+-0) = 1 exactly, alpha = 1 - 1 = +0 and the weight w = +0 * T = +0 (T >= 0; a NaN T stays
+// NaN whatever the colour is).  The skipping wave writes (0, 0, 0, sigma) records: the colour enters every sum of raw2outputs
+// as w * sigmoid(raw) = +0 * sigmoid(0) = +0 = +0 * sigmoid(the real raw), for every finite real raw -- and raw is finite
+// whenever the weights are and no activation overflows the operand type (fp16: 65504).  KNOWN DIVERGENCE, not enforced: an
+// overflow in the trunk reaches sigma too (inf * w = inf or NaN: the wave does not skip), but an fp16 field whose view-layer
+// activations alone overflow to inf gives NaN rgb on the production kernel (inf * 0 in the rgb head) and 0 here, for samples of
+// zero weight.  It cannot be seen without computing the colour layers; ns_debug_set("no_colour_skip", 1) is the way out.  Outputs that read raw rgb without the weight (raw itself, the
+// max-weight sample, the guards' records) keep a launch on the production kernel.
 namespace nsob16 {
 // the field inputs, and what in-kernel placement and compositing takes (ns_comp_epilogue.h)
-struct Nerf16Args : nsmlp::FieldArgs, nsepi::CompFields {};
+struct Nerf16Args : nsmlp::FieldArgs, nsepi::CompFields {
+  uint32_t* skip_count;   // render kernel only: NULL, or a device counter bumped once per wave that skipped its colour statements
+};
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
+// the five-tile render kernel on the sigma-first stream (a.stream / a.bias name it): defined in the NS_OB16_TU_RENDER unit
+int launch_render_t5(int dtype, Nerf16Args& a, hipStream_t stream);
 }  // namespace nsob16
+
+#ifdef NS_OB16_TU_RENDER
+#define NS_OB16_KERNEL nerf_render_ob16_kernel
+#else
+#define NS_OB16_KERNEL nerf_mlp_ob16_kernel
+#endif
+#if !defined(NS_OB16_TU_T5) && !defined(NS_OB16_TU_RENDER)
+#define NS_OB16_TU_MAIN
+#endif
 
 namespace {
 
@@ -46,7 +78,15 @@ using Ob16Lds = FieldLds<kWaves, T * 3 * 1024, 11 * (T * 64)>;
 #define NS_OB16_ASM_INC "ns_ob16_asm.inc"
 #endif
 #include NS_OB16_ASM_INC
+#ifdef NS_OB16_TU_RENDER
+#include "ns_ob16_render_asm.inc"
+#endif
 namespace {
+#ifdef NS_OB16_TU_RENDER
+constexpr bool kRenderTU = true;
+#else
+constexpr bool kRenderTU = false;
+#endif
 // One W = 256 hidden layer (ReLU) as a generated asm statement: set A (hA, AGPRs) -> set V (hB, VGPRs) or back; SKIP:
 // K-blocks 0, 1 are the embedded point xs.  Same chunk walk, ring protocol and arithmetic as layer_ob16<> +
 // convert_last16<> (bit-identical results); the ring's bookkeeping is handed over and taken back here.
@@ -116,6 +156,46 @@ __device__ __forceinline__ void rgb_asm(PipeT& ring, const float* bias_lds, int 
   static_for<T>([&](auto t_) { last[decltype(t_)::value] = __builtin_bit_cast(f32x4a, ACCO[decltype(t_)::value]); });
 }
 
+#ifdef NS_OB16_TU_RENDER
+// the sigma-first tail (ns_ob16_render_asm.inc): the view layer's sigma sub-block, its eight colour sub-blocks, the rgb head
+// (sigma hands the embedded direction D on to colour in its registers; only row 0 of the sigma sub-block is kept)
+template <class M, int T, class PipeT>
+__device__ __forceinline__ void render_sigma_asm(PipeT& ring, const float* bias_lds, int g, const typename M::Block (&hB)[T][8],
+                                                 u32x4 (&D)[T], float (&sigma)[T]) {
+  u32x4 V[8 * T], ACCO[T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) { V[8 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, hB[t][decltype(kb_)::value].v); });
+  });
+  render_sigma_asm_run<M, T>(ring, bias_lds, g, V, D, ACCO);
+  static_for<T>([&](auto t_) { sigma[decltype(t_)::value] = __builtin_bit_cast(f32x4a, ACCO[decltype(t_)::value])[0]; });
+}
+template <class M, int T, class PipeT>
+__device__ __forceinline__ void render_colour_asm(PipeT& ring, const float* bias_lds, int g, const typename M::Block (&hB)[T][8],
+                                                  const u32x4 (&D)[T], typename M::Block (&hA)[T][8]) {
+  u32x4 V[8 * T], A[4 * T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) { V[8 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, hB[t][decltype(kb_)::value].v); });
+  });
+  render_colour_asm_run<M, T>(ring, bias_lds, g, V, D, A);
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<4>([&](auto kb_) { hA[t][decltype(kb_)::value].v = __builtin_bit_cast(typename M::AFrag, A[4 * t + decltype(kb_)::value]); });
+  });
+}
+template <class M, int T, class PipeT>
+__device__ __forceinline__ void render_rgb_asm(PipeT& ring, const float* bias_lds, int g, const typename M::Block (&hA)[T][8], f32x4a (&last)[T]) {
+  u32x4 A[4 * T], ACCO[T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<4>([&](auto kb_) { A[4 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, hA[t][decltype(kb_)::value].v); });
+  });
+  render_rgb_asm_run<M, T>(ring, bias_lds, g, A, ACCO);
+  static_for<T>([&](auto t_) { last[decltype(t_)::value] = __builtin_bit_cast(f32x4a, ACCO[decltype(t_)::value]); });
+}
+#endif
+
 using nsob16::Nerf16Args;
 
 // PROD: the production network (8 x 256, skips = [4], view directions: experiments/run.py) as straight-line code whose
@@ -123,7 +203,7 @@ using nsob16::Nerf16Args;
 // the statements pin them to; every other network takes the generic, compiler-scheduled path.
 template <class M, int NKB, bool EMBEDDED, bool PROD = false, int TT = kT>   // NKB = W / 32 K-blocks of a hidden layer
 __global__ void __launch_bounds__(kWaves * 64)
-nerf_mlp_ob16_kernel(Nerf16Args a) {
+NS_OB16_KERNEL(Nerf16Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int T = TT, NWAVES = kWaves, NSB = 2 * NKB;   // 16-row output sub-blocks of a hidden layer
   using Block = typename M::Block;
@@ -225,6 +305,7 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
     // nn.Linear and torch.relu all propagate it).  Here the packed-int16 ReLU would drop the NEGATIVE NaNs the matrix
     // cores produce, so the samples are flagged (bit t of `bad`, one register across the network) and written as NaN.
     uint32_t bad = 0;
+    [[maybe_unused]] bool rec_finite = true;   // render kernel: the {z, dist |d|} records of this lane's samples are finite
     auto finite = [](float v) { return __builtin_fabsf(v) < __builtin_inff(); };
     asm volatile("" ::: "memory");   // the staged inputs landed several slab steps ago (in-order vmcnt)
     if constexpr (EMBEDDED) {
@@ -259,7 +340,14 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
         if (a.pts) {
           static_for<3>([&](auto c_) { P[t][decltype(c_)::value] = staged(t, decltype(c_)::value); });
         } else {
-          const float zz = a.comp ? (*rec.zd(par, (wave * T + t) * 16 + n)).x : staged(t, 6);
+          float zz;
+          if constexpr (kRenderTU) {   // (always composites) the whole record: a non-finite dist could turn a zero alpha into NaN
+            const nsepi::v2f zdr = *rec.zd(par, (wave * T + t) * 16 + n);
+            zz = zdr.x;
+            rec_finite = rec_finite && finite(zdr.x) && finite(zdr.y);
+          } else {
+            zz = a.comp ? (*rec.zd(par, (wave * T + t) * 16 + n)).x : staged(t, 6);
+          }
           static_for<3>([&](auto c_) {
             constexpr int c = decltype(c_)::value;
             P[t][c] = staged(t, c) + staged(t, 3 + c) * zz;
@@ -389,15 +477,39 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
       if constexpr (kb < NKB) return hA[decltype(t_)::value][kb]; else return vs[decltype(t_)::value];
     };
     float sigma[T];
+    [[maybe_unused]] bool skipped = false;   // render kernel: this wave ran the drain twins
     if constexpr (PROD) {   // the trunk ended in hB: (hB, ve) -> hA[0 .. NKB/2), then rgb from hA
       auto in_Bv = [&](auto t_, auto kb_) -> const Block& {
         constexpr int kb = decltype(kb_)::value;
         if constexpr (kb < NKB) return hB[decltype(t_)::value][kb]; else return vs[decltype(t_)::value];
       };
       (void)in_Bv;
+#ifdef NS_OB16_TU_RENDER
+      // the sigma-first stream: sigma, then EITHER colour and rgb OR their drain twins (see the file's header comment)
+      u32x4 D[T];
+      static_for<T>([&](auto t_) { D[decltype(t_)::value] = __builtin_bit_cast(u32x4, vs[decltype(t_)::value].v); });
+      render_sigma_asm<M, T>(ring, bias, g, hB, D, sigma); bias += 16;
+      // (bitwise, not ||: straight-line code) this lane knows of a sample that may contribute, or that must come out NaN
+      uint32_t live = static_cast<uint32_t>(bad != 0) | static_cast<uint32_t>(!rec_finite);
+      static_for<T>([&](auto t_) {
+        constexpr int t = decltype(t_)::value;
+        // lanes 0..15 hold row 0 = sigma; a NaN compares false, -0 <= 0
+        live |= static_cast<uint32_t>(g == 0) & static_cast<uint32_t>(!(sigma[t] <= 0.0f));
+      });
+      skipped = __builtin_amdgcn_ballot_w64(live != 0) == 0;   // (wave-uniform: a scalar branch)
+      if (skipped) {
+        render_drain_asm_run<M, T, 3>(ring, bias, g); bias += (NSB / 2) * 16;
+        render_drain_asm_run<M, T, 4>(ring, bias, g);
+        static_for<T>([&](auto t_) { last[decltype(t_)::value] = f32x4a{0.0f, 0.0f, 0.0f, 0.0f}; });
+      } else {
+        render_colour_asm<M, T>(ring, bias, g, hB, D, hA); bias += (NSB / 2) * 16;
+        render_rgb_asm<M, T>(ring, bias, g, hA, last);
+      }
+#else
       views_asm<M, T>(ring, bias, g, hB, vs, hA, last); bias += (NSB / 2 + 1) * 16;
       static_for<T>([&](auto t_) { sigma[decltype(t_)::value] = last[decltype(t_)::value][0]; });
       rgb_asm<M, T>(ring, bias, g, hA, last);
+#endif
     } else {
     layer_ob16<M, T, NSB / 2 + 1, NKB + 1, kRelu>(ring, bias, g, hB, last, in_Av); bias += (NSB / 2 + 1) * 16;
     static_for<T>([&](auto t_) { sigma[decltype(t_)::value] = last[decltype(t_)::value][0]; });
@@ -419,6 +531,9 @@ nerf_mlp_ob16_kernel(Nerf16Args a) {
         if (valid && a.raw) reinterpret_cast<float4*>(a.raw)[sidx] = o4;
       });
     }
+    if constexpr (kRenderTU) {
+      if (skipped && a.skip_count && le == 0) atomicAdd(a.skip_count, 1u);
+    }
     if constexpr (!EMBEDDED) nsepi::composite_group(a, rec, comp, grp, gi, par, wave, le);
   }
   ring.finish();
@@ -431,10 +546,18 @@ int launch(Nerf16Args& a, hipStream_t stream) {
   a.sg_groups = nsepi::run_groups(kWaves * TT * 16, a.m_chunks, a.N);
   const int64_t n_runs = (n_groups + a.sg_groups - 1) / a.sg_groups;
   const Ob16Lds<TT> lm(a.bias_floats, a.comp && !EMB ? nsepi::Records<TT, kWaves>::kBytes : 0);
-  return ns::launch_persistent("ns_nerf_forward", nerf_mlp_ob16_kernel<M, NKB, EMB, PROD, TT>, a, kWaves * 64, lm.end, n_runs, stream);
+  return ns::launch_persistent("ns_nerf_forward", NS_OB16_KERNEL<M, NKB, EMB, PROD, TT>, a, kWaves * 64, lm.end, n_runs, stream);
 }
 
-#ifndef NS_OB16_TU_T5
+#ifdef NS_OB16_TU_MAIN
+// Which launches the render kernel takes (five tiles): the handle carries the sigma-first stream (a production 16-bit network),
+// the kernel composites rays of one chunk, and nothing handed out reads raw rgb of a sample whose weight may be zero -- raw
+// itself, the max-weight sample, the every-ray and the selective guard.  Per-sample weights / z / pts do not disqualify.
+bool render_eligible(const ns_weights* net, const Nerf16Args& a) {
+  return net->stream2_dev && net->bias2_dev && !ns::debug_flags().no_colour_skip && a.comp != 0 && !a.m_chunks && a.N >= 2 &&
+         a.N <= 64 && (a.N & (a.N - 1)) == 0 && !a.raw && !a.pts && !a.x90 && !a.max_w && !a.max_z && !a.max_rgb && !a.fix_rec &&
+         !a.sig_last;
+}
 template <class M, bool EMB>
 int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
 #if NS_NERF16_T == 4 && NS_NERF16_WAVES == 4
@@ -450,7 +573,14 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
     int tiles = NS_OB16_PROD_T ? NS_OB16_PROD_T : (t5 < t4 ? 5 : 4);
     if (ns::prod_tiles_hint()) tiles = ns::prod_tiles_hint();               // the renderer's hint (host copies in flight)
     if (ns::debug_flags().prod_tiles) tiles = ns::debug_flags().prod_tiles;   // diagnostic override (ns_debug_set)
-    if (tiles == 5) return nsob16::launch_prod_t5(M::kDtype, EMB, a, stream);
+    if (tiles == 5) {
+      if (!EMB && render_eligible(net, a)) {
+        Nerf16Args r = a;
+        r.stream = static_cast<const char*>(net->stream2_dev); r.bias = net->bias2_dev;
+        return nsob16::launch_render_t5(M::kDtype, r, stream);
+      }
+      return nsob16::launch_prod_t5(M::kDtype, EMB, a, stream);
+    }
     return launch<M, 8, EMB, true, 4>(a, stream);
   }
 #endif
@@ -460,7 +590,12 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
 
 }  // namespace
 
-#ifdef NS_OB16_TU_T5
+#if defined(NS_OB16_TU_RENDER)
+int nsob16::launch_render_t5(int dtype, Nerf16Args& a, hipStream_t stream) {
+  if (dtype == Mma16BF16::kDtype) return launch<Mma16BF16, 8, false, true, 5>(a, stream);
+  return launch<Mma16F16, 8, false, true, 5>(a, stream);
+}
+#elif defined(NS_OB16_TU_T5)
 int nsob16::launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream) {
   if (dtype == Mma16BF16::kDtype) return embedded ? launch<Mma16BF16, 8, true, true, 5>(a, stream) : launch<Mma16BF16, 8, false, true, 5>(a, stream);
   return embedded ? launch<Mma16F16, 8, true, true, 5>(a, stream) : launch<Mma16F16, 8, false, true, 5>(a, stream);
@@ -509,6 +644,10 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
       a.fix_thr = comp->fix_thr; a.fix_count = comp->fix_count_dev; a.fix_rec = comp->fix_rec_dev;
     }
   }
+  // the render kernel's skip counter: NULL unless ns_debug_set("count_colour_skips", 1); zeroed for EVERY launch from here, so a
+  // launch that runs another kernel reads back as 0
+  const int rc_count = ns::colour_skip_counter(&a.skip_count, stream);
+  if (rc_count != NS_OK) return rc_count;
   const bool emb = x90_dev != nullptr;
 #ifdef NS_OB16_VARIANT_BUILD   // tools/build_asm_variant.sh: only the kernel under test is instantiated (a 20 s build)
   if (net->dtype == NS_DTYPE_BF16 && !emb && net->width == 256 && net->depth == 8 && net->skip_mask == (1u << 4) && net->use_viewdirs)
@@ -519,4 +658,4 @@ int ns_nerf_forward_ob16(const ns_weights* net, const float* pts_dev, const floa
   if (net->dtype == NS_DTYPE_F16) return emb ? dispatch_m<Mma16F16, true>(net, a, stream) : dispatch_m<Mma16F16, false>(net, a, stream);
   return NS_E_UNSUPPORTED;
 }
-#endif  // NS_OB16_TU_T5
+#endif  // NS_OB16_TU_RENDER / NS_OB16_TU_T5 / main

@@ -137,10 +137,11 @@ struct Builder {
       }
     }
   }
-  void layer_ob16(const float* Wm, int out_f, int in_f, int nsb, const std::vector<Seg>& segs) {
+  // (sb0: the first of the nsb sub-blocks, for a stream that walks a layer's sub-blocks in another order)
+  void layer_ob16(const float* Wm, int out_f, int in_f, int nsb, const std::vector<Seg>& segs, int sb0 = 0) {
     const size_t base = bytes.size();
     size_t n = 0;
-    for (int sb = 0; sb < nsb; ++sb)
+    for (int sb = sb0; sb < sb0 + nsb; ++sb)
       for (const Seg& sg : segs)
         for (int kb = 0; kb < sg.nblk; ++kb) {
           bytes.resize(base + (n + 1 + (split ? 1 : 0)) * kChunkBytes, 0);
@@ -156,8 +157,8 @@ struct Builder {
     const size_t slabs = (padded + kSlabChunks - 1) / kSlabChunks;
     bytes.resize(base + slabs * kSlabBytes, 0);
   }
-  void add_bias16(const float* b, int out_f, int nsb) {   // natural order, 16 per sub-block
-    for (int i = 0; i < 16 * nsb; ++i) bias.push_back(i < out_f ? b[i] : 0.0f);
+  void add_bias16(const float* b, int out_f, int nsb, int sb0 = 0) {   // natural order, 16 per sub-block
+    for (int i = 16 * sb0; i < 16 * (sb0 + nsb); ++i) bias.push_back(i < out_f ? b[i] : 0.0f);
   }
 
   void add_bias(const float* b, int out_f, int nbo) {
@@ -298,6 +299,26 @@ int finish(Builder& b, ns_weights* w) {
   NS_HIP(hipMemcpy(w->bias_dev, b.bias.data(), b.bias.size() * sizeof(float), hipMemcpyHostToDevice));
   return NS_OK;
 }
+// the sigma-first twin of a production field's stream: optional -- without it (no device memory) the launches run the production kernel
+void finish_sigma_first(const Builder& b2, ns_weights* w) {
+  if (b2.bytes.size() != static_cast<size_t>(w->n_slabs) * kSlabBytes || static_cast<int>(b2.bias.size()) != w->bias_floats) return;
+  void* s2 = nullptr;
+  float* bias2 = nullptr;
+  if (hipMalloc(&s2, b2.bytes.size()) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&bias2), b2.bias.size() * sizeof(float)) == hipSuccess &&
+      hipMemcpy(s2, b2.bytes.data(), b2.bytes.size(), hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(bias2, b2.bias.data(), b2.bias.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) {
+    w->stream2_dev = s2; w->bias2_dev = bias2;
+    return;
+  }
+  (void)hipGetLastError();
+  if (s2) (void)hipFree(s2);
+  if (bias2) (void)hipFree(bias2);
+}
+
+// Host part of ns_pack_nerf_ex: validates, folds and builds the stream and the bias image into `bl` -- and, for a production 16-bit
+// field, their sigma-first twins into `bl2` (has2).  Wk: the kernel width the network was padded to.
+int build_nerf(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w, const float* const* b,
+               int dtype, Builder& bl, Builder& bl2, bool& has2, int& Wk);
 
 }  // namespace
 
@@ -313,10 +334,13 @@ int ns_pack_nerf(int D, int W, int skip, const float* const* w, const float* con
   return ns_pack_nerf_ex(D, W, skip >= 0 ? (1u << skip) : 0u, 1, 4, w, b, dtype, out);
 }
 
-int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w,
-                    const float* const* b, int dtype, ns_weights** out) {
-  NS_REQUIRE(out && w && b, "null pointer");
-  *out = nullptr;
+}  // extern "C"
+
+namespace {
+int build_nerf(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w, const float* const* b,
+               int dtype, Builder& bl, Builder& bl2, bool& has2, int& Wk) {
+  has2 = false;
+  Wk = W;
   const int out_ch = use_viewdirs ? 4 : output_ch;
   if (W >= 1 && W <= 256 && W != 128 && W != 256 && D >= 1 && D <= 32) {
     // Any width up to 256 runs on the W = 128 / 256 kernels: every tensor is zero-padded to the next kernel width Wp.  A padded
@@ -353,7 +377,7 @@ int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int outp
     }
     std::vector<const float*> wp(n_tensors), bp(n_tensors);
     for (int i = 0; i < n_tensors; ++i) { wp[i] = pw[i].data(); bp[i] = pb[i].data(); }
-    return ns_pack_nerf_ex(D, Wp, skip_mask, use_viewdirs, output_ch, wp.data(), bp.data(), dtype, out);
+    return build_nerf(D, Wp, skip_mask, use_viewdirs, output_ch, wp.data(), bp.data(), dtype, bl, bl2, has2, Wk);
   }
   if (!(W == 128 || W == 256) || D < 1 || D > 32 || (skip_mask >> (D - 1)) != 0 || out_ch < 1 || out_ch > 16 ||
       !(dtype == NS_DTYPE_F32 || dtype == NS_DTYPE_BF16 || dtype == NS_DTYPE_F16 || dtype == NS_DTYPE_F16X3)) {
@@ -379,7 +403,6 @@ int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int outp
     }
   }
   const int NB = W / 32;
-  Builder bl(dtype);
   auto ident = [](int k) { return k; };
   auto xcol = [](int k) { return nsmlp::embed3_col(k, 10); };
   const int layout = dtype == NS_DTYPE_F32 ? 0 : 16;   // 0 = k-major (fp32 kernel); 16 = 16x16x32 engine (bf16 / f16)
@@ -443,9 +466,21 @@ int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int outp
       std::memcpy(bc.data(), bvf.data(), bvf.size() * sizeof(float));
       std::memcpy(wc.data() + static_cast<size_t>(HV) * KV, wf[1], static_cast<size_t>(W) * sizeof(float));
       bc[HV] = b[D + 1][0];
+      const std::vector<Builder::Seg> vsegs = {{NKB, ident}, {1, [W](int k) { const int c = nsmlp::embed3_col16(k, 4); return c < 0 ? -1 : W + c; }}};
+      if (W == 256 && D == 8 && skip_mask == (1u << 4) && !bl.split) {
+        // the production field: the sigma-first twin for the render kernel.  Same chunks (the sigma sub-block keeps its all-zero
+        // view K-block: the accumulator chain is the view layer's), each of the three statements padded and slab-aligned like a layer
+        has2 = true;
+        bl2.bytes = bl.bytes; bl2.bias = bl.bias;
+        bl2.add_bias16(bc.data(), HV + 1, 1, NSB / 2);
+        bl2.layer_ob16(wc.data(), HV + 1, KV, 1, vsegs, NSB / 2);
+        bl2.add_bias16(bc.data(), HV + 1, NSB / 2);
+        bl2.layer_ob16(wc.data(), HV + 1, KV, NSB / 2, vsegs);
+        bl2.add_bias16(b[D + 3], 3, 1);
+        bl2.layer_ob16(wf[3], 3, W / 2, 1, {{NKB / 2, ident}});
+      }
       bl.add_bias16(bc.data(), HV + 1, NSB / 2 + 1);
-      bl.layer_ob16(wc.data(), HV + 1, KV, NSB / 2 + 1,
-                    {{NKB, ident}, {1, [W](int k) { const int c = nsmlp::embed3_col16(k, 4); return c < 0 ? -1 : W + c; }}});
+      bl.layer_ob16(wc.data(), HV + 1, KV, NSB / 2 + 1, vsegs);
       bl.add_bias16(b[D + 3], 3, 1);
       bl.layer_ob16(wf[3], 3, W / 2, 1, {{NKB / 2, ident}});
     } else {
@@ -454,15 +489,58 @@ int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int outp
     }
   }
 
+  return NS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ns_pack_nerf_ex(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w,
+                    const float* const* b, int dtype, ns_weights** out) {
+  NS_REQUIRE(out && w && b, "null pointer");
+  *out = nullptr;
+  Builder bl(dtype), bl2(dtype);
+  bool has2 = false;
+  int Wk = W;
+  int rc = build_nerf(D, W, skip_mask, use_viewdirs, output_ch, w, b, dtype, bl, bl2, has2, Wk);
+  if (rc != NS_OK) return rc;
   ns_weights* h = new ns_weights();
   std::memset(h, 0, sizeof(*h));
-  h->kind = NS_KIND_NERF; h->dtype = dtype; h->width = W; h->depth = D; h->layout = layout;
-  h->skip_mask = skip_mask; h->use_viewdirs = use_viewdirs ? 1 : 0; h->out_ch = out_ch;
+  h->kind = NS_KIND_NERF; h->dtype = dtype; h->width = Wk; h->depth = D; h->layout = dtype == NS_DTYPE_F32 ? 0 : 16;
+  h->skip_mask = skip_mask; h->use_viewdirs = use_viewdirs ? 1 : 0; h->out_ch = use_viewdirs ? 4 : output_ch;
   h->skip = -1;
   for (int i = 0; i < 32; ++i) if ((skip_mask >> i) & 1u) { h->skip = i; break; }
-  int rc = finish(bl, h);
+  rc = finish(bl, h);
   if (rc != NS_OK) { ns_weights_destroy(h); return rc; }
+  if (has2) finish_sigma_first(bl2, h);
   *out = h;
+  return NS_OK;
+}
+
+int ns_pack_nerf_host_image(int D, int W, uint32_t skip_mask, int use_viewdirs, int output_ch, const float* const* w,
+                            const float* const* b, int dtype, int sigma_first, void* stream_out, int64_t stream_cap,
+                            float* bias_out, int64_t bias_cap, int64_t* stream_bytes, int64_t* bias_floats) {
+  NS_REQUIRE(w && b && stream_bytes && bias_floats, "null pointer");
+  Builder bl(dtype), bl2(dtype);
+  bool has2 = false;
+  int Wk = W;
+  const int rc = build_nerf(D, W, skip_mask, use_viewdirs, output_ch, w, b, dtype, bl, bl2, has2, Wk);
+  if (rc != NS_OK) return rc;
+  if (sigma_first && !has2) {
+    ns::set_error("ns_pack_nerf_host_image: only a 16-bit production field (8 x 256, skips = [4], view directions) has a sigma-first stream");
+    return NS_E_UNSUPPORTED;
+  }
+  const Builder& src = sigma_first ? bl2 : bl;
+  *stream_bytes = static_cast<int64_t>(src.bytes.size());
+  *bias_floats = static_cast<int64_t>(src.bias.size());
+  if (stream_out) {
+    NS_REQUIRE(stream_cap >= *stream_bytes, "stream buffer too small");
+    std::memcpy(stream_out, src.bytes.data(), src.bytes.size());
+  }
+  if (bias_out) {
+    NS_REQUIRE(bias_cap >= *bias_floats, "bias buffer too small");
+    std::memcpy(bias_out, src.bias.data(), src.bias.size() * sizeof(float));
+  }
   return NS_OK;
 }
 
@@ -610,6 +688,8 @@ void ns_weights_destroy(ns_weights* w) {
   if (!w) return;
   if (w->stream_dev) (void)hipFree(w->stream_dev);
   if (w->bias_dev) (void)hipFree(w->bias_dev);
+  if (w->stream2_dev) (void)hipFree(w->stream2_dev);
+  if (w->bias2_dev) (void)hipFree(w->bias2_dev);
   delete w;
 }
 

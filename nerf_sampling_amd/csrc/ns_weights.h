@@ -19,6 +19,12 @@ struct ns_weights {
   uint32_t n_slabs;
   float* bias_dev;       // all biases in LDS image order, fp32
   int bias_floats;
+  // 16-bit production field (8 x 256, skips = [4], view directions; bf16 / f16) only, else NULL: the SIGMA-FIRST stream of the
+  // render kernel (ns_nerf_mlp_ob16.hip) -- the same n_slabs, the same chunks with the same contents, the tail re-ordered into
+  // three slab-aligned statements: the view layer's sigma sub-block | its eight colour sub-blocks | the rgb head -- and the
+  // bias image in that order (bias_floats as well)
+  void* stream2_dev;
+  float* bias2_dev;
 };
 
 enum { NS_KIND_NERF = 0, NS_KIND_DEPTHNET = 1 };

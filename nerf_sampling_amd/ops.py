@@ -832,6 +832,14 @@ class debug_switch:
         return False
 
 
+def colour_skip_count() -> int:
+    """Waves that skipped the colour layers in the last 16-bit radiance-field launch made under
+    ``debug_switch(count_colour_skips=1)`` (0 when that launch did not run the render kernel); waits for the device."""
+    n = C.c_int64(0)
+    check(_lib.load().ns_colour_skip_count(C.byref(n)), "ns_colour_skip_count")
+    return int(n.value)
+
+
 class Event:
     """hipEvent wrapper for timing a kernel on the stream it is launched on."""
 

@@ -616,13 +616,24 @@ def special_spec(kind, m):
         return dict(nsb=9, nkb=9, operand=lambda t, kc: m.SETV(t, kc) if kc < 8 else m.XS(t, 0), convert=True, convert_last=False, out_acc=True)
     if kind == "rgb":
         return dict(nsb=1, nkb=4, operand=lambda t, kc: m.SETA(t, kc), convert=False, convert_last=False, out_acc=True)
+    # the view layer of the sigma-first stream (--render): its sigma sub-block on its own, returned raw (the all-zero view
+    # K-block stays: the accumulator chain is the view layer's), then the eight colour sub-blocks, all converted
+    if kind == "sigma":
+        return dict(nsb=1, nkb=9, operand=lambda t, kc: m.SETV(t, kc) if kc < 8 else m.XS(t, 0), convert=False, convert_last=False, out_acc=True)
+    if kind == "colour":
+        return dict(nsb=8, nkb=9, operand=lambda t, kc: m.SETV(t, kc) if kc < 8 else m.XS(t, 0), convert=True, convert_last=True, out_acc=False)
     raise ValueError(kind)
 
 
-def gen_layer_special(dt, kind, m):
+def gen_layer_special(dt, kind, m, drain=False):
     """Layer 0, view layer, rgb head as statements (queue layout of gen_layer_q: together they are 9 of the 67 slabs).
     Their streams are not slab multiples: the chunks are padded to the fragment pipeline depth (pad steps carry no MFMA),
-    the last slab may be short (its refill pieces ride on its first four steps)."""
+    the last slab may be short (its refill pieces ride on its first four steps).
+
+    drain: the statement's twin for a wave that does not need its result -- every step is a pad step.  The ring protocol is
+    the full statement's (same slabs, vmcnt waits, barriers, refill pieces with their islab / dsto / M0 bookkeeping, the same
+    read-ahead of the NEXT statement's first fragments at the end), so the wave stays in step with the three that compute; no
+    MFMA, no fragment or bias read, no conversion."""
     sp = special_spec(kind, m)
     TT, nsb, nkb = m.T, sp["nsb"], sp["nkb"]
     real = nsb * nkb
@@ -631,7 +642,8 @@ def gen_layer_special(dt, kind, m):
     cvt = "v_cvt_pk_bf16_f32" if dt == "bf16" else "v_cvt_pk_f16_f32"
     e = Emitter(dt)
     e.salu("s_mov_b32 %[keep], m0")
-    e.lds_read(m.BIAS, "%[bias]", 0)
+    if not drain:
+        e.lds_read(m.BIAS, "%[bias]", 0)
 
     def dma_setup():
         e.valu(f"v_lshl_add_u32 {fmt(m.VOFF)}, %[islab], 14, %[loff]", (), (m.VOFF,))
@@ -663,7 +675,8 @@ def gen_layer_special(dt, kind, m):
     def read_ahead(p):
         q = p + DEPTH - 1
         if q < real:
-            e.lds_read(m.FR(q), f"%[rb{(q // SLAB) % RING}]", (q % SLAB) * 1024)
+            if not drain:
+                e.lds_read(m.FR(q), f"%[rb{(q // SLAB) % RING}]", (q % SLAB) * 1024)
         elif q >= total:                 # the next statement's first chunks, in the slab after this layer's last
             e.lds_read(m.FR(q), f"%[rb{slabs % RING}]", (q - total) * 1024)
 
@@ -689,7 +702,7 @@ def gen_layer_special(dt, kind, m):
                 if p + 1 < total:
                     dma_setup()
 
-        if p >= real:                    # pad step: no MFMA
+        if p >= real or drain:           # pad step: no MFMA
             if c == 0 and not OPT.no_barrier:
                 e.salu(f"s_waitcnt vmcnt({VM_WAIT})")
                 e.salu("s_barrier")
@@ -725,7 +738,7 @@ def gen_layer_special(dt, kind, m):
     assert not pending_salu
     while conv_q:
         conv_q.pop(0)()
-    if sp["convert_last"]:
+    if sp["convert_last"] and not drain:
         s_ = nsb - 1
         scratch = [R('v', m.ACC((s_ & 1) ^ 1, 0)[1] + i) for i in range(2 * TT)]
         for t0 in range(0, TT, 2):
@@ -801,6 +814,143 @@ template <> struct SpecialAsm<{mname}, {nt}, {kid}> {{
   }}
 }};
 """
+
+
+RENDER_KINDS = (("sigma", False), ("colour", False), ("rgb", False), ("colour", True), ("rgb", True))   # RenderAsm<.., KIND>
+
+
+def cpp_render(dt, kind, drain, e, slabs, mp):
+    """struct RenderAsm<M, NT, KIND> of the sigma-first tail (--render): KIND 0 = sigma sub-block (set V, D -> raw accumulators),
+    1 = colour sub-blocks (set V, D -> set A K-blocks 0..3), 2 = rgb head (set A K-blocks 0..3 -> raw accumulators), 3 / 4 = the
+    drain twins of 1 / 2 (the ring only)"""
+    nt = mp.T
+    mname = {"bf16": "Mma16BF16", "f16": "Mma16F16"}[dt]
+    kid = RENDER_KINDS.index((kind, drain))
+    text = "\\n\\t\"\n      \"".join(i.text for i in e.ins)
+    outs, ins, params = [], [], []
+    clobber = list(mp.CLOBBER)
+    if drain:
+        clobber = [mp.VOFF[1]]           # the refill address is all a drain twin writes
+    else:
+        if kind in ("sigma", "colour"):
+            # sigma hands the embedded direction on to colour in the registers it arrived in (an in-out operand it never writes:
+            # the compiler would otherwise form it a second time in front of colour)
+            params = [f"const u32x4 (&V)[{8 * nt}]", f"u32x4 (&D)[{nt}]" if kind == "sigma" else f"const u32x4 (&D)[{nt}]"]
+            for t in range(nt):
+                for kb in range(8):
+                    ins.append(f'"{{{fmt(mp.SETV(t, kb))}}}"(V[{8 * t + kb}])')
+                if kind == "sigma":
+                    outs.append(f'"+{{{fmt(mp.XS(t, 0))}}}"(D[{t}])')
+                else:
+                    ins.append(f'"{{{fmt(mp.XS(t, 0))}}}"(D[{t}])')
+        if kind == "colour":
+            params.append(f"u32x4 (&A)[{4 * nt}]")
+            for t in range(nt):
+                for kb in range(4):
+                    outs.append(f'"=&{{{fmt(mp.SETA(t, kb))}}}"(A[{4 * t + kb}])')
+        if kind == "rgb":
+            params = [f"const u32x4 (&A)[{4 * nt}]"]
+            for t in range(nt):
+                for kb in range(4):
+                    ins.append(f'"{{{fmt(mp.SETA(t, kb))}}}"(A[{4 * t + kb}])')
+        if kind in ("sigma", "rgb"):
+            params.append(f"u32x4 (&ACCO)[{nt}]")
+            for t in range(nt):
+                r = mp.ACC(0, t)
+                outs.append(f'"=&{{{fmt(r)}}}"(ACCO[{t}])')
+                for i in range(4):
+                    clobber.remove(r[1] + i)
+    for i in range(DEPTH):
+        outs.append(f'"+{{{fmt(mp.FR(i))}}}"(F[{i}])')
+    outs += ['[islab] "+s"(islab)', '[dsto] "+s"(dsto)', '[keep] "=&s"(keep)']
+    ins += ['[rb0] "v"(rb0)', '[rb1] "v"(rb1)', '[rb2] "v"(rb2)', '[rb3] "v"(rb3)', '[bias] "v"(bias)', '[loff] "v"(loff)',
+            '[sbase] "s"(sbase)', '[nsl] "s"(nsl)', '[ldsw] "s"(ldsw)']
+    clob = ['"memory"', '"scc"', '"vcc"'] + [f'"v{i}"' for i in clobber]
+    n_mfma = sum(i.kind == "mfma" for i in e.ins)
+    return f"""
+// {dt} {nt} tiles {kind}{' drain' if drain else ''}: {len(e.ins)} instructions, {n_mfma} MFMAs, {slabs} slabs; s_nop {sum(i.kind == 'nop' for i in e.ins)}
+template <> struct RenderAsm<{mname}, {nt}, {kid}> {{
+  static constexpr int kSlabs = {slabs};
+  static __device__ __forceinline__ void run({', '.join(params + ['u32x4 (&F)[4]'])},
+                                             uint32_t rb0, uint32_t rb1, uint32_t rb2, uint32_t rb3, uint32_t bias, uint32_t loff,
+                                             uint64_t sbase, uint32_t nsl, uint32_t ldsw, uint32_t& islab, uint32_t& dsto) {{
+    uint32_t keep;
+    asm volatile(
+      "{text}"
+      : {', '.join(outs)}
+      : {', '.join(ins)}
+      : {', '.join(clob)});
+  }}
+}};
+"""
+
+
+RENDER_HEADER = """// GENERATED by tools/gen_ob16_asm.py --render -- do not edit; regenerate with `python tools/gen_ob16_asm.py --render`.
+// The tail of the sigma-first weight stream (ns_pack.hip) as statements, and the drain twins a wave runs instead of the colour
+// statements when none of its samples can contribute (ns_nerf_mlp_ob16.hip, NS_OB16_TU_RENDER).  Included after ns_ob16_asm.inc.
+#pragma once
+namespace nsmlp {
+// KIND: 0 sigma sub-block, 1 colour sub-blocks, 2 rgb head, 3 drain twin of 1, 4 drain twin of 2
+template <class M, int NT, int KIND> struct RenderAsm;
+"""
+
+
+RENDER_FOOTER = """
+// sigma: (set V, embedded direction D) -> ACCO, the raw accumulators of the view layer's sigma sub-block
+template <class M, int NT, class PipeT>
+__device__ __forceinline__ void render_sigma_asm_run(PipeT& ring, const float* bias_lds, int g, const u32x4 (&V)[8 * NT], u32x4 (&D)[NT],
+                                                     u32x4 (&ACCO)[NT]) {
+  using Gen = RenderAsm<M, NT, 0>;
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(V, D, ACCO, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+// colour: (set V, D) -> K-blocks 0..3 of set A
+template <class M, int NT, class PipeT>
+__device__ __forceinline__ void render_colour_asm_run(PipeT& ring, const float* bias_lds, int g, const u32x4 (&V)[8 * NT], const u32x4 (&D)[NT],
+                                                      u32x4 (&A)[4 * NT]) {
+  using Gen = RenderAsm<M, NT, 1>;
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(V, D, A, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+// rgb head: K-blocks 0..3 of set A -> raw accumulators
+template <class M, int NT, class PipeT>
+__device__ __forceinline__ void render_rgb_asm_run(PipeT& ring, const float* bias_lds, int g, const u32x4 (&A)[4 * NT], u32x4 (&ACCO)[NT]) {
+  using Gen = RenderAsm<M, NT, 2>;
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(A, ACCO, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+// the drain twin of the colour (KIND 3) or the rgb (KIND 4) statement: walks the ring, computes nothing
+template <class M, int NT, int KIND, class PipeT>
+__device__ __forceinline__ void render_drain_asm_run(PipeT& ring, const float* bias_lds, int g) {
+  using Gen = RenderAsm<M, NT, KIND>;
+  static_assert((KIND == 3 || KIND == 4) && Gen::kSlabs == RenderAsm<M, NT, KIND - 2>::kSlabs, "a drain twin walks its statement's slabs");
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+}  // namespace nsmlp
+"""
+
+
+def render_main(path, maps):
+    """--render: the statements of the sigma-first tail and their drain twins (each through check() inside gen_layer_special)"""
+    out = [RENDER_HEADER]
+    for dt in ("bf16", "f16"):
+        for mp in maps:
+            for kind, drain in RENDER_KINDS:
+                e, slabs = gen_layer_special(dt, kind, mp, drain=drain)
+                out.append(cpp_render(dt, kind, drain, e, slabs, mp))
+                print(f"{dt} {mp.T} tiles {kind}{' drain' if drain else ''}: {len(e.ins)} instr, {slabs} slabs", file=sys.stderr)
+    out.append(RENDER_FOOTER)
+    with open(path, "w") as f:
+        f.write("".join(out))
 
 
 def gen_layer_x3(in_a, skip, nsb=16, nkb_h=8, act="relu"):
@@ -1129,7 +1279,11 @@ __device__ __forceinline__ void rgb_asm_run(PipeT& ring, const float* bias_lds, 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("-o", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "nerf_sampling_amd", "csrc", "ns_ob16_asm.inc"))
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "nerf_sampling_amd", "csrc")
+    ap.add_argument("-o", help="output file (default: csrc/ns_ob16_asm.inc, or csrc/ns_ob16_render_asm.inc with --render)")
+    ap.add_argument("--render", action="store_true",
+                    help="write the sigma-first tail of the renderer (sigma, colour, rgb and the drain twins; five tiles) instead")
+    ap.add_argument("--render-tiles4", action="store_true", help="with --render: the four-tile statements as well")
     ap.add_argument("--dump", help="write the plain instruction stream of one variant (e.g. bf16_AV) here")
     for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"):
         ap.add_argument("--exp-" + k.replace("_", "-"), dest=k, action="store_true")
@@ -1142,6 +1296,10 @@ def main():
     assert len(OPT.dma_steps) == 4 and OPT.dma_steps[-1] <= 9
     for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"):
         setattr(OPT, k, getattr(a, k))
+    if a.render:
+        render_main(a.o or os.path.join(csrc, "ns_ob16_render_asm.inc"), (Map4, Map5) if a.render_tiles4 else (Map5,))
+        return
+    a.o = a.o or os.path.join(csrc, "ns_ob16_asm.inc")
     out = [HEADER]
     for dt in ("bf16", "f16"):
         for in_a in (True, False):
