@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "ns_composite_ray.h"
+#include "ns_guard.h"
 #include "ns_mlp_engine.h"
 #include "ns_place.h"
 #include "ns_weights.h"
@@ -22,18 +23,6 @@ typedef v4f __attribute__((address_space(3))) * CrawPtr;
 typedef v2f __attribute__((address_space(3))) * CzdPtr;
 typedef float __attribute__((address_space(3))) * CsigPtr;
 typedef uint32_t __attribute__((address_space(3))) * CslotPtr;
-
-// The selective guard's record of a flagged ray of SEVERAL chunks (ns_render_args::guard_long_selective): kFixLongFloats floats.
-// The last sample's share sits inside the last chunk's 64-lane sum, which reduce5<64> forms on lane 63 as
-//   u6 + (u5 + (u4 + (u3 + (u2 + (x62 + x63)))))        x_i: lane i's share;  u_k: what lane 63 - 2^(k-1) holds after k - 1 steps
-// (u2 = x60 + x61, u3 the sum of lanes 56 .. 59, u4 of 48 .. 55, u5 of 32 .. 47, u6 of 0 .. 31, each as the scan rounds it), and
-// the ray's totals are (the earlier chunks' running totals) + that.  The record keeps, per sum, the earlier total and the six
-// operands beside x63, so the fix-up repeats the seven additions with the re-evaluated share -- the forward's own arithmetic
-// stays as it is.  Floats 5 .. 12 are those of the single-chunk record (ns_fix_gather reads either):
-//   0..4 earlier totals {r, g, b, depth, acc} | 5 T entering the last sample | 6..8 its raw rgb | 9 z | 10 dist | 11, 12 ray index
-//   lo / hi | 16 + 5 k + 0..4, k = 0 .. 5: x62, u2, u3, u4, u5, u6 of {r, g, b, depth, acc}
-constexpr int kFixLongFloats = NS_FIX_LONG_FLOATS, kFixLongOperands = 16;
-static_assert(kFixLongOperands + 6 * 5 <= kFixLongFloats, "six operands of five sums behind the single-chunk record's fields");
 
 // The compositing fields of a kernel's argument struct (Nerf16Args, NerfX3CompArgs, nstan::TanArgs inherit them), which place_wave /
 // composite_group / set_comp_args read by name.
@@ -58,11 +47,8 @@ struct CompFields {
   // groups -- lcm(group samples, N) samples, whole rays -- before it jumps, so that a ray's chunks meet in one workgroup and
   // the transmittance / sums of the ray that is open at a group boundary carry over in LDS
   int m_chunks, sg_groups;
-  // the selective guard: a ray whose own sigma of the last sample is within fix_thr of zero -- where the step
-  // alpha = step(sigma) could flip under the 16-bit rounding -- leaves a record at slot atomicAdd(fix_count) of fix_rec.  Rays of
-  // one chunk: 16 floats {tree sums r g b depth acc, T, raw rgb of the last sample, its z and dist, ray index lo / hi}
-  // (ns_fix_last_sample re-evaluates sigma through the fp32-grade handle and repeats the last addition).  Rays of several chunks:
-  // kFixLongFloats floats, the operands of the last chunk's additions as well (above, ns_fix_last_sample_long)
+  // the selective guard: a ray whose own sigma of the last sample is within fix_thr of zero leaves a record at slot
+  // atomicAdd(fix_count) of fix_rec (ns_guard.h: nsfix::kFloats floats for a ray of one chunk, kLongFloats for one of several)
   float fix_thr;
   uint32_t* fix_count;
   float* fix_rec;
@@ -255,7 +241,7 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         if (__builtin_expect(afix && pos == m - 1, 0)) {
           // The selective guard, on the chunk that ends a ray (wave-uniform): lane 63 holds the ray's last sample.  A sigma within
           // fix_thr of zero (a NaN compares false: a NaN ray stays NaN) flags the ray: the wave writes the record's operands
-          // (kFixLongFloats above) at the slot lane 63 draws, and phase 3 adds the earlier chunks' totals through kFIX.
+          // (ns_guard.h) at the slot lane 63 draws, and phase 3 adds the earlier chunks' totals through kFIX.
           const int i = c * 64 + le;
           const v4f qv = *rec.raw(i);                             // (this group's until the barrier below)
           const bool flag = le == 63 && okc[ci] && __builtin_fabsf(qv.w) < a.fix_thr;
@@ -264,14 +250,14 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
             uint32_t slot = 0;
             if (le == 63) slot = atomicAdd(a.fix_count, 1u);
             slot = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(slot), 63));
-            float* q = a.fix_rec + static_cast<size_t>(slot) * kFixLongFloats;
+            float* q = a.fix_rec + static_cast<size_t>(slot) * nsfix::kLongFloats;
             if (le == 63) {
               const v2f zd = *rec.zd(par, i);
-              const uint64_t r = static_cast<uint64_t>((C0 + c) / m);
+              const int64_t r = (C0 + c) / m;
               *rec.slot(c) = slot + 1u;
-              q[5] = Tr; q[6] = qv.x; q[7] = qv.y;                                     // (floats 0 .. 4 are phase 3's)
-              reinterpret_cast<float4*>(q)[2] = make_float4(qv.z, zd.x, zd.y, __builtin_bit_cast(float, static_cast<uint32_t>(r)));
-              q[12] = __builtin_bit_cast(float, static_cast<uint32_t>(r >> 32));
+              q[nsfix::kLongT] = Tr; q[nsfix::kLongRaw] = qv.x; q[nsfix::kLongRaw + 1] = qv.y;   // (kLongSum + 0 .. 4 are phase 3's)
+              *reinterpret_cast<float4*>(q + nsfix::kLongRaw + 2) = make_float4(qv.z, zd.x, zd.y, nsfix::fix_ray_lo(r));
+              q[nsfix::kLongRayHi] = nsfix::fix_ray_hi(r);
             }
             // x62, then u2 .. u6: lane 63 - SW after the first log2 SW steps of the 64-lane reduction, which are reduce5<SW>'s own
             nsmlp::static_for<6>([&](auto k_) {
@@ -280,7 +266,7 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
               nscomp::RayAccum X = shares();
               if constexpr (k > 0) nscomp::reduce_sums<SW>(X, le);
               if (le == (k == 0 ? 62 : 63 - SW)) {
-                float* u = q + kFixLongOperands + 5 * k;
+                float* u = q + nsfix::kLongOps + nsfix::kSums * k;
                 u[0] = X.r; u[1] = X.g; u[2] = X.b; u[3] = X.depth; u[4] = X.acc;
               }
             });
@@ -320,9 +306,9 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         if (__builtin_expect(afix && ends, 0)) {     // a flagged ray: its totals before the last chunk, for the fix-up
           const uint32_t slot = *rec.slot(c);
           if (slot) {
-            float* q = a.fix_rec + static_cast<size_t>(slot - 1u) * kFixLongFloats;
-            reinterpret_cast<float4*>(q)[0] = make_float4(tot.r, tot.g, tot.b, tot.depth);
-            q[4] = tot.acc;
+            float* q = a.fix_rec + static_cast<size_t>(slot - 1u) * nsfix::kLongFloats;
+            *reinterpret_cast<float4*>(q + nsfix::kLongSum) = make_float4(tot.r, tot.g, tot.b, tot.depth);
+            q[nsfix::kLongSum + 4] = tot.acc;
           }
         }
         add_chunk(c);
@@ -405,11 +391,11 @@ __device__ __forceinline__ void composite_group(const Args& a, const Records<T, 
         if (a.depth) a.depth[r] = A.depth;
         if (a.acc) a.acc[r] = A.acc;
         if (a.fix_rec && __builtin_fabsf(q.w) < a.fix_thr) {      // (a NaN sigma compares false: a NaN ray stays NaN)
-          float* rec16 = a.fix_rec + static_cast<size_t>(atomicAdd(a.fix_count, 1u)) * 16;
-          reinterpret_cast<float4*>(rec16)[0] = make_float4(tree.r, tree.g, tree.b, tree.depth);
-          reinterpret_cast<float4*>(rec16)[1] = make_float4(tree.acc, Tr, q.x, q.y);
-          reinterpret_cast<float4*>(rec16)[2] = make_float4(q.z, zd.x, zd.y, __builtin_bit_cast(float, static_cast<uint32_t>(r)));
-          rec16[12] = __builtin_bit_cast(float, static_cast<uint32_t>(static_cast<uint64_t>(r) >> 32));
+          float* fr = a.fix_rec + static_cast<size_t>(atomicAdd(a.fix_count, 1u)) * nsfix::kFloats;
+          *reinterpret_cast<float4*>(fr + nsfix::kSum) = make_float4(tree.r, tree.g, tree.b, tree.depth);
+          *reinterpret_cast<float4*>(fr + nsfix::kSum + 4) = make_float4(tree.acc, Tr, q.x, q.y);
+          *reinterpret_cast<float4*>(fr + nsfix::kRaw + 2) = make_float4(q.z, zd.x, zd.y, nsfix::fix_ray_lo(r));
+          fr[nsfix::kRayHi] = nsfix::fix_ray_hi(r);
         }
       }
     };

@@ -6,6 +6,8 @@
 
 #include <type_traits>
 
+#include "ns_guard.h"
+
 namespace nscomp {
 
 // running sums of one ray, one lane's share
@@ -216,15 +218,15 @@ __device__ __forceinline__ void recomposite_last(RayAccum& A /* in: tree sums, o
 // The fix-up of a ray of SEVERAL chunks: its last sample's share x63 sits inside the last chunk's 64-lane sum, which reduce5<64>
 // leaves on lane 63 as u6 + (u5 + (u4 + (u3 + (u2 + (x62 + x63))))), and add_chunk_totals adds that to the earlier chunks' running
 // total.  op[k][s], k = 0 .. 5: x62, u2 .. u6 of sum s (r, g, b, depth, acc) as the one-kernel renderer recorded them
-// (ns_comp_epilogue.h); A: in the earlier chunks' totals, out the ray's.
-__device__ __forceinline__ void recomposite_last_long(RayAccum& A, const float (&op)[6][5], float T, float qx, float qy, float qz,
+// (ns_guard.h); A: in the earlier chunks' totals, out the ray's.
+__device__ __forceinline__ void recomposite_last_long(RayAccum& A, const float (&op)[nsfix::kOps][nsfix::kSums], float T, float qx, float qy, float qz,
                                                       float sigma, float z, float dist, int white_bkgd, float& disp, float& w_out) {
   const float w = sample_alpha(sigma, dist) * T;
-  float c[5] = {0.0f + w * sample_colour(qx), 0.0f + w * sample_colour(qy), 0.0f + w * sample_colour(qz), 0.0f + w * z, 0.0f + w};
+  float c[nsfix::kSums] = {0.0f + w * sample_colour(qx), 0.0f + w * sample_colour(qy), 0.0f + w * sample_colour(qz), 0.0f + w * z, 0.0f + w};
 #pragma unroll
-  for (int s = 0; s < 5; ++s)
+  for (int s = 0; s < nsfix::kSums; ++s)
 #pragma unroll
-    for (int k = 0; k < 6; ++k) c[s] = op[k][s] + c[s];
+    for (int k = 0; k < nsfix::kOps; ++k) c[s] = op[k][s] + c[s];
   A.r = A.r + c[0]; A.g = A.g + c[1]; A.b = A.b + c[2]; A.depth = A.depth + c[3]; A.acc = A.acc + c[4];
   finish_totals(A, white_bkgd, disp);
   w_out = w;

@@ -435,15 +435,6 @@ place_z_uniform4_kernel(const float* __restrict__ mean, int64_t R, int N, float 
   }
 }
 
-// the LAST sample of every ray only (the guard pass of ns_render_rays_*: ns_render_args::nerf_guard)
-__global__ void __launch_bounds__(kBlock)
-place_last_kernel(const float* __restrict__ mean, int64_t R, int N, float std_, float* __restrict__ z_last) {
-  const int steps = N - 1;
-  const float step = steps > 1 ? (std_ - (-std_)) / static_cast<float>(steps - 1) : 0.0f;
-  for (int64_t r = blockIdx.x * (int64_t)kBlock + threadIdx.x; r < R; r += (int64_t)gridDim.x * kBlock)
-    z_last[r] = nsplace::uniform_z(mean[r], std_, step, steps, N - 1);
-}
-
 __global__ void __launch_bounds__(kBlock)
 points_kernel(const float* __restrict__ o, const float* __restrict__ d,
               const float* __restrict__ z, int64_t R, int N, float* __restrict__ pts) {
@@ -765,12 +756,3 @@ int ns_coarse_z_scalar(float near_, float far_, int64_t R, int N, int lindisp, c
 }
 
 }  // extern "C"
-
-#include "ns_weights.h"
-int ns_place_last_sample(const float* mean_dev, int64_t R, int N, float std_, float* z_last_dev, void* stream) {
-  NS_REQUIRE(R >= 0 && N >= 2 && mean_dev && z_last_dev, "bad arguments");
-  if (R == 0) return NS_OK;
-  place_last_kernel<<<ns::ew_grid(R, kBlock), kBlock, 0, ns::as_stream(stream)>>>(mean_dev, R, N, std_, z_last_dev);
-  NS_LAUNCH_CHECK();
-  return NS_OK;
-}

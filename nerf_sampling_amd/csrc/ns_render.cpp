@@ -1,6 +1,7 @@
 // The DepthNet branch of render_rays_test (nerf_utils.py:836-865) as one call: a fixed chain of
 // kernel launches on the caller's stream, intermediates in a caller-provided workspace.
 #include "ns_common.h"
+#include "ns_guard.h"
 #include "ns_weights.h"
 
 namespace {
@@ -35,16 +36,17 @@ ChainLayout chain_layout(Carve& ws, int64_t R, int N) {
 }
 
 struct FusedLayout { RaySlices rays; float *mean, *z_last, *raw_last; uint32_t* fix_count; float* fix_rec; RaySlices fix_rays; };
-// long_records: the selective guard on rays of several chunks (ns_render_args::guard_long_selective) -- its records are
-// NS_FIX_LONG_FLOATS floats; every other call keeps the layout and the size it has had
-FusedLayout fused_layout(Carve& ws, int64_t R, bool long_records) {
+// rec_floats: the selective guard's record (ns_guard.h) -- nsfix::kLongFloats on rays of several chunks
+// (ns_render_args::guard_long_selective); every other call keeps nsfix::kFloats, the layout and the size it has had
+constexpr int64_t kFixCountBytes = 256;   // the selective guard's counter, a slice of its own
+FusedLayout fused_layout(Carve& ws, int64_t R, int rec_floats) {
   FusedLayout l;
   l.rays = take_rays(ws, R);
   l.mean = ws.take(R * 4);
   l.z_last = ws.take(R * 4);          // the every-ray guard's depth and raw of the last sample; the selective guard's z and raw
   l.raw_last = ws.take(R * 16);       // of the flagged rays' last samples
-  l.fix_count = reinterpret_cast<uint32_t*>(ws.take(256));   // the selective guard: counter, records (64 bytes for a ray of one
-  l.fix_rec = ws.take(R * (long_records ? NS_FIX_LONG_FLOATS * 4 : 64));   // chunk, 192 for one of several), compacted rays
+  l.fix_count = reinterpret_cast<uint32_t*>(ws.take(kFixCountBytes));   // the selective guard: counter, records, compacted rays
+  l.fix_rec = ws.take(R * rec_floats * 4);
   l.fix_rays = take_rays(ws, R);
   return l;
 }
@@ -198,14 +200,14 @@ int ns_render_fused_supported(const ns_weights* nerf, int mode, int N) {
 int64_t ns_render_fused_workspace_bytes(int64_t R) {
   if (R < 0) return 0;
   Carve ws;
-  fused_layout(ws, R, false);
+  fused_layout(ws, R, nsfix::kFloats);
   return ws.total;
 }
 
 int64_t ns_render_fused_guard_long_workspace_bytes(int64_t R) {
   if (R < 0) return 0;
   Carve ws;
-  fused_layout(ws, R, true);
+  fused_layout(ws, R, nsfix::kLongFloats);
   return ws.total;
 }
 
@@ -228,9 +230,10 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   const bool long_rays = a->N > 64;
   const bool selective = a->nerf_guard && a->guard_threshold > 0.0f && (!long_rays || a->guard_long_selective == 1) &&
                          a->nerf_guard->dtype == NS_DTYPE_F16X3 && a->nerf_guard->layout == 16 && a->nerf->dtype != NS_DTYPE_F16X3;
+  const int rec_floats = selective && long_rays ? nsfix::kLongFloats : nsfix::kFloats;
   FusedLayout l;
   Rays r;
-  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = fused_layout(ws, R, selective && long_rays); return l.rays; }, &r, stream);
+  rc = resolve_rays(a, [&](Carve& ws, int64_t R) { l = fused_layout(ws, R, rec_floats); return l.rays; }, &r, stream);
   if (rc != NS_OK || r.R == 0) return rc;
   rc = ns_depthnet_forward(a->depthnet, r.o, r.d, r.R, a->near_, a->far_, a->sphere_radius, l.mean, stream);
   if (rc != NS_OK) return rc;
@@ -243,7 +246,7 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
     c.fix_thr = a->guard_threshold;
     c.fix_count_dev = l.fix_count;
     c.fix_rec_dev = l.fix_rec;
-    NS_HIP(hipMemsetAsync(l.fix_count, 0, 256, ns::as_stream(stream)));
+    NS_HIP(hipMemsetAsync(l.fix_count, 0, kFixCountBytes, ns::as_stream(stream)));
   } else if (a->nerf_guard) {     // (before the event pair: the pair times the fused kernel alone)
     rc = guard_pass(a, r, l.mean, l.z_last, l.raw_last, stream);
     if (rc != NS_OK) return rc;
@@ -259,15 +262,13 @@ int ns_render_rays_fused(const ns_render_args* a, void* stream) {
   if ((rc = record(a->ev_mlp_end, stream)) != NS_OK) return rc;
   if (!selective) return NS_OK;
   const RaySlices& fr = l.fix_rays;
-  rc = ns_fix_gather(l.fix_rec, long_rays ? NS_FIX_LONG_FLOATS : 16, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view,
-                     l.z_last, stream);
+  rc = ns_fix_gather(l.fix_rec, rec_floats, l.fix_count, r.R, r.o, r.d, r.view, fr.o, fr.d, fr.view, l.z_last, stream);
   if (rc != NS_OK) return rc;
   rc = ns_nerf_forward_x3(a->nerf_guard, nullptr, fr.o, fr.d, l.z_last, fr.view, nullptr, r.R, 1, l.raw_last,
                           ns::as_stream(stream), l.fix_count, nullptr);
   if (rc != NS_OK) return rc;
-  rc = (long_rays ? ns_fix_last_sample_long : ns_fix_last_sample)(l.fix_rec, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd,
-                                                                  out.rgb, out.rgb_stride, out.disp, out.disp_stride, out.weights,
-                                                                  out.depth, out.acc, stream);
+  rc = ns_fix_last_sample(l.fix_rec, rec_floats, l.fix_count, r.R, l.raw_last, a->N, a->white_bkgd, out.rgb, out.rgb_stride,
+                          out.disp, out.disp_stride, out.weights, out.depth, out.acc, stream);
   if (rc != NS_OK || !a->guard_count_dev) return rc;
   NS_HIP(hipMemcpyAsync(a->guard_count_dev, l.fix_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, ns::as_stream(stream)));
   return NS_OK;

@@ -43,9 +43,8 @@ struct ns_composite_args {
   float* pts_out_dev;      // [R,N,3] or NULL
   const float* sigma_last_dev;   // NULL, or [R,4] raw of every ray's LAST sample from the guard pass: its sigma (element 3)
                                  // replaces the kernel's own for that sample (ns_render_args::nerf_guard)
-  // the selective guard (ns_render_args::guard_threshold > 0): records of the rays whose own |sigma_last| < fix_thr (16 floats
-  // each for N <= 64, NS_FIX_LONG_FLOATS for rays of several chunks: nsepi::CompFields::fix_rec), counted in *fix_count_dev (zeroed by
-  // the caller)
+  // the selective guard (ns_render_args::guard_threshold > 0): records of the rays whose own |sigma_last| < fix_thr (laid out in
+  // ns_guard.h), counted in *fix_count_dev (zeroed by the caller)
   float fix_thr;
   uint32_t* fix_count_dev;
   float* fix_rec_dev;
@@ -57,23 +56,6 @@ struct ns_composite_args {
   float* depth_dev;        // [R]
   float* acc_dev;          // [R]
 };
-// the selective guard's two small kernels (ns_composite.hip): compact inputs of the flagged rays' last samples for the fp32-grade
-// network; then the flagged pixels from the records and the re-evaluated sigma (raw_c [.,4], element 3)
-// (rec_floats: the record's length, 16 or NS_FIX_LONG_FLOATS -- ray index and z sit at the same floats of both)
-int ns_fix_gather(const float* rec_dev, int rec_floats, const uint32_t* count_dev, int64_t cap, const float* o_dev,
-                  const float* d_dev, const float* view_dev, float* o_c, float* d_c, float* view_c, float* z_c, void* stream);
-int ns_fix_last_sample(const float* rec_dev, const uint32_t* count_dev, int64_t cap, const float* raw_c, int N, int white_bkgd,
-                       float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev,
-                       float* depth_dev, float* acc_dev, void* stream);
-// ... and the second of them for rays of several chunks (N = 128 .. 512: records of NS_FIX_LONG_FLOATS floats, laid out in
-// ns_comp_epilogue.h)
-enum { NS_FIX_LONG_FLOATS = 48 };
-int ns_fix_last_sample_long(const float* rec_dev, const uint32_t* count_dev, int64_t cap, const float* raw_c, int N, int white_bkgd,
-                            float* rgb_dev, int64_t rgb_stride, float* disp_dev, int64_t disp_stride, float* weights_dev,
-                            float* depth_dev, float* acc_dev, void* stream);
-// internal helpers of the guard pass (ns_rays.hip, ns_composite.hip)
-int ns_place_last_sample(const float* mean_dev, int64_t R, int N, float std_, float* z_last_dev, void* stream);
-int ns_patch_sigma_last(float* raw_dev, const float* raw_last_dev, int64_t R, int N, void* stream);
 bool ns_nerf_can_composite(const ns_weights* net, int N);
 
 // The layout-16 kernels behind the public forwards and the one-call renderers (arguments validated by the callers).

@@ -469,6 +469,37 @@ def test_psnr_guard_replaces_sigma_of_the_last_sample(gpu_modules, dtype):
         assert bool((shard == -7.0).all()), one
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_selective_guard_with_every_ray_and_no_ray_flagged(gpu_modules, dtype):
+    """The selective guard's record, gather and fix-up at the smallest shapes where they can go wrong: one ray and 67 (a ragged
+    last group) of 2, 64 (one chunk: 16-float records) and 128 samples (two chunks: 48-float records, guard_long_rays=
+    "selective").  Threshold 1e30 flags every ray: each pixel, map and last weight is rewritten from its record and must carry the
+    every-ray guard's bits.  Threshold 1e-30 flags none: the unguarded render's bits."""
+    from nerf_sampling_amd import ops
+
+    m = gpu_modules("tiny_synth")                        # (its rays are NaN-free: torch.equal compares values)
+    dn, nf, gw = m["depth"].packed("f16x3"), m["fine"].packed(dtype), m["fine"].packed("f16x3")
+    _, K = O.blender_intrinsics(9, 9)
+    o, d, view = ops.get_rays(9, 9, K, O.pose_spherical(30.0, -30.0, 4.0)[:3, :4])[:3]
+    outs = ("rgb", "disp", "depth", "acc", "weights")
+    for R in (1, 67):
+        rays = (o[:R].contiguous(), d[:R].contiguous(), view[:R].contiguous())
+        for n in (2, 64, 128):
+            def render(**kw):
+                return ops.render_rays_depthnet(dn, nf, rays=rays, n_samples=n, mode="uniform", std=0.1, one_kernel=True,
+                                                extras=("weights", "depth", "acc", "guard_count"),
+                                                guard_long_rays="selective" if n > 64 else "every", **kw)
+            every = render(guard=gw, guard_threshold=0.0)
+            flagged = render(guard=gw, guard_threshold=1e30)
+            plain = render()
+            none = render(guard=gw, guard_threshold=1e-30)
+            assert all(bool(torch.isfinite(every[k]).all()) for k in outs), (R, n)
+            assert int(flagged["guard_count"]) == R and int(none["guard_count"]) == 0, (R, n)
+            for k in outs:
+                assert torch.equal(flagged[k], every[k]), (R, n, k, float((flagged[k] - every[k]).abs().max()))
+                assert torch.equal(none[k], plain[k]), (R, n, k, float((none[k] - plain[k]).abs().max()))
+
+
 def step_rule_mask(raw_ref, z_ref, d, rgb_ref, sigma_last_eps, tol=1e-2):
     """Rays whose ORACLE colour moves by more than `tol` when sigma of the LAST sample alone moves by +-sigma_last_eps: the
     reference composites the last sample with dist = 1e10 (sampling_trainer.py:176-180), so alpha_last = step(sigma_last)
