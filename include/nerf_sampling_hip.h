@@ -160,6 +160,25 @@ int64_t ns_image_ssim_workspace_bytes(int H, int W);
 int ns_image_ssim(const ns_ray_dataset* ds, int image_idx, const float* rgb_dev, int64_t rgb_stride, double* sum_dev,
                   void* workspace_dev, void* stream);
 
+/* ---- placed samples against the field's depth  (nerf_utils.py:311-317 render_path's "MSE:" under compare_nerf,
+ * mse_loss(max_z_vals, depth_net_z_vals); Trainer.py:537 depth_net_loss = mse(depth_net_z_vals, max_z_vals)) ----
+ * *sum_dev = sum over rays r in [0, R) and samples k in [0, N) of (double)(fl32(z_dev[r * z_row_stride + k] - ref_dev[r]))^2:
+ * ONE fp32 subtraction (torch's mse_loss on fp32 tensors), its square exact in double, the sum kept in double; the mean,
+ * sum / (R * N), is the host's.  ref_dev is [R] packed (a contiguous [R,1] has the same layout); z_row_stride is in floats,
+ * 0 = packed N, otherwise >= N (a column slice of a wider buffer); N = 1 scores a vector [R].  sum_dev is one double in
+ * device memory (a slot of a longer array).  Deterministic as ns_image_sqerr: workgroup g owns the NS_DEPTH_SQERR_SHARE flat
+ * elements e = r * N + k from g * NS_DEPTH_SQERR_SHARE on, a thread adds its elements in index order, then a wave tree,
+ * per-workgroup partials in workspace_dev (ns_depth_sqerr_workspace_bytes(R, N) bytes) and ns_image_sqerr's second launch
+ * adding them in index order -- the order of every addition depends on (R, N) alone; no atomics.  A NaN term (a ray that
+ * misses the sphere has a NaN DepthNet depth) makes the sum NaN, as the reference's MSE is then.  Checked before any launch
+ * (NS_E_INVALID): z_dev / ref_dev / sum_dev / workspace_dev NULL, R < 1, N < 1, a stride in [1, N), and R * N >= 2^31 -- the
+ * flat element index and its division by N are 32-bit (800 x 800 x 64 is 4.1e7).  ns_depth_sqerr_workspace_bytes is 0 for a
+ * shape that would be refused.                                                                                            */
+#define NS_DEPTH_SQERR_SHARE 2048
+int64_t ns_depth_sqerr_workspace_bytes(int64_t R, int N);
+int ns_depth_sqerr(const float* z_dev, int64_t z_row_stride, const float* ref_dev, int64_t R, int N, double* sum_dev,
+                   void* workspace_dev, void* stream);
+
 /* ---- a2 find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

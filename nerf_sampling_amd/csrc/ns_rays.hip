@@ -253,6 +253,33 @@ image_sqerr_combine_kernel(const double* __restrict__ partial, int n_partial, do
   if (threadIdx.x == 0) *sum = s;
 }
 
+// ---- placed samples against the field's depth (ns_depth_sqerr) ------------------------------------------------------
+// sum over rays r and samples k of (double)(fl32(z[r, k] - ref[r]))^2, the flat element e = r * N + k.  Workgroup g owns
+// elements [g * kDepthShare, (g + 1) * kDepthShare); thread t adds its elements g * kDepthShare + j * kBlock + t in the order of
+// j (consecutive lanes read consecutive floats of a packed z); lanes, waves and workgroups are combined as ns_image_sqerr's are
+// (block_sum_ordered, partial[g], the same second launch), so every addition is fixed by (R, N) alone.
+constexpr int kDepthShare = NS_DEPTH_SQERR_SHARE;
+static_assert(kDepthShare % kBlock == 0, "a whole number of elements per thread");
+
+__global__ void __launch_bounds__(kBlock)
+depth_sqerr_kernel(const float* __restrict__ z, int64_t stride, const float* __restrict__ ref, uint32_t total, uint32_t N,
+                   double* __restrict__ partial) {
+  __shared__ double wave_sums[kBlock / 64];
+  const uint32_t base = blockIdx.x * static_cast<uint32_t>(kDepthShare) + threadIdx.x;   // below 2^31 + kDepthShare
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < kDepthShare / kBlock; ++j) {
+    const uint32_t e = base + j * kBlock;
+    if (e < total) {
+      const uint32_t r = e / N, k = e - r * N;
+      const double d = static_cast<double>(z[static_cast<int64_t>(r) * stride + k] - ref[r]);   // one fp32 subtraction, as mse_loss
+      acc += d * d;                                                                            // exact in double
+    }
+  }
+  const double s = block_sum_ordered(acc, wave_sums);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
 // ---- frame SSIM on the device (ns_image_ssim) -----------------------------------------------------------------------
 // Wang et al. 2004 over every 11 x 11 window that lies wholly inside the frame, per colour channel, weights g(i) g(j).
 // Workgroup b owns the kSsimTileH x kSsimTileW tile of window origins at (b / tiles_x, b % tiles_x) * tile, thread t the
@@ -603,6 +630,35 @@ int ns_image_sqerr(const ns_ray_dataset* ds, int image_idx, int row0, int row1, 
   hipStream_t s = ns::as_stream(stream);
   image_sqerr_kernel<<<groups, kBlock, 0, s>>>(*ds, image_idx, row0 * ds->W, n, rgb_dev,
                                                rgb_stride == 0 ? 3 : static_cast<int>(rgb_stride), partial);
+  NS_LAUNCH_CHECK();
+  image_sqerr_combine_kernel<<<1, kBlock, 0, s>>>(partial, groups, sum_dev);
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+// R * N in [1, 2^31): the flat element index and its division by N are 32-bit in the kernel
+static bool depth_sqerr_shape_ok(int64_t R, int N) {
+  return R >= 1 && N >= 1 && R <= ((int64_t(1) << 31) - 1) / N;
+}
+
+int64_t ns_depth_sqerr_workspace_bytes(int64_t R, int N) {
+  if (!depth_sqerr_shape_ok(R, N)) return 0;
+  const int64_t groups = (R * N + kDepthShare - 1) / kDepthShare;
+  return (groups * static_cast<int64_t>(sizeof(double)) + 255) / 256 * 256;
+}
+
+int ns_depth_sqerr(const float* z_dev, int64_t z_row_stride, const float* ref_dev, int64_t R, int N, double* sum_dev,
+                   void* workspace_dev, void* stream) {
+  NS_REQUIRE(z_dev && ref_dev && sum_dev && workspace_dev, "null pointer");
+  NS_REQUIRE(R >= 1 && N >= 1, "R and N must be at least 1");
+  NS_REQUIRE(depth_sqerr_shape_ok(R, N), "R * N must be below 2^31");
+  NS_REQUIRE(z_row_stride == 0 || z_row_stride >= N, "z_row_stride is 0 (packed) or at least N floats");
+  const int64_t total = R * N;
+  const int groups = static_cast<int>((total + kDepthShare - 1) / kDepthShare);
+  double* partial = static_cast<double*>(workspace_dev);
+  hipStream_t s = ns::as_stream(stream);
+  depth_sqerr_kernel<<<groups, kBlock, 0, s>>>(z_dev, z_row_stride == 0 ? N : z_row_stride, ref_dev,
+                                               static_cast<uint32_t>(total), static_cast<uint32_t>(N), partial);
   NS_LAUNCH_CHECK();
   image_sqerr_combine_kernel<<<1, kBlock, 0, s>>>(partial, groups, sum_dev);
   NS_LAUNCH_CHECK();

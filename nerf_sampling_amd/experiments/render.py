@@ -50,6 +50,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--device-ssim", "device_ssim", is_flag=True, default=False,
               help="(not in the reference) --device-psnr, and the SSIM of every test view beside it (ns_image_ssim, "
                    "Trainer(device_ssim=True)): ssim.txt next to psnr.txt.")
+@click.option("--device-depth", "device_depth", is_flag=True, default=False,
+              help="(not in the reference) --device-psnr, and per test view the MSE of the DepthNet's placed samples and of its "
+                   "own depth against the field's max-weight depth (ns_depth_sqerr, Trainer(device_depth=True)): -nc's MSE "
+                   "without its host copies, in depth.txt next to psnr.txt.  Not with -nf.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -60,10 +64,12 @@ def main(**kw):
     k.update(single_image=kw["single_image"], single_ray=kw["single_ray"], save_scene_data=kw["save_scene_data"],
              i_print=kw["i_print"], compare_nerf=kw["nerf_compare"], use_nerf_max_pts=kw["nerf_max"],
              use_full_nerf=kw["nerf_full"], render_only=True, render_test=True)
-    if kw["device_psnr"] or kw["device_ssim"]:
+    if kw["device_psnr"] or kw["device_ssim"] or kw["device_depth"]:
         k["device_eval"] = True
     if kw["device_ssim"]:
         k["device_ssim"] = True
+    if kw["device_depth"]:
+        k["device_depth"] = True
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -50,6 +50,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--device-ssim", "device_ssim", is_flag=True, default=False,
               help="--device-eval, and the SSIM of the test views beside their PSNR (ns_image_ssim, Trainer(device_ssim=True) / "
                    "FieldFitter.fit(test_ssim=True)): ssim.txt next to every psnr.txt.")
+@click.option("--device-depth", "device_depth", is_flag=True, default=False,
+              help="--device-eval, and the MSE of the DepthNet's placed samples and of its own depth against the field's "
+                   "max-weight depth on the test views (ns_depth_sqerr, Trainer(device_depth=True)): depth.txt next to every "
+                   "psnr.txt.  Not with --fit-field, which has no DepthNet.")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -75,11 +79,15 @@ def main(**kw):
         k["fused_step"] = True
     if kw["device_batches"]:
         k["device_batches"] = kw["device_batches"]
-    if kw["device_eval"] or kw["device_ssim"]:
+    if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"]:
         k["device_eval"] = True
     if kw["device_ssim"]:
         k["device_ssim"] = True
+    if kw["device_depth"]:
+        k["device_depth"] = True
     if kw["fit_field"]:
+        if kw["device_depth"]:
+            raise click.UsageError("--device-depth scores a DepthNet's depth; --fit-field trains none")
         k.update(ft_path=None)
         return fit_field(load_obj_from_config(cfg=config), kw["iters"], gemm_engine=kw["gemm_engine"])
     trainer = load_obj_from_config(cfg=config)

@@ -384,33 +384,77 @@ def _write_ssim_txt(savedir, ssims, avg):
         file.write(format_ssim_txt(ssims, avg))
 
 
-def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_frames=False, ssim=False):
+def format_depth_txt(sample_mses, avg_sample_mse, mean_mses, avg_mean_mse) -> str:
+    """depth.txt of a set of views, psnr.txt's layout: one "NNN.png, MSE: x, mean MSE: y" line per view -- x the reference's
+    compare_nerf ``MSE:`` (nerf_utils.py:311-317), y the DepthNet's own depth against the field's -- then the averages"""
+    lines = [f"{i:03d}.png, MSE: {s}, mean MSE: {m}\n" for i, (s, m) in enumerate(zip(sample_mses, mean_mses))]
+    return "".join(lines) + f"Avg of {len(lines)} images:\nMSE: {avg_sample_mse}\nmean MSE: {avg_mean_mse}\n"
+
+
+def _write_depth_txt(savedir, sample_mses, avg_sample_mse, mean_mses, avg_mean_mse):
+    os.makedirs(savedir, exist_ok=True)
+    with open(os.path.join(savedir, "depth.txt"), "a") as file:
+        file.write(format_depth_txt(sample_mses, avg_sample_mse, mean_mses, avg_mean_mse))
+
+
+def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_frames=False, ssim=False, depth=False,
+                field_depths=None, return_depths=False):
     """The loop of evaluate_views over any whole-frame renderer: ``render_frame(c2w [3,4], workspace)`` returns the view's rgb
     [H*W,3] on the device (or the [:, :3] view of a [H*W,4] shard), which is scored against image ``image_ids[k]`` into slot
     k of one float64 device array (DeviceRayDataset.image_sqerr).  The workspace is this call's own, and the sums are read back
     once, after the last frame.  -> (psnr per view [n] float64, their mean[, the frames]).  ``ssim``: every frame is also scored
     by DeviceRayDataset.image_ssim into slot k of a second row of that array (still one read-back), ``savedir`` also gets
-    ssim.txt -> (psnr per view, their mean, ssim per view [n] float64, their mean[, the frames])."""
+    ssim.txt -> (psnr per view, their mean, ssim per view [n] float64, their mean[, the frames]).
+
+    ``depth``: ``render_frame`` returns (rgb, z [R,N], mean [R] or [R,1], field_depth) instead -- the samples the frame was
+    composited from, the DepthNet's own depth of the same rays, and a function without arguments that renders the field's
+    max-weight depth max_z [R,1] of those rays.  ops.depth_sqerr scores z and mean against max_z into slot k of two further
+    rows of the array (still one read-back): sample_mse = mean (max_z - z_k)^2 over all placed samples, the reference's
+    compare_nerf ``MSE:`` (nerf_utils.py:311-317), and mean_mse = mean (max_z - mean)^2, the training's depth_net_loss on
+    held-out rays.  ``field_depths``: max_z of every view from an earlier call (``return_depths``); ``field_depth`` is then
+    not called.  ``savedir`` also gets depth.txt.  The result grows in this order:
+    (psnrs, avg[, ssims, avg_ssim][, sample_mses, avg_sample_mse, mean_mses, avg_mean_mse][, frames][, depths]) -- ``depths``
+    (``return_depths``): per view (z, mean, max_z) as device tensors."""
     import numpy as np
 
     ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
     if len(ids) == 0 or len(ids) != len(poses):
         raise ValueError(f"{len(ids)} image ids for {len(poses)} poses (at least one view)")
+    if not depth and (field_depths is not None or return_depths):
+        raise ValueError("field_depths / return_depths belong to the depth report: depth=True")
+    if field_depths is not None and len(field_depths) != len(ids):
+        raise ValueError(f"{len(field_depths)} field depths for {len(ids)} views")
     workspace = ops.RenderWorkspace()
-    sums = torch.empty((2, len(ids)) if ssim else (len(ids),), dtype=torch.float64, device=dataset.device)
-    sq_sums, ssim_sums = (sums[0], sums[1]) if ssim else (sums, None)
+    rows = 1 + int(bool(ssim)) + 2 * int(bool(depth))
+    sums = torch.empty((rows, len(ids)) if rows > 1 else (len(ids),), dtype=torch.float64, device=dataset.device)
+    sq_sums = sums[0] if rows > 1 else sums
+    ssim_sums = sums[1] if ssim else None
+    sample_sums, mean_sums = (sums[rows - 2], sums[rows - 1]) if depth else (None, None)
     ssim_ws = (torch.empty((dataset.ssim_workspace_bytes(),), dtype=torch.uint8, device=dataset.device) if ssim else None)
-    frames = []
+    depth_ws, n_placed = None, 0
+    frames, depths = [], []
     with torch.no_grad():
         for k, (img, c2w) in enumerate(zip(ids, poses)):
             rgb = render_frame(c2w[:3, :4], workspace)
+            if depth:
+                rgb, z, mean, field_depth = rgb
             dataset.image_sqerr(img, rgb, out=sq_sums, slot=k)
             if ssim:
                 dataset.image_ssim(img, rgb, out=ssim_sums, slot=k, workspace=ssim_ws)
+            if depth:
+                max_z = field_depths[k] if field_depths is not None else field_depth()
+                if depth_ws is None:                                           # every view has the same R and N
+                    n_placed = z.numel()
+                    depth_ws = torch.empty((ops.depth_sqerr_workspace_bytes(z.shape[0], z.numel() // z.shape[0]),),
+                                           dtype=torch.uint8, device=dataset.device)
+                ops.depth_sqerr(z, max_z, out=sample_sums, slot=k, workspace=depth_ws)
+                ops.depth_sqerr(mean, max_z, out=mean_sums, slot=k, workspace=depth_ws)
+                if return_depths:
+                    depths.append((z, mean, max_z))
             if return_frames:
                 frames.append(rgb)
     sums = sums.cpu().numpy()                                                 # the one device-to-host copy
-    psnrs = dataset.psnr_from_sqerr(sums[0] if ssim else sums, 3 * dataset.H * dataset.W)
+    psnrs = dataset.psnr_from_sqerr(sums[0] if rows > 1 else sums, 3 * dataset.H * dataset.W)
     avg = float(np.mean(psnrs))                                               # the mean of the dB values, as the reference's
     if savedir is not None:
         _write_psnr_txt(savedir, psnrs, avg)
@@ -421,7 +465,16 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
         if savedir is not None:
             _write_ssim_txt(savedir, ssims, avg_ssim)
         out += (ssims, avg_ssim)
-    return out + (frames,) if return_frames else out
+    if depth:
+        sample_mses = ops.mse_from_sqerr(sums[rows - 2], n_placed)
+        mean_mses = ops.mse_from_sqerr(sums[rows - 1], dataset.H * dataset.W)
+        avg_sample, avg_mean = float(np.mean(sample_mses)), float(np.mean(mean_mses))
+        if savedir is not None:
+            _write_depth_txt(savedir, sample_mses, avg_sample, mean_mses, avg_mean)
+        out += (sample_mses, avg_sample, mean_mses, avg_mean)
+    if return_frames:
+        out += (frames,)
+    return out + (depths,) if return_depths else out
 
 
 def hierarchical_frame_renderer(network_fn, network_fine, H, W, K, N_samples, N_importance, lindisp, white_bkgd, near, far,
@@ -464,7 +517,50 @@ def _dataset_targets_host(dataset, image_ids):
 _evaluate_fallback_warned = False
 
 
-def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=None, return_frames=False, ssim=False):
+def _depth_frame_renderer(kw, trainer, net, H, W, K, dev):
+    """``render_frame`` of score_views(depth=True): the view's rays are generated once and feed the DepthNet one-call render
+    (evaluate_views' own, plus the z extra), ops.depthnet_forward on the handle that render used, and -- when asked -- the
+    field's max-weight depth through ops.render_rays_hierarchical with the trainer's N_samples / N_importance / lindisp /
+    bounds, in a workspace of its own.  The draws of gaussian placement and of ``perturb`` > 0 come from generators of the
+    evaluation's own."""
+    dn = kw["depth_network"]
+    coarse, fine = kw["network_fn"], kw.get("network_fine")
+    n_coarse, n_importance, perturb = int(kw["N_samples"]), int(trainer.N_importance), float(kw.get("perturb", 0.0))
+    hier_ws = ops.RenderWorkspace()
+    gens = {}
+
+    def generator(name):
+        if name not in gens:
+            gens[name] = torch.Generator(device=dev)
+            gens[name].manual_seed(0)
+        return gens[name]
+
+    def render_frame(c2w, workspace):
+        rays = ops.get_rays(H, W, K, c2w, device=dev)
+        noise = None
+        if trainer.sampling_mode == "gaussian" and int(trainer.n_depth_samples) > 1:
+            noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=generator("placement"))
+        out = _depthnet_one_call(dn, net, trainer, rays=rays, extras=("z",), device=dev, noise=noise, workspace=workspace)
+        dn_w = ops.psnr_guard_handles(dn, net, mode=trainer.sampling_mode, n_samples=trainer.n_depth_samples)[0]
+        mean = ops.depthnet_forward(dn_w, rays[0], rays[1], dn.near, dn.far, float(dn.sphere_radius.reshape(-1)[0]))
+
+        def field_depth():
+            # the chain's draws, in _vanilla_one_call's order
+            t_rand = torch.rand([H * W, n_coarse], device=dev, generator=generator("field")) if perturb > 0.0 else None
+            u = torch.rand([H * W, n_importance], device=dev, generator=generator("field")) if perturb != 0.0 else None
+            return ops.render_rays_hierarchical(coarse.packed(), fine.packed() if fine is not None else None, rays=rays,
+                                                n_coarse=n_coarse, n_importance=n_importance,
+                                                lindisp=bool(kw.get("lindisp", False)), white_bkgd=bool(kw["white_bkgd"]),
+                                                near=float(kw["near"]), far=float(kw["far"]), t_rand=t_rand, u=u, extras=False,
+                                                device=dev, max_sample=True, workspace=hier_ws)["max_z"]
+
+        return out["rgb"], out["z"], mean, field_depth
+
+    return render_frame
+
+
+def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=None, return_frames=False, ssim=False,
+                   depth=False, field_depths=None, return_depths=False):
     """The device counterpart of render_path(gt_imgs=...): the PSNR of view ``poses[k]`` against image ``image_ids[k]`` of
     ``dataset`` (a ray_batches.DeviceRayDataset, whose images are already on the device), nothing per pixel leaving it.  Every
     view is rendered from its camera in ONE call without per-sample outputs -- ops.render_rays_depthnet with the choices of
@@ -474,7 +570,18 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
     do not take falls back to render_path (PNGs included), with one warning.  The reports of compare_nerf / use_nerf_max_pts are
     more than a PSNR: ValueError.  ``ssim``: every view is also scored by ns_image_ssim -- the frames render_path returned are
     uploaded for it on the fallback -- and the result is (psnr per view, their mean, ssim per view, their mean[, frames]), with
-    ssim.txt beside psnr.txt."""
+    ssim.txt beside psnr.txt.
+
+    ``depth`` (the DepthNet frame only): every view's placed samples z [R,N] and the DepthNet's own depth are also scored
+    against the frozen field's max-weight fine sample max_z of the same rays (ns_depth_sqerr; score_views states the two
+    numbers): the reference's compare_nerf ``MSE:`` without compare_nerf's per-sample host copies.  The view's rays are
+    generated once and feed the frame's render, ops.depthnet_forward and ops.render_rays_hierarchical(max_sample=True); the
+    PSNRs and SSIMs are those of depth=False bit for bit.  ``field_depths``: the max_z tensors of an earlier call
+    (``return_depths``), one per view, valid while the field and its sampling stay as they were -- no hierarchical render is
+    launched then.  The result is (psnrs, avg[, ssims, avg_ssim][, sample_mses, avg_sample_mse, mean_mses, avg_mean_mse]
+    [, frames][, depths]), ``depths`` per view (z, mean, max_z) on the device, and ``savedir`` gets depth.txt
+    (format_depth_txt).  The depth report has no render_path fallback: a configuration that is not eligible for both
+    one-call renderers, or use_full_nerf (no DepthNet in that frame), raises ValueError."""
     global _evaluate_fallback_warned
     import numpy as np
 
@@ -482,11 +589,32 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
     trainer = kw["trainer"]
     if trainer.compare_nerf or trainer.use_nerf_max_pts:
         raise ValueError("evaluate_views reports a PSNR only: compare_nerf / use_nerf_max_pts go through render_path")
+    if not depth and (field_depths is not None or return_depths):
+        raise ValueError("field_depths / return_depths belong to the depth report: depth=True")
+    if depth and trainer.use_full_nerf:
+        raise ValueError("evaluate_views(depth=True): a use_full_nerf frame has no DepthNet whose depth could be scored")
     H, W = int(hwf[0]), int(hwf[1])
     if (H, W) != (dataset.H, dataset.W):
         raise ValueError(f"hwf says {H} x {W}, the dataset's images are {dataset.H} x {dataset.W}")
     dev = dataset.device
     net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
+    if depth:
+        with torch.no_grad():
+            if not (bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)):
+                why = "it needs view directions and ndc=False"
+            elif not _one_call_eligible(kw.get("depth_network"), net, kw["network_query_fn"], trainer, True):
+                why = "the frame is not one of the one-call DepthNet renderer's"
+            elif not _hier_one_call_eligible(kw["network_fn"], kw.get("network_fine"), kw["network_query_fn"], trainer, True,
+                                             kw["N_samples"], kw.get("raw_noise_std", 0.0), False):
+                why = ("the field's depth is not one of the one-call hierarchical renderer's (N_importance > 0, N_samples >= 3, "
+                       "no raw noise, this package's NeRF modules and operators)")
+            else:
+                why = None
+        if why is not None:
+            raise ValueError(f"evaluate_views(depth=True): {why}; the depth report has no render_path fallback")
+        render_frame = _depth_frame_renderer(kw, trainer, net, H, W, K, dev)
+        return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames, ssim=ssim,
+                           depth=True, field_depths=field_depths, return_depths=return_depths)
     with torch.no_grad():
         basics = bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)
         if trainer.use_full_nerf:

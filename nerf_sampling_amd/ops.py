@@ -195,6 +195,65 @@ def ray_batch_draw(dataset, B: int, step: int = 0, window=None, scope: str = "pe
     return dataset.draw(B, step=step, window=window, scope=scope, seed=seed, **kw)
 
 
+# ---- placed samples against the field's depth (not an operator of the reference: nerf_utils.py:311-317 on the host) ----
+def depth_sqerr_workspace_bytes(R: int, N: int) -> int:
+    """ns_depth_sqerr_workspace_bytes: the partial sums ``depth_sqerr`` needs for R rays of N samples (0: a shape it refuses)"""
+    return int(_lib.load().ns_depth_sqerr_workspace_bytes(int(R), int(N)))
+
+
+def depth_sqerr(z, ref, out=None, slot: int = 0, workspace=None):
+    """ns_depth_sqerr: sum over rays and samples of (double)(fl32(z[r, k] - ref[r]))^2, in double on the device -- the numerator
+    of render_path's ``MSE:`` under compare_nerf (mse_loss(max_z_vals, depth_net_z_vals)) with ``z`` the placed samples, and of
+    the training's depth_net_loss with ``z`` the DepthNet's own depth.  ``z``: fp32 [R,N] or [R] on the device, contiguous or a
+    column slice with unit inner stride; ``ref``: fp32 [R] or [R,1] on the same device.  Returns a 1-element float64 device
+    tensor, or writes ``out[slot]`` (``out``: a contiguous 1-d float64 device tensor) and returns ``out``.  ``workspace``: a
+    contiguous 8-byte-aligned device tensor of at least ``depth_sqerr_workspace_bytes(R, N)`` bytes (None: allocated for the
+    call).  The same bits on every call; a NaN anywhere makes the sum NaN.  Nothing is read back: see ``mse_from_sqerr``.  What
+    is wrong with the arguments raises ValueError before any launch."""
+    if not (isinstance(z, Tensor) and z.is_cuda and z.dtype == torch.float32 and z.dim() in (1, 2)):
+        raise ValueError("z: a float32 device tensor [R,N] or [R]")
+    R, N = int(z.shape[0]), (int(z.shape[1]) if z.dim() == 2 else 1)
+    if R < 1 or N < 1:
+        raise ValueError(f"z: at least one ray and one sample, got {tuple(z.shape)}")
+    if R * N >= 2 ** 31:
+        raise ValueError(f"z: R * N = {R * N} is not below 2^31")
+    if z.dim() == 1:
+        stride = 1 if R == 1 else int(z.stride(0))              # one column of a wider buffer: its row stride
+        if stride < 1:
+            raise ValueError("z: a vector [R] with a positive stride")
+    else:
+        stride = N if R == 1 else int(z.stride(0))
+        if (N > 1 and z.stride(1) != 1) or stride < N:
+            raise ValueError("z: contiguous [R,N], or a column slice of a wider contiguous buffer (unit inner stride)")
+    if not (isinstance(ref, Tensor) and ref.is_cuda and ref.device == z.device and ref.dtype == torch.float32
+            and tuple(ref.shape) in ((R,), (R, 1)) and ref.is_contiguous()):
+        raise ValueError(f"ref: a contiguous float32 tensor of shape ({R},) or ({R}, 1) on z's device")
+    if out is None:
+        out, slot = torch.empty((1,), dtype=torch.float64, device=z.device), 0
+    elif not (isinstance(out, Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError("out: a contiguous 1-d float64 device tensor")
+    slot = int(slot)
+    if not 0 <= slot < out.numel():
+        raise ValueError(f"slot {slot} out of range [0, {out.numel()})")
+    need = depth_sqerr_workspace_bytes(R, N)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=z.device)
+    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.is_contiguous()
+              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
+        raise ValueError(f"workspace: a contiguous 8-byte-aligned device tensor of at least {need} bytes")
+    check(_lib.load().ns_depth_sqerr(_ptr(z), stride, _ptr(ref), R, N, C.c_void_p(out.data_ptr() + 8 * slot), _ptr(workspace),
+                                     _stream(z.device)), "ns_depth_sqerr")
+    return out
+
+
+def mse_from_sqerr(sums, n_values):
+    """sum / n_values in float64, on the host: the mean squared error of ``depth_sqerr`` sums ``sums`` (a device or host tensor,
+    an array or a number) over ``n_values`` = R * N values each.  A device tensor is read back here, once."""
+    if hasattr(sums, "detach"):
+        sums = sums.detach().cpu().numpy()
+    return np.asarray(sums, dtype=np.float64) / np.asarray(n_values, dtype=np.float64)
+
+
 # ---- a2 -------------------------------------------------------------------------------------------
 def sphere_intersect(o: Tensor, d: Tensor, radius: float) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()

@@ -22,7 +22,14 @@ from .run_nerf_helpers import Embedder, NeRF
 
 
 class Trainer:
-    """Attribute bag with the reference's constructor arguments and defaults (Trainer.py:19-130)."""
+    """Attribute bag with the reference's constructor arguments and defaults (Trainer.py:19-130).
+
+    Not in the reference: ``hip_graph`` (default on) and, off by default, ``device_batches`` / ``batch_seed`` and the device
+    evaluation of held-out views -- ``device_eval`` (psnr.txt scored on the device, i_testset honoured by train()), with it
+    ``device_ssim`` (ssim.txt) and ``device_depth`` (depth.txt: per view the MSE of the DepthNet's placed samples and of its
+    own depth against the field's max-weight depth, "[TRAIN] Iter: i test depth MSE: x mean MSE: y"; the field's depth maps
+    of the i_test views are rendered once while train_depth_net_only keeps the field frozen and the test perturb is 0).
+    Both need device_eval."""
 
     def __init__(self, dataset_type, basedir, expname, no_batching, datadir, device="cpu", render_test=False,
                  config_path=None, N_rand=32 * 32 * 4, render_only=False, chunk=1024 * 32, render_factor=0,
@@ -34,7 +41,7 @@ class Trainer:
                  train_depth_net_only: bool = False, trial=None, single_image=False, single_ray=False,
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
                  hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False,
-                 device_ssim: bool = False):
+                 device_ssim: bool = False, device_depth: bool = False):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -61,6 +68,15 @@ class Trainer:
         self.device_ssim = bool(device_ssim)
         if self.device_ssim and not self.device_eval:
             raise ValueError("device_ssim scores the frames of the device evaluation: it needs device_eval=True")
+        # device_depth (not in the reference; default off): the device evaluation also reports, per view, the MSE of the placed
+        # samples and of the DepthNet's own depth against the field's max-weight depth (ns_depth_sqerr; the reference's
+        # compare_nerf "MSE:", nerf_utils.py:311-317, and depth_net_loss on held-out rays) -- depth.txt beside each psnr.txt.
+        # With train_depth_net_only and a test perturb of 0 the field's depth maps of the i_test views cannot change: train()
+        # keeps them from its first evaluation (_field_depths); in any other case they are rendered at every evaluation.
+        self.device_depth = bool(device_depth)
+        if self.device_depth and not self.device_eval:
+            raise ValueError("device_depth scores the depths of the device evaluation: it needs device_eval=True")
+        self._field_depths = None
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -170,7 +186,7 @@ class Trainer:
                 if ds is None:          # called on its own: the test views alone go to the device
                     ds, ids = ops.ray_dataset(np.asarray(images, dtype=np.float32), render_poses, self.K, [0]), range(len(i_test))
                 scores = nerf_utils.evaluate_views(ds, ids, render_poses, hwf, self.K, render_kwargs_test,
-                                                   savedir=testsavedir, ssim=self.device_ssim)
+                                                   savedir=testsavedir, ssim=self.device_ssim, depth=self.device_depth)
                 return scores[1]
             _, _, avg_test_psnr = nerf_utils.render_path(
                 render_poses, hwf, self.K, self.chunk, render_kwargs_test, step=self.global_step,
@@ -179,11 +195,23 @@ class Trainer:
 
     def evaluate_testset(self, i, i_test, test_poses, hwf, render_kwargs_test):
         """device_eval: the i_test views into {basedir}/{expname}/testset_{i:06d}/psnr.txt (Trainer.log, Trainer.py:289-316,
-        without its PNGs) -> their average PSNR; under device_ssim ssim.txt too -> (average PSNR, average SSIM)."""
+        without its PNGs) -> their average PSNR; under device_ssim ssim.txt too -> (average PSNR, average SSIM); under
+        device_depth depth.txt too, and (average sample MSE, average mean MSE) as the last element of the tuple.  While the
+        field is frozen and the test perturb is 0 the field's depth maps of the first call serve the later ones."""
         savedir = os.path.join(self.basedir, self.expname, "testset_{:06d}".format(i))
+        if not self.device_depth:
+            scores = nerf_utils.evaluate_views(self._ray_dataset, i_test, test_poses, hwf, self.K, render_kwargs_test,
+                                               savedir=savedir, ssim=self.device_ssim)
+            return (scores[1], scores[3]) if self.device_ssim else scores[1]
+        keep = bool(self.train_depth_net_only) and float(render_kwargs_test.get("perturb", 0.0)) == 0.0
         scores = nerf_utils.evaluate_views(self._ray_dataset, i_test, test_poses, hwf, self.K, render_kwargs_test,
-                                           savedir=savedir, ssim=self.device_ssim)
-        return (scores[1], scores[3]) if self.device_ssim else scores[1]
+                                           savedir=savedir, ssim=self.device_ssim, depth=True,
+                                           field_depths=self._field_depths if keep else None, return_depths=keep)
+        if keep and self._field_depths is None:
+            self._field_depths = [max_z for _z, _mean, max_z in scores[-1]]
+        averages = scores[1:4 if self.device_ssim else 2:2]           # (PSNR[, SSIM]): every second element is an average
+        _sample_mses, avg_sample_mse, _mean_mses, avg_mean_mse = scores[len(averages) * 2:len(averages) * 2 + 4]
+        return averages + ((avg_sample_mse, avg_mean_mse),)
 
     def train(self, N_iters=200000 + 1):
         """Trainer.train (Trainer.py:712-787): load data, build / reload the networks; render_only: render the test
@@ -236,6 +264,10 @@ class Trainer:
             if test_poses is not None and self.i_testset and i % self.i_testset == 0 and i > 0:
                 with torch.no_grad():
                     avg = self.evaluate_testset(i, i_test, test_poses, hwf, render_kwargs_test)
+                if self.device_depth:
+                    avg, (avg_sample_mse, avg_mean_mse) = avg[:-1], avg[-1]
+                    avg = avg if self.device_ssim else avg[0]
+                    print(f"[TRAIN] Iter: {i} test depth MSE: {avg_sample_mse} mean MSE: {avg_mean_mse}")
                 if self.device_ssim:
                     avg, avg_ssim = avg
                     print(f"[TRAIN] Iter: {i} test SSIM: {avg_ssim}")

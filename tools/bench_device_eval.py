@@ -2,9 +2,11 @@
 a PNG -- against nerf_utils.evaluate_views -- the frame rendered in one call, scored on the device by ns_image_sqerr -- on the
 fitted scene at 800 x 800 x 64, bf16 field with the PSNR guard; and the scoring launch alone at 800 x 800.  Each figure is the
 median of three alternations on one box, with the spread of the first path beside it.  --ssim: evaluate_views without and
-with ssim=True instead (the host path is not run), and ns_image_ssim alone beside ns_image_sqerr.
+with ssim=True instead (the host path is not run), and ns_image_ssim alone beside ns_image_sqerr.  --depth: evaluate_views
+without depth, with depth=True and the field's depth maps rendered afresh, and with them passed in as field_depths, the three
+alternating; then ns_depth_sqerr alone at (640 000, 64) and (640 000, 1).
 
-    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim]
+    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim | --depth]
 """
 import argparse
 import os
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--alternations", type=int, default=3)
     ap.add_argument("--ssim", action="store_true", help="evaluate_views with ssim=True against without; ns_image_ssim alone")
+    ap.add_argument("--depth", action="store_true",
+                    help="evaluate_views without depth, with depth=True and fresh field depths, with cached ones; ns_depth_sqerr alone")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _coarse, fine, dn, _params = bench.build_modules("shapes_fit", dev)
@@ -70,6 +74,8 @@ def main():
             torch.cuda.synchronize()
             return 1e3 * (time.perf_counter() - t0) / a.views, float(psnr)
 
+    if a.depth:
+        return bench_depth(a, dev, ds, ids, poses, [H, W, focal], K, kw, timed)
     # the first path of the pair is the one the second is measured against
     first, second = ((device_path, device_ssim_path) if a.ssim else (host_path, device_path))
     timed(first), timed(second)                              # warm-up: pinned buffers, packed streams, workspaces
@@ -115,6 +121,45 @@ def main():
             torch.cuda.synchronize()
             per.append(1e3 * e0.elapsed_time(e1_) / reps)
         print(f"  ns_image_ssim alone       {statistics.median(per):8.2f} us per {H} x {W} frame   (spread {max(per) - min(per):.2f})")
+
+
+def bench_depth(a, dev, ds, ids, poses, hwf, K, kw, timed):
+    """--depth: the three evaluations in alternation, then ns_depth_sqerr alone (both launches) on the placed samples of an
+    800 x 800 x 64 frame and on a depth vector of its rays"""
+    field = nerf_utils.evaluate_views(ds, ids, poses, hwf, K, kw, depth=True, return_depths=True)[-1]
+    field = [max_z for _z, _mean, max_z in field]
+    paths = [("evaluate_views", lambda d: nerf_utils.evaluate_views(ds, ids, poses, hwf, K, kw, savedir=d)[1]),
+             ("  depth=True, fresh field", lambda d: nerf_utils.evaluate_views(ds, ids, poses, hwf, K, kw, savedir=d, depth=True)[3]),
+             ("  depth=True, cached field", lambda d: nerf_utils.evaluate_views(ds, ids, poses, hwf, K, kw, savedir=d, depth=True,
+                                                                              field_depths=field)[3])]
+    for _name, fn in paths:
+        timed(fn)                                            # warm-up: packed streams, workspaces
+    runs = [[] for _ in paths]
+    for _ in range(a.alternations):
+        for r, (_name, fn) in zip(runs, paths):
+            r.append(timed(fn))
+    print(f"{hwf[0]} x {hwf[1]} x {a.samples}, bf16 + PSNR guard, {a.views} views; ms per view, median of {a.alternations} alternations")
+    for (name, _fn), r, what in zip(paths, runs, ("avg PSNR", "avg sample MSE", "avg sample MSE")):
+        t = [ms for ms, _ in r]
+        print(f"  {name:<28s} {statistics.median(t):8.2f}   (spread {max(t) - min(t):.2f})   {what} {r[-1][1]:.6g}")
+    out = torch.empty((1,), dtype=torch.float64, device=dev)
+    R = 640000
+    ref = torch.rand((R,), device=dev) * 4.0 + 2.0
+    for N in (64, 1):
+        z = torch.rand((R, N), device=dev) * 4.0 + 2.0
+        ws = torch.empty((ops.depth_sqerr_workspace_bytes(R, N),), dtype=torch.uint8, device=dev)
+        for _ in range(10):
+            ops.depth_sqerr(z, ref, out=out, workspace=ws)
+        reps, per = 200, []
+        for _ in range(a.alternations):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                ops.depth_sqerr(z, ref, out=out, workspace=ws)
+            e1.record()
+            torch.cuda.synchronize()
+            per.append(1e3 * e0.elapsed_time(e1) / reps)
+        print(f"  ns_depth_sqerr alone ({R}, {N:2d}) {statistics.median(per):8.2f} us   (spread {max(per) - min(per):.2f})")
 
 
 if __name__ == "__main__":
