@@ -179,6 +179,38 @@ int64_t ns_depth_sqerr_workspace_bytes(int64_t R, int N);
 int ns_depth_sqerr(const float* z_dev, int64_t z_row_stride, const float* ref_dev, int64_t R, int N, double* sum_dev,
                    void* workspace_dev, void* stream);
 
+/* ---- the scene's point cloud  (experiments/plot.py:13-22: all_pts[all_weights >= t] of the per-sample points and weights
+ * render_path(save_scene_data=True) collects; utils.py:36-43 get_min_indices) ----  An ordered stream compaction.  The flat
+ * element e = r * N + k, r in [0, R), k in [0, N), is KEPT iff w_dev[r * w_row_stride + k] >= min_weight: a NaN weight is
+ * dropped, -0.0 >= 0.0 keeps.  A kept element's record index is i = *count_dev (its value before the call) + the number of
+ * kept elements with a smaller e: records are ray-major, sample-minor and call after call, the order of
+ * torch.cat(all_pts)[torch.cat(all_weights) >= t].  The record is written iff 0 <= i < capacity -- nothing is ever written at
+ * or beyond capacity --
+ *   pts_out[i] = o[r] + d[r] * z_dev[r * z_row_stride + k]   (multiply and add rounded separately: ns_points_along_rays' bits),
+ *   w_out[i]   = the weight,
+ *   rgb_out[i] = rgb_dev[r * rgb_stride + 0..2], the colour of the RAY, when rgb_out is given (rgb_dev is then required; rgb_dev
+ *                alone is ignored),
+ * and afterwards *count_dev has grown by the number of ALL kept elements, those that did not fit included: one 8-byte readback
+ * at the very end tells the caller the capacity it would have needed.  *count_dev must not be negative.  o, d are [R,3] packed;
+ * the strides are in floats, 0 = packed (N, N, 3), otherwise >= N, >= N, >= 3 (column slices of wider buffers, the interleaved
+ * [R,4] shard).  R == 0 leaves everything untouched; capacity == 0 (the outputs may then be NULL) is a pure count.
+ * Three launches on `stream`, no atomics: (1) workgroup g counts the kept elements among its NS_CLOUD_SHARE flat elements from
+ * g * NS_CLOUD_SHARE on (thread t takes g * NS_CLOUD_SHARE + j * 256 + t) into workspace_dev (one int64 per share,
+ * ns_cloud_workspace_bytes(R, N) bytes); (2) ONE workgroup reads *count_dev, turns the counts into absolute record indices in
+ * the order of g and writes *count_dev + total back; (3) every workgroup evaluates the predicate again and places its kept
+ * elements: the share's index + the kept elements of its earlier steps j and waves (LDS) + the kept lanes below (a 64-bit
+ * ballot and a popcount).  No workgroup waits on another's memory, and the result depends on the inputs alone.  Checked before
+ * any launch (NS_E_INVALID): R < 0, N < 1, R * N >= 2^31 (the flat index and its division by N are 32-bit), a negative stride
+ * or one below the packed one, a negative capacity, capacity > 0 without pts_out / w_out, rgb_out without rgb_dev, count_dev
+ * NULL, count_dev / workspace_dev not 8-byte aligned, and for R > 0 o / d / z / w / workspace_dev NULL.
+ * ns_cloud_workspace_bytes is 0 for a shape that would be refused or has no work (R < 1).                                  */
+#define NS_CLOUD_SHARE 2048
+int64_t ns_cloud_workspace_bytes(int64_t R, int N);
+int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, int64_t z_row_stride, const float* w_dev,
+                    int64_t w_row_stride, const float* rgb_dev, int64_t rgb_stride, int64_t R, int N, float min_weight,
+                    float* pts_out, float* w_out, float* rgb_out, int64_t capacity, int64_t* count_dev, void* workspace_dev,
+                    void* stream);
+
 /* ---- a2 find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

@@ -54,6 +54,17 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="(not in the reference) --device-psnr, and per test view the MSE of the DepthNet's placed samples and of its "
                    "own depth against the field's max-weight depth (ns_depth_sqerr, Trainer(device_depth=True)): -nc's MSE "
                    "without its host copies, in depth.txt next to psnr.txt.  Not with -nf.")
+@click.option("--device-cloud", "device_cloud", is_flag=True, default=False,
+              help="(not in the reference) Also select the scene's point cloud of the rendered views on the device "
+                   "(ns_cloud_append, Trainer(device_cloud=True), nerf_utils.scene_cloud): scene_cloud.pt and scene_cloud.ply "
+                   "beside the frames, what -ssd's scene_data.pt gives after experiments/plot.py's threshold, without its "
+                   "per-sample host copies.  With -nm / -nf the field's samples.")
+@click.option("--cloud-min-weight", "cloud_min_weight", default=0.0, type=float, show_default=True,
+              help="(not in the reference) --device-cloud keeps the samples whose weight is at least this.  0.0 is the "
+                   "reference's own (plot.py:17) and keeps every sample: raise it (0.05 - 0.5) for a cloud of the surfaces.")
+@click.option("--cloud-points", "cloud_points", default=None, type=int, show_default=True,
+              help="(not in the reference) --device-cloud writes at most this many of the kept samples, drawn uniformly "
+                   "(plot.py draws 5e4).")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -70,6 +81,8 @@ def main(**kw):
         k["device_ssim"] = True
     if kw["device_depth"]:
         k["device_depth"] = True
+    if kw["device_cloud"]:
+        k.update(device_cloud=True, cloud_min_weight=kw["cloud_min_weight"], cloud_points=kw["cloud_points"])
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -671,6 +671,154 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
     return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames, ssim=ssim)
 
 
+# ---- the scene's point cloud selected on the device (the reference: scene_data.pt on the host, then experiments/plot.py) ----
+CLOUD_MAX_DEFAULT_CAPACITY = 2 ** 26          # records of a cloud whose capacity the caller leaves open (1.9 GB with colours)
+
+
+def write_ply(path, pts, rgb, weights) -> None:
+    """A binary little-endian PLY point cloud from host arrays: per vertex float x y z, uchar red green blue (``rgb`` in [0, 1]
+    through to8b; None: white) and float weight -- 19 bytes each."""
+    import numpy as np
+
+    pts = np.asarray(pts, dtype=np.float32).reshape(-1, 3)
+    n = pts.shape[0]
+    weights = np.asarray(weights, dtype=np.float32).reshape(-1)
+    colours = np.full((n, 3), 255, dtype=np.uint8) if rgb is None else run_nerf_helpers.to8b(np.asarray(rgb, dtype=np.float32).reshape(-1, 3))
+    if weights.shape[0] != n or colours.shape[0] != n:
+        raise ValueError(f"{n} points, {colours.shape[0]} colours, {weights.shape[0]} weights")
+    vertex = np.empty((n,), dtype=[("xyz", "<f4", (3,)), ("rgb", "u1", (3,)), ("weight", "<f4")])
+    vertex["xyz"], vertex["rgb"], vertex["weight"] = pts, colours, weights
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {n}\n"
+              "property float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              "property float weight\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vertex.tobytes())
+
+
+def _cloud_frame_renderer(kw, trainer, H, W, K, dev, seed):
+    """``render(c2w)`` -> (rays_o, rays_d, z [R,N], weights [R,N], rgb [R,3]) of one view, all on the device: the per-sample
+    arrays the frame render_rays_test makes for this trainer is composited from, through the one-call renderers and without the
+    points.  A configuration they do not take, or one without a weight per sample, raises ValueError."""
+    coarse, fine = kw["network_fn"], kw.get("network_fine")
+    net = fine if fine is not None else coarse
+    if not (bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)):
+        raise ValueError("scene_cloud: it needs view directions and ndc=False")
+    hier = trainer.use_nerf_max_pts or trainer.use_full_nerf
+    with torch.no_grad():
+        if hier and not _hier_one_call_eligible(coarse, fine, kw["network_query_fn"], trainer, True, kw["N_samples"],
+                                                kw.get("raw_noise_std", 0.0), False):
+            raise ValueError("scene_cloud: the frame is not one of the one-call hierarchical renderer's (N_importance > 0, "
+                             "N_samples >= 3, no raw noise, this package's NeRF modules and operators)")
+        if not hier and not _one_call_eligible(kw.get("depth_network"), net, kw["network_query_fn"], trainer, True):
+            raise ValueError("scene_cloud: the frame is not one of the one-call DepthNet renderer's")
+    if not hier and (trainer.sampling_mode == "depth_only" or int(trainer.n_depth_samples) == 1):
+        raise ValueError("scene_cloud: one sample per ray has no weights to threshold (the reference's are [R, 0])")
+    workspace = ops.RenderWorkspace()
+    perturb = float(kw.get("perturb", 0.0))
+    gen = None
+
+    def generator():
+        nonlocal gen
+        if gen is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        return gen
+
+    def render(c2w):
+        rays = ops.get_rays(H, W, K, c2w, device=dev)
+        if hier:
+            # the chain's draws, in _vanilla_one_call's order
+            t_rand = torch.rand([H * W, int(kw["N_samples"])], device=dev, generator=generator()) if perturb > 0.0 else None
+            u = torch.rand([H * W, int(trainer.N_importance)], device=dev, generator=generator()) if perturb != 0.0 else None
+            full = not trainer.use_nerf_max_pts
+            out = ops.render_rays_hierarchical(coarse.packed(), fine.packed() if fine is not None else None, rays=rays,
+                                               n_coarse=int(kw["N_samples"]), n_importance=int(trainer.N_importance),
+                                               lindisp=bool(kw.get("lindisp", False)), white_bkgd=bool(kw["white_bkgd"]),
+                                               near=float(kw["near"]), far=float(kw["far"]), t_rand=t_rand, u=u,
+                                               extras=("z", "weights") if full else False, device=dev, max_sample=not full,
+                                               workspace=workspace)
+            if full:
+                return rays[0], rays[1], out["z"], out["weights"], out["rgb"]
+            return rays[0], rays[1], out["max_z"], out["max_weights"], out["max_rgb"]
+        noise = None
+        if trainer.sampling_mode == "gaussian":
+            noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=generator())
+        out = _depthnet_one_call(kw["depth_network"], net, trainer, rays=rays, extras=("z", "weights"), device=dev, noise=noise,
+                                 workspace=workspace)
+        return rays[0], rays[1], out["z"], out["weights"], out["rgb"]
+
+    return render
+
+
+def scene_cloud(render_poses, hwf, K, render_kwargs, min_weight=0.0, max_points=None, capacity=None, colours=True,
+                savedir=None, seed=0):
+    """The scene's point cloud, selected on the device: the device counterpart of render_path(save_scene_data=True) followed by
+    experiments/plot.py:13-22 -- ``all_pts[all_weights >= min_weight]`` over the samples of every view of ``render_poses``, and
+    then ``max_points`` of them at random -- without a per-sample array ever leaving the device or the points [R,N,3] of a view
+    ever being written.  Per view the rays are generated once and rendered in one call by what the trainer in ``render_kwargs``
+    selects -- the DepthNet frame (its z and weights [R,N], the frame's rgb), under use_nerf_max_pts the field's max-weight
+    sample (max_z / max_weights [R,1], max_rgb), under use_full_nerf the fine pass (z and weights [R,Nc+Nf], its rgb) -- and
+    ns_cloud_append appends the samples whose weight is at least ``min_weight`` to one ops.PointCloud, in the order of
+    torch.cat(all_pts)[torch.cat(all_weights) >= min_weight]: views, rays, samples.  The points and weights are the bits of that
+    expression on render_path's scene_data.pt; a record's colour is its RAY's.
+
+    ``min_weight``: 0.0 is the reference's own (plot.py:17) and keeps every sample with a non-negative weight; raise it.
+    ``capacity``: records the cloud has room for; None = the number of candidates, at most 2^26.  More kept than that:
+    RuntimeError naming the count (a rerun's capacity).  ``max_points``: when more are kept, exactly that many, drawn uniformly
+    without replacement by torch.randperm on a device generator seeded with ``seed`` and kept in the cloud's order (the
+    reference's get_random_indices).  ``seed`` also seeds the draws of gaussian placement and of a perturbed field pass.
+    One sample per ray through the DepthNet frame (depth_only, n_depth_samples == 1), or a configuration the one-call
+    renderers do not take: ValueError.
+
+    Returns dict(pts [M,3], weights [M], rgb [M,3] or None, n_candidates, n_kept) with device tensors; n_kept counts before
+    ``max_points``.  ``savedir`` gets scene_cloud.pt -- all_pts, all_weights, all_rgb, min_weight, n_candidates, host tensors
+    and numbers only (torch.load(weights_only=True)); a script that reads scene_data.pt's all_pts / all_weights reads it too --
+    and scene_cloud.ply (write_ply)."""
+    kw = render_kwargs
+    trainer = kw["trainer"]
+    H, W = int(hwf[0]), int(hwf[1])
+    n_views = len(render_poses)
+    if n_views == 0:
+        raise ValueError("scene_cloud: at least one view")
+    if max_points is not None and int(max_points) < 0:
+        raise ValueError("max_points must be >= 0")
+    net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
+    dev = next(net.parameters()).device
+    render = _cloud_frame_renderer(kw, trainer, H, W, K, dev, seed)
+    cloud, n_candidates = None, 0
+    with torch.no_grad():
+        for c2w in render_poses:
+            o, d, z, w, rgb = render(c2w[:3, :4])
+            if cloud is None:                                                  # every view has the same R and N
+                if capacity is None:
+                    capacity = min(n_views * z.numel(), CLOUD_MAX_DEFAULT_CAPACITY)
+                cloud = ops.PointCloud(int(capacity), colours=bool(colours), device=dev)
+            n_candidates += z.numel()
+            cloud.append(o, d, z, w, rgb=rgb if colours else None, min_weight=min_weight)
+        n_kept = cloud.count()                                                 # the one device-to-host copy
+        if n_kept > cloud.capacity:
+            raise RuntimeError(f"scene_cloud: {n_kept} of {n_candidates} samples pass min_weight={min_weight} but the cloud has "
+                               f"room for {cloud.capacity}: pass capacity={n_kept}, or raise min_weight")
+        pts, weights, rgb = cloud.tensors()
+        if max_points is not None and n_kept > int(max_points):
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+            idx = torch.sort(torch.randperm(n_kept, device=dev, generator=gen)[:int(max_points)]).values
+            pts, weights, rgb = pts[idx], weights[idx], (rgb[idx] if rgb is not None else None)
+    out = dict(pts=pts, weights=weights, rgb=rgb, n_candidates=n_candidates, n_kept=n_kept)
+    if savedir is not None:
+        os.makedirs(savedir, exist_ok=True)
+        host = {k: (None if out[k] is None else out[k].cpu()) for k in ("pts", "weights", "rgb")}
+        torch.save({"all_pts": host["pts"], "all_weights": host["weights"], "all_rgb": host["rgb"],
+                    "min_weight": float(min_weight), "n_candidates": int(n_candidates)}, os.path.join(savedir, "scene_cloud.pt"))
+        write_ply(os.path.join(savedir, "scene_cloud.ply"), host["pts"].numpy(),
+                  None if host["rgb"] is None else host["rgb"].numpy(), host["weights"].numpy())
+    return out
+
+
 def create_nerf(args, model):
     """(render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer) -- nerf_utils.py:393-494."""
     embed_fn, input_ch = run_nerf_helpers.get_embedder(args.multires, args.i_embed, args.input_dims_embed)

@@ -254,6 +254,119 @@ def mse_from_sqerr(sums, n_values):
     return np.asarray(sums, dtype=np.float64) / np.asarray(n_values, dtype=np.float64)
 
 
+# ---- the scene's point cloud (experiments/plot.py:13-22 all_pts[all_weights >= t], selected on the device) ---------------
+def cloud_workspace_bytes(R: int, N: int) -> int:
+    """ns_cloud_workspace_bytes: the per-share counts ``cloud_append`` needs for R rays of N samples (0: a shape it refuses, or
+    no rays)"""
+    return int(_lib.load().ns_cloud_workspace_bytes(int(R), int(N)))
+
+
+def _cloud_rows(t, name: str, dev):
+    """(R, N, row stride in floats) of ``t``: float32 [R,N] or [R] on ``dev``, contiguous or a column slice (unit inner stride)"""
+    if not (isinstance(t, Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() in (1, 2)):
+        raise ValueError(f"{name}: a float32 tensor [R,N] or [R] on the rays' device")
+    R, N = int(t.shape[0]), (int(t.shape[1]) if t.dim() == 2 else 1)
+    if N < 1:
+        raise ValueError(f"{name}: at least one sample per ray, got {tuple(t.shape)}")
+    if t.dim() == 1:
+        stride = 1 if R <= 1 else int(t.stride(0))              # one column of a wider buffer: its row stride
+        if stride < 1:
+            raise ValueError(f"{name}: a vector [R] with a positive stride")
+    else:
+        stride = N if R <= 1 else int(t.stride(0))
+        if (N > 1 and t.stride(1) != 1) or stride < N:
+            raise ValueError(f"{name}: contiguous [R,N], or a column slice of a wider contiguous buffer (unit inner stride)")
+    return R, N, stride
+
+
+def cloud_append(cloud, o, d, z, w, rgb=None, min_weight: float = 0.0):
+    """ns_cloud_append: append the samples of one batch of rays whose weight passes the threshold to ``cloud`` (a PointCloud), on
+    the device and in order -- ray-major, sample-minor, call after call: ``torch.cat(all_pts)[torch.cat(all_weights) >= t]`` of
+    the reference's scene data (experiments/plot.py:13-22, utils.py:36-43).  ``o``, ``d``: contiguous fp32 [R,3]; ``z``, ``w``:
+    fp32 [R,N] (or [R]), contiguous or column slices of wider buffers; ``rgb``: the rays' colours [R,3] with unit inner stride
+    and any row stride >= 3 (``shard[:, :3]`` of an [R,4] tensor), required iff the cloud keeps colours.  A kept record is
+    ``o + d * z`` (ops.points_along_rays' bits), the weight and the ray's colour; a NaN weight is dropped.  Records beyond the
+    cloud's capacity are counted, not written.  Nothing is read back; what is wrong with the arguments raises ValueError before
+    any launch.  Returns ``cloud``."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError("cloud: an ops.PointCloud")
+    dev = cloud.count_dev.device
+    for name, t in (("o", o), ("d", d)):
+        if not (isinstance(t, Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() == 2
+                and t.shape[1] == 3 and t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous float32 tensor [R,3] on the cloud's device")
+    R = int(o.shape[0])
+    if int(d.shape[0]) != R:
+        raise ValueError("o and d: the same number of rays")
+    Rz, N, z_stride = _cloud_rows(z, "z", dev)
+    Rw, Nw, w_stride = _cloud_rows(w, "w", dev)
+    if (Rz, Rw, Nw) != (R, R, N):
+        raise ValueError(f"z and w: both [{R}, N], got {tuple(z.shape)} and {tuple(w.shape)}")
+    if R * N >= 2 ** 31:
+        raise ValueError(f"R * N = {R * N} is not below 2^31")
+    if (rgb is not None) != cloud.colours:
+        raise ValueError("rgb: required by a cloud with colours, and only by it")
+    rgb_stride = 0
+    if rgb is not None:
+        if not (isinstance(rgb, Tensor) and rgb.is_cuda and rgb.device == dev and rgb.dtype == torch.float32 and rgb.dim() == 2
+                and tuple(rgb.shape) == (R, 3) and (R == 0 or rgb.stride(1) == 1) and (R <= 1 or rgb.stride(0) >= 3)):
+            raise ValueError(f"rgb: a float32 tensor [{R},3] on the cloud's device, unit inner stride, row stride >= 3")
+        rgb_stride = 3 if R <= 1 else int(rgb.stride(0))
+    min_weight = float(min_weight)
+    if R == 0:
+        return cloud
+    check(_lib.load().ns_cloud_append(_ptr(o), _ptr(d), _ptr(z), z_stride, _ptr(w), w_stride, _ptr(rgb), rgb_stride, R, N,
+                                      min_weight, _ptr(cloud.pts), _ptr(cloud.weights), _ptr(cloud.rgb), cloud.capacity,
+                                      _ptr(cloud.count_dev), _ptr(cloud._workspace_for(R, N)), _stream(dev)),
+          "ns_cloud_append")
+    return cloud
+
+
+class PointCloud:
+    """The compact arrays ns_cloud_append fills: ``pts`` [capacity,3], ``weights`` [capacity], ``rgb`` [capacity,3] (None without
+    ``colours``), the int64 record counter ``count_dev`` (one element, zeroed) and a workspace that only ever grows -- all on the
+    device.  ``capacity`` = 0 counts without storing.  The counter keeps counting beyond the capacity, so ``count()`` -- one
+    8-byte readback -- is the capacity a rerun needs."""
+
+    def __init__(self, capacity: int, colours: bool = False, device="cuda"):
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"a PointCloud lives on the GPU (got {device}); this path has no CPU fallback")
+        self.capacity, self.colours = capacity, bool(colours)
+        self.pts = torch.empty((capacity, 3), dtype=torch.float32, device=device)
+        self.weights = torch.empty((capacity,), dtype=torch.float32, device=device)
+        self.rgb = torch.empty((capacity, 3), dtype=torch.float32, device=device) if colours else None
+        self.count_dev = torch.zeros((1,), dtype=torch.int64, device=device)
+        self._workspace = None
+
+    def _workspace_for(self, R: int, N: int):
+        need = cloud_workspace_bytes(R, N)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.count_dev.device)
+        return self._workspace
+
+    def append(self, o, d, z, w, rgb=None, min_weight: float = 0.0):
+        return cloud_append(self, o, d, z, w, rgb=rgb, min_weight=min_weight)
+
+    def count(self) -> int:
+        """the number of records kept so far, those beyond the capacity included (reads the counter back)"""
+        return int(self.count_dev.cpu()[0])
+
+    def tensors(self, truncate: bool = False):
+        """(pts[:M], weights[:M], rgb[:M] or None), M = count().  More records than the capacity: RuntimeError naming the capacity
+        needed, or with ``truncate`` the first ``capacity`` records."""
+        M = self.count()
+        if M > self.capacity:
+            if not truncate:
+                raise RuntimeError(f"the point cloud kept {M} records but has room for {self.capacity}: "
+                                   f"a capacity of {M} is needed (or tensors(truncate=True))")
+            M = self.capacity
+        return self.pts[:M], self.weights[:M], (self.rgb[:M] if self.colours else None)
+
+
 # ---- a2 -------------------------------------------------------------------------------------------
 def sphere_intersect(o: Tensor, d: Tensor, radius: float) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()

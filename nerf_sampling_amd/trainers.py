@@ -41,7 +41,8 @@ class Trainer:
                  train_depth_net_only: bool = False, trial=None, single_image=False, single_ray=False,
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
                  hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False,
-                 device_ssim: bool = False, device_depth: bool = False):
+                 device_ssim: bool = False, device_depth: bool = False, device_cloud: bool = False,
+                 cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -77,6 +78,15 @@ class Trainer:
         if self.device_depth and not self.device_eval:
             raise ValueError("device_depth scores the depths of the device evaluation: it needs device_eval=True")
         self._field_depths = None
+        # device_cloud (not in the reference; default off): render() also selects the scene's point cloud of the rendered poses
+        # on the device (nerf_utils.scene_cloud, ns_cloud_append) -- scene_cloud.pt and scene_cloud.ply beside the frames: the
+        # samples whose weight is at least cloud_min_weight (0.0 is the reference's plot.py:17; raise it), and at most
+        # cloud_points of them at random.  The frames and psnr.txt are those of the run without the switch.
+        self.device_cloud = bool(device_cloud)
+        self.cloud_min_weight = float(cloud_min_weight)
+        self.cloud_points = None if cloud_points is None else int(cloud_points)
+        if self.cloud_points is not None and self.cloud_points < 0:
+            raise ValueError("cloud_points must be >= 0")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -175,12 +185,22 @@ class Trainer:
 
     def render(self, render_test, save_scene_data, images, i_test, render_poses, hwf, render_kwargs_test):
         """renderonly_{test|path}_{step:06d}/ with NNN.png, psnr.txt[, scene_data.pt] -- Trainer.py:181-230
-        (the mp4 of the reference needs imageio-ffmpeg and is not written)."""
+        (the mp4 of the reference needs imageio-ffmpeg and is not written).  Under device_cloud also scene_cloud.pt and
+        scene_cloud.ply of the same poses (nerf_utils.scene_cloud)."""
         with torch.no_grad():
             images = images[i_test] if render_test else None
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
                 "test" if render_test else "path", self.global_step))
             os.makedirs(testsavedir, exist_ok=True)
+            if self.device_cloud:
+                H, W = int(hwf[0]), int(hwf[1])
+                if self.render_factor != 0:
+                    raise ValueError("device_cloud renders whole frames at the dataset's size: render_factor must be 0")
+                cloud = nerf_utils.scene_cloud(render_poses, (H, W, hwf[2]), self.K, render_kwargs_test,
+                                               min_weight=self.cloud_min_weight, max_points=self.cloud_points,
+                                               savedir=testsavedir)
+                print(f"scene cloud: {cloud['n_kept']} of {cloud['n_candidates']} samples with weight >= {self.cloud_min_weight}"
+                      f", {cloud['pts'].shape[0]} written to {testsavedir}")
             if self.device_eval and render_test and self.render_factor == 0:
                 ds, ids = self._ray_dataset, i_test
                 if ds is None:          # called on its own: the test views alone go to the device

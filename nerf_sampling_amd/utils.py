@@ -45,6 +45,20 @@ def unfreeze_model(model):
         p.requires_grad = True
 
 
+def get_min_indices(densities: torch.Tensor, min_density):
+    """The mask of the values at or above ``min_density`` (utils.py:36-43): what experiments/plot.py thresholds the weights of
+    the scene data with, and the predicate ns_cloud_append evaluates on the device."""
+    return densities >= min_density
+
+
+def get_random_indices(N_samples: int, k: int):
+    """``k`` distinct indices of range(N_samples) as a list, drawn with Python's ``random`` (utils.py:46-56): plot.py's random
+    subset of the kept points.  nerf_utils.scene_cloud(max_points=k) draws its subset on the device instead."""
+    import random
+
+    return random.sample(range(N_samples), k=k)
+
+
 def save_state(global_step, network_fn, network_fine, optimizer, depth_network, sampling_optimizer, path) -> None:
     """Checkpoint in the reference's layout (utils.py:59-89).  ``depth_network`` / ``sampling_optimizer`` may be None (a field
     fit has neither, trainers.FieldFitter): their keys are then left out, and the file loads as a NeRF checkpoint (ft_path)."""
