@@ -211,6 +211,24 @@ int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, 
                     float* pts_out, float* w_out, float* rgb_out, int64_t capacity, int64_t* count_dev, void* workspace_dev,
                     void* stream);
 
+/* ---- a rendered frame as 8-bit pixels  (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
+ * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a
+ * quarter of the frame's bytes cross to the host:
+ *   out_dev[p * C + c] = (uint8) trunc(255.0f * min(max(x, 0), 1)),  x = rgb_dev[p * rgb_stride + c],  c = 0, 1, 2,
+ * p in [0, n_pixels), C = out_channels: ONE fp32 multiply, then truncation -- numpy's bits on fp32 input for every finite x.
+ * NaN gives 0 (numpy leaves the cast of NaN to the platform; here it is defined), as -0.0, everything below 0 and -inf do;
+ * +inf gives 255.  rgb_stride as ns_image_sqerr's: in floats, 0 = packed 3, 3 or 4 (the interleaved [R,4] shard, whose fourth
+ * float is never used).  out_channels is 3 or 4; with 4 the fourth byte is the same map of alpha_dev[p] (packed [n_pixels]), or
+ * 255 when alpha_dev is NULL; alpha_dev with 3 channels is ignored.  rgb_dev and alpha_dev need no more than a float's
+ * alignment and out_dev none (a row band of a frame): a thread converts four pixels and stores their 12 or 16 bytes as whole
+ * dwords when out_dev is 4-byte aligned, and as bytes otherwise and for the last pixels of a count that is no multiple of 4;
+ * it loads float4s when rgb_dev is 16-byte aligned and single floats otherwise.  Nothing outside out_dev[0 .. n_pixels * C) is
+ * written.  One launch on `stream`.  Checked before the launch (NS_E_INVALID): n_pixels < 0, n_pixels * 4 >= 2^31, a stride
+ * other than 0, 3 or 4, out_channels other than 3 or 4, and for n_pixels > 0 rgb_dev or out_dev NULL.  n_pixels == 0 does
+ * nothing and returns NS_OK.                                                                                              */
+int ns_frame_to8b(const float* rgb_dev, int64_t rgb_stride, const float* alpha_dev, int64_t n_pixels, uint8_t* out_dev,
+                  int out_channels, void* stream);
+
 /* ---- a2 find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

@@ -54,6 +54,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="(not in the reference) --device-psnr, and per test view the MSE of the DepthNet's placed samples and of its "
                    "own depth against the field's max-weight depth (ns_depth_sqerr, Trainer(device_depth=True)): -nc's MSE "
                    "without its host copies, in depth.txt next to psnr.txt.  Not with -nf.")
+@click.option("--device-frames", "device_frames", is_flag=True, default=False,
+              help="(not in the reference) --device-psnr, and the frames as NNN.png beside psnr.txt after all: quantised on the "
+                   "device (ns_frame_to8b, to8b's bits), copied as bytes and encoded by nerf_utils.FrameWriter's threads while "
+                   "the next view renders (Trainer(device_frames=True)).")
 @click.option("--device-cloud", "device_cloud", is_flag=True, default=False,
               help="(not in the reference) Also select the scene's point cloud of the rendered views on the device "
                    "(ns_cloud_append, Trainer(device_cloud=True), nerf_utils.scene_cloud): scene_cloud.pt and scene_cloud.ply "
@@ -75,8 +79,10 @@ def main(**kw):
     k.update(single_image=kw["single_image"], single_ray=kw["single_ray"], save_scene_data=kw["save_scene_data"],
              i_print=kw["i_print"], compare_nerf=kw["nerf_compare"], use_nerf_max_pts=kw["nerf_max"],
              use_full_nerf=kw["nerf_full"], render_only=True, render_test=True)
-    if kw["device_psnr"] or kw["device_ssim"] or kw["device_depth"]:
+    if kw["device_psnr"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"]:
         k["device_eval"] = True
+    if kw["device_frames"]:
+        k["device_frames"] = True
     if kw["device_ssim"]:
         k["device_ssim"] = True
     if kw["device_depth"]:

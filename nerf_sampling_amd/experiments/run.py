@@ -54,6 +54,10 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="--device-eval, and the MSE of the DepthNet's placed samples and of its own depth against the field's "
                    "max-weight depth on the test views (ns_depth_sqerr, Trainer(device_depth=True)): depth.txt next to every "
                    "psnr.txt.  Not with --fit-field, which has no DepthNet.")
+@click.option("--device-frames", "device_frames", is_flag=True, default=False,
+              help="--device-eval, and the test views as NNN.png next to every psnr.txt (ns_frame_to8b on the device, "
+                   "nerf_utils.FrameWriter's threads for the PNGs; Trainer(device_frames=True) / "
+                   "FieldFitter.fit(test_frames=True)).")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -79,8 +83,10 @@ def main(**kw):
         k["fused_step"] = True
     if kw["device_batches"]:
         k["device_batches"] = kw["device_batches"]
-    if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"]:
+    if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"]:
         k["device_eval"] = True
+    if kw["device_frames"]:
+        k["device_frames"] = True
     if kw["device_ssim"]:
         k["device_ssim"] = True
     if kw["device_depth"]:
@@ -117,7 +123,7 @@ def fit_field(trainer, n_iters, gemm_engine="tile"):
     return fitter.fit(split, n_iters, N_rand=trainer.N_rand, basedir=trainer.basedir, expname=f"{trainer.expname}_field",
                       i_weights=trainer.i_weights, i_print=trainer.i_print, device_batches=trainer.device_batches,
                       batch_seed=trainer.batch_seed, i_testset=trainer.i_testset if trainer.device_eval else 0,
-                      test_ssim=trainer.device_ssim)
+                      test_ssim=trainer.device_ssim, test_frames=trainer.device_frames)
 
 
 if __name__ == "__main__":

@@ -397,8 +397,162 @@ def _write_depth_txt(savedir, sample_mses, avg_sample_mse, mean_mses, avg_mean_m
         file.write(format_depth_txt(sample_mses, avg_sample_mse, mean_mses, avg_mean_mse))
 
 
+class FrameWriter:
+    """The frames of a device evaluation as ``{k:03d}.png`` under ``savedir``, the files render_path(savedir=...) writes
+    (nerf_utils.py:322-325), without a float frame on the host and without the PNG encoder on the rendering thread.
+
+    The writer owns ``n_buffers`` slots, allocated once: a uint8 [H,W,channels] device tensor and its pinned host twin each.
+    ``put(k, rgb, alpha=None)`` takes a free slot, quantises the frame into its device tensor on the CURRENT stream
+    (ops.frame_to8b: to8b's bits) and records an event; the writer's own copy stream waits for that event, copies the slot to
+    its twin (non-blocking, a quarter of the fp32 frame's bytes) and records a second event; (k, slot) goes to a queue.
+    ``workers`` plain threads (at most MAX_WORKERS, a number the caller chooses: never the machine's CPU count) take jobs
+    from it: wait for the slot's copy event, ``Image.fromarray(slot).save(...)`` -- render_path's call, so equal pixels at an
+    equal ``compress_level`` (None: PIL's default, as render_path) give equal files -- and hand the slot back.  A slot is
+    therefore reused only after its copy AND its file are done.  put() blocks only while every slot is in flight, and then on
+    the return of a slot -- a worker's wait on that slot's copy event; the compute stream is never synchronised and nothing but
+    the frames is read back.  The writer keeps no reference to ``rgb``: it is read by a launch on the stream that produced it.
+
+    ``close()`` drains the queue, joins the workers, releases the buffers and raises the first exception a worker met (the
+    other frames are still written); it may be called twice, and a ``with`` block calls it -- quietly when the block itself
+    raised, so that the block's exception is the one that surfaces."""
+
+    MAX_WORKERS = 8
+
+    def __init__(self, savedir, H, W, channels=3, n_buffers=4, workers=4, compress_level=None, device=None):
+        import queue
+        import threading
+
+        H, W, channels, n_buffers, workers = int(H), int(W), int(channels), int(n_buffers), int(workers)
+        if savedir is None:
+            raise ValueError("FrameWriter: a directory to write into")
+        if H < 1 or W < 1 or channels not in (3, 4):
+            raise ValueError(f"FrameWriter: a frame of at least 1 x 1 pixels with 3 or 4 channels, got {H} x {W} x {channels}")
+        if n_buffers < 1 or workers < 1:
+            raise ValueError("FrameWriter: at least one buffer and one worker")
+        if compress_level is not None and not 0 <= int(compress_level) <= 9:
+            raise ValueError("FrameWriter: compress_level is None (PIL's default) or 0 .. 9")
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError(f"a FrameWriter's frames live on the GPU (got {device}); this path has no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        from PIL import Image  # noqa: F401  (a missing encoder fails here, not in a worker)
+
+        os.makedirs(savedir, exist_ok=True)
+        self.savedir, self.H, self.W, self.channels = savedir, H, W, channels
+        self.compress_level = None if compress_level is None else int(compress_level)
+        self.device, self.n_buffers, self.workers = device, n_buffers, min(workers, self.MAX_WORKERS)
+        self._dev = torch.empty((n_buffers, H, W, channels), dtype=torch.uint8, device=device)
+        # device="cpu" explicitly: the experiment scripts switch torch's default device to cuda
+        self._host = torch.empty((n_buffers, H, W, channels), dtype=torch.uint8, device="cpu", pin_memory=True)
+        self._quantised = [torch.cuda.Event() for _ in range(n_buffers)]
+        self._copied = [torch.cuda.Event() for _ in range(n_buffers)]
+        self._stream = torch.cuda.Stream(device)
+        self._free, self._jobs = queue.Queue(), queue.Queue()
+        for s in range(n_buffers):
+            self._free.put(s)
+        self._error, self._closed, self.n_written = None, False, 0
+        self._lock = threading.Lock()
+        self._threads = [threading.Thread(target=self._work, name=f"frame-writer-{i}", daemon=True)
+                         for i in range(self.workers)]
+        for t in self._threads:
+            t.start()
+
+    def _work(self):
+        from PIL import Image
+
+        while True:
+            job = self._jobs.get()
+            if job is None:
+                return
+            k, s = job
+            try:
+                self._copied[s].synchronize()
+                view = self._host[s].numpy()
+                path = os.path.join(self.savedir, "{:03d}.png".format(k))
+                if self.compress_level is None:
+                    Image.fromarray(view).save(path)
+                else:
+                    Image.fromarray(view).save(path, compress_level=self.compress_level)
+                with self._lock:
+                    self.n_written += 1
+            except BaseException as e:  # noqa: BLE001  (kept for close(); the worker goes on, so no slot is ever lost)
+                with self._lock:
+                    if self._error is None:
+                        self._error = e
+            finally:
+                self._free.put(s)
+
+    def put(self, k, rgb, alpha=None):
+        """Queue frame ``k``: ``rgb`` fp32 [H*W,3] on the writer's device (contiguous, or the [:, :3] view of a [H*W,4] shard),
+        ``alpha`` fp32 [H*W] for the fourth channel of a 4-channel writer (None: opaque)."""
+        if self._closed:
+            raise RuntimeError("FrameWriter.put after close()")
+        k = int(k)
+        if k < 0:
+            raise ValueError("FrameWriter.put: a frame number >= 0")
+        if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.device == self.device
+                and tuple(rgb.shape) == (self.H * self.W, 3)):
+            raise ValueError(f"FrameWriter.put: rgb is a float32 tensor of shape ({self.H * self.W}, 3) on {self.device}")
+        s = self._free.get()                                   # blocks only while every slot is in flight
+        queued = False
+        try:
+            ops.frame_to8b(rgb, alpha=alpha, out=self._dev[s], channels=self.channels)
+            compute = torch.cuda.current_stream(self.device)
+            self._quantised[s].record(compute)
+            self._stream.wait_event(self._quantised[s])
+            with torch.cuda.stream(self._stream):
+                self._host[s].copy_(self._dev[s], non_blocking=True)
+            self._copied[s].record(self._stream)
+            self._jobs.put((k, s))
+            queued = True
+        finally:
+            if not queued:                                     # refused arguments, or a failed launch: the slot goes back once
+                self._stream.synchronize()                     # whatever of it reached the copy stream is over
+                self._free.put(s)
+
+    def close(self, reraise=True):
+        if not self._closed:
+            self._closed = True
+            for _ in self._threads:
+                self._jobs.put(None)                           # behind every queued frame: the queue drains first
+            for t in self._threads:
+                t.join()
+            self._stream.synchronize()
+            self._threads = []
+            self._dev = self._host = None
+            self._quantised = self._copied = None
+        error, self._error = self._error, None
+        if error is not None and reraise:
+            raise error
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(reraise=exc_type is None)
+        return False
+
+
+def _frame_writer(frames, savedir, H, W, device):
+    """the FrameWriter of ``frames`` (True, or a dict of FrameWriter's keyword arguments: n_buffers, workers, compress_level),
+    or a context that does nothing when ``frames`` is off"""
+    import contextlib
+
+    if not frames:
+        return contextlib.nullcontext()
+    return FrameWriter(savedir, H, W, device=device, **(frames if isinstance(frames, dict) else {}))
+
+
+def _check_frames(frames, savedir, who):
+    if frames and savedir is None:
+        raise ValueError(f"{who}(frames=...) writes the frames as PNGs under savedir: savedir is required")
+    if isinstance(frames, dict) and not set(frames) <= {"n_buffers", "workers", "compress_level"}:
+        raise ValueError(f"{who}: frames is True or a dict of n_buffers / workers / compress_level")
+
+
 def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_frames=False, ssim=False, depth=False,
-                field_depths=None, return_depths=False):
+                field_depths=None, return_depths=False, frames=False):
     """The loop of evaluate_views over any whole-frame renderer: ``render_frame(c2w [3,4], workspace)`` returns the view's rgb
     [H*W,3] on the device (or the [:, :3] view of a [H*W,4] shard), which is scored against image ``image_ids[k]`` into slot
     k of one float64 device array (DeviceRayDataset.image_sqerr).  The workspace is this call's own, and the sums are read back
@@ -414,9 +568,15 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
     held-out rays.  ``field_depths``: max_z of every view from an earlier call (``return_depths``); ``field_depth`` is then
     not called.  ``savedir`` also gets depth.txt.  The result grows in this order:
     (psnrs, avg[, ssims, avg_ssim][, sample_mses, avg_sample_mse, mean_mses, avg_mean_mse][, frames][, depths]) -- ``depths``
-    (``return_depths``): per view (z, mean, max_z) as device tensors."""
+    (``return_depths``): per view (z, mean, max_z) as device tensors.
+
+    ``frames`` (needs ``savedir``; True, or a dict of FrameWriter's n_buffers / workers / compress_level): every view's rgb,
+    after it is scored, also goes through a FrameWriter -- ``{k:03d}.png`` beside psnr.txt, render_path's files, quantised on the
+    device and encoded by the writer's threads while the next view renders.  The writer only reads ``rgb`` and is closed before
+    the sums are read back: the scores, their text files and ``return_frames`` are those of frames=False."""
     import numpy as np
 
+    _check_frames(frames, savedir, "score_views")
     ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
     if len(ids) == 0 or len(ids) != len(poses):
         raise ValueError(f"{len(ids)} image ids for {len(poses)} poses (at least one view)")
@@ -432,8 +592,8 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
     sample_sums, mean_sums = (sums[rows - 2], sums[rows - 1]) if depth else (None, None)
     ssim_ws = (torch.empty((dataset.ssim_workspace_bytes(),), dtype=torch.uint8, device=dataset.device) if ssim else None)
     depth_ws, n_placed = None, 0
-    frames, depths = [], []
-    with torch.no_grad():
+    kept_frames, depths = [], []
+    with torch.no_grad(), _frame_writer(frames, savedir, dataset.H, dataset.W, dataset.device) as writer:
         for k, (img, c2w) in enumerate(zip(ids, poses)):
             rgb = render_frame(c2w[:3, :4], workspace)
             if depth:
@@ -451,8 +611,10 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
                 ops.depth_sqerr(mean, max_z, out=mean_sums, slot=k, workspace=depth_ws)
                 if return_depths:
                     depths.append((z, mean, max_z))
+            if writer is not None:
+                writer.put(k, rgb)
             if return_frames:
-                frames.append(rgb)
+                kept_frames.append(rgb)
     sums = sums.cpu().numpy()                                                 # the one device-to-host copy
     psnrs = dataset.psnr_from_sqerr(sums[0] if rows > 1 else sums, 3 * dataset.H * dataset.W)
     avg = float(np.mean(psnrs))                                               # the mean of the dB values, as the reference's
@@ -473,7 +635,7 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
             _write_depth_txt(savedir, sample_mses, avg_sample, mean_mses, avg_mean)
         out += (sample_mses, avg_sample, mean_mses, avg_mean)
     if return_frames:
-        out += (frames,)
+        out += (kept_frames,)
     return out + (depths,) if return_depths else out
 
 
@@ -559,14 +721,61 @@ def _depth_frame_renderer(kw, trainer, net, H, W, K, dev):
     return render_frame
 
 
+def _one_call_frame_renderer(kw, H, W, K, dev):
+    """``render_frame(c2w, workspace)`` -> rgb [H*W,3] of score_views / write_views for the configuration ``kw`` (a trainer's
+    render_kwargs): ops.render_rays_hierarchical under trainer.use_full_nerf, otherwise ops.render_rays_depthnet with the
+    choices of render_rays_test's one-call branch; None when the configuration is neither's."""
+    trainer = kw["trainer"]
+    net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
+    with torch.no_grad():
+        basics = bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)
+        if trainer.use_full_nerf:
+            eligible = basics and _hier_one_call_eligible(kw["network_fn"], kw.get("network_fine"), kw["network_query_fn"],
+                                                          trainer, True, kw["N_samples"], kw.get("raw_noise_std", 0.0), False)
+        else:
+            eligible = basics and _one_call_eligible(kw.get("depth_network"), net, kw["network_query_fn"], trainer, True)
+    if not eligible:
+        return None
+    if trainer.use_full_nerf:
+        return hierarchical_frame_renderer(kw["network_fn"], kw.get("network_fine"), H, W, K, kw["N_samples"],
+                                           trainer.N_importance, kw.get("lindisp", False), kw["white_bkgd"],
+                                           kw["near"], kw["far"], perturb=float(kw.get("perturb", 0.0)), device=dev)
+    dn = kw["depth_network"]
+    gen = None
+
+    def render_frame(c2w, workspace):
+        nonlocal gen
+        noise = None
+        if trainer.sampling_mode == "gaussian" and int(trainer.n_depth_samples) > 1:
+            # the draws come from a generator of the evaluation's own: the global one belongs to the training step
+            if gen is None:
+                gen = torch.Generator(device=dev)
+                gen.manual_seed(0)
+            noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=gen)
+        return _depthnet_one_call(dn, net, trainer, camera=(H, W, K, c2w, 0, H), extras=False, device=dev, noise=noise,
+                                  workspace=workspace)["rgb"]
+
+    return render_frame
+
+
+def _warn_render_path_fallback(who):
+    global _evaluate_fallback_warned
+    if not _evaluate_fallback_warned:
+        import warnings
+
+        warnings.warn(f"{who}: this configuration is not one of the one-call renderers'; the views go through render_path")
+        _evaluate_fallback_warned = True
+
+
 def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=None, return_frames=False, ssim=False,
-                   depth=False, field_depths=None, return_depths=False):
+                   depth=False, field_depths=None, return_depths=False, frames=False):
     """The device counterpart of render_path(gt_imgs=...): the PSNR of view ``poses[k]`` against image ``image_ids[k]`` of
     ``dataset`` (a ray_batches.DeviceRayDataset, whose images are already on the device), nothing per pixel leaving it.  Every
     view is rendered from its camera in ONE call without per-sample outputs -- ops.render_rays_depthnet with the choices of
     render_rays_test's one-call branch, or ops.render_rays_hierarchical under trainer.use_full_nerf -- and scored by
     ns_image_sqerr (score_views).  Returns (psnr per view as a float64 array, their mean[, the rgb frames as device tensors with
-    ``return_frames``]); with ``savedir``, psnr.txt in render_path's format and no PNG.  A configuration the one-call renderers
+    ``return_frames``]); with ``savedir``, psnr.txt in render_path's format and no PNG (``frames`` below adds them).  A
+    configuration the one-call renderers
     do not take falls back to render_path (PNGs included), with one warning.  The reports of compare_nerf / use_nerf_max_pts are
     more than a PSNR: ValueError.  ``ssim``: every view is also scored by ns_image_ssim -- the frames render_path returned are
     uploaded for it on the fallback -- and the result is (psnr per view, their mean, ssim per view, their mean[, frames]), with
@@ -581,10 +790,15 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
     launched then.  The result is (psnrs, avg[, ssims, avg_ssim][, sample_mses, avg_sample_mse, mean_mses, avg_mean_mse]
     [, frames][, depths]), ``depths`` per view (z, mean, max_z) on the device, and ``savedir`` gets depth.txt
     (format_depth_txt).  The depth report has no render_path fallback: a configuration that is not eligible for both
-    one-call renderers, or use_full_nerf (no DepthNet in that frame), raises ValueError."""
-    global _evaluate_fallback_warned
+    one-call renderers, or use_full_nerf (no DepthNet in that frame), raises ValueError.
+
+    ``frames`` (needs ``savedir``, otherwise ValueError; True, or a dict of FrameWriter's n_buffers / workers /
+    compress_level): the views are also written as ``{k:03d}.png`` beside psnr.txt -- render_path's files -- by a FrameWriter:
+    quantised on the device (ns_frame_to8b), copied as bytes, encoded off this thread (score_views).  Every score and text
+    file keeps its bits.  The render_path fallback writes its PNGs itself."""
     import numpy as np
 
+    _check_frames(frames, savedir, "evaluate_views")
     kw = render_kwargs
     trainer = kw["trainer"]
     if trainer.compare_nerf or trainer.use_nerf_max_pts:
@@ -614,21 +828,10 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
             raise ValueError(f"evaluate_views(depth=True): {why}; the depth report has no render_path fallback")
         render_frame = _depth_frame_renderer(kw, trainer, net, H, W, K, dev)
         return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames, ssim=ssim,
-                           depth=True, field_depths=field_depths, return_depths=return_depths)
-    with torch.no_grad():
-        basics = bool(kw.get("use_viewdirs", False)) and not kw.get("ndc", True)
-        if trainer.use_full_nerf:
-            eligible = basics and _hier_one_call_eligible(kw["network_fn"], kw.get("network_fine"), kw["network_query_fn"],
-                                                          trainer, True, kw["N_samples"], kw.get("raw_noise_std", 0.0), False)
-        else:
-            eligible = basics and _one_call_eligible(kw.get("depth_network"), net, kw["network_query_fn"], trainer, True)
-    if not eligible:
-        if not _evaluate_fallback_warned:
-            import warnings
-
-            warnings.warn("evaluate_views: this configuration is not one of the one-call renderers'; the views go through "
-                          "render_path")
-            _evaluate_fallback_warned = True
+                           depth=True, field_depths=field_depths, return_depths=return_depths, frames=frames)
+    render_frame = _one_call_frame_renderer(kw, H, W, K, dev)
+    if render_frame is None:
+        _warn_render_path_fallback("evaluate_views")
         gt = _dataset_targets_host(dataset, image_ids)
         if savedir is not None:
             os.makedirs(savedir, exist_ok=True)
@@ -636,39 +839,56 @@ def evaluate_views(dataset, image_ids, poses, hwf, K, render_kwargs, savedir=Non
             rgbs, _disps, avg = render_path(poses, hwf, K, trainer.chunk, kw, step=0, gt_imgs=gt, savedir=savedir)
         psnrs = np.array([-10.0 * np.log10(np.mean(np.square(r - g))) for r, g in zip(rgbs, gt)], dtype=np.float64)
         out = (psnrs, float(avg))
-        frames = [torch.from_numpy(r).reshape(-1, 3).to(dev) for r in rgbs] if (return_frames or ssim) else None
+        host_frames = [torch.from_numpy(r).reshape(-1, 3).to(dev) for r in rgbs] if (return_frames or ssim) else None
         if ssim:
             ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
             sums = torch.empty((len(ids),), dtype=torch.float64, device=dev)
-            for k, (img, rgb) in enumerate(zip(ids, frames)):
+            for k, (img, rgb) in enumerate(zip(ids, host_frames)):
                 dataset.image_ssim(img, rgb, out=sums, slot=k)
             ssims = dataset.ssim_from_sum(sums, H, W)
             avg_ssim = float(np.mean(ssims))
             if savedir is not None:
                 _write_ssim_txt(savedir, ssims, avg_ssim)
             out += (ssims, avg_ssim)
-        return out + (frames,) if return_frames else out
-    if trainer.use_full_nerf:
-        render_frame = hierarchical_frame_renderer(kw["network_fn"], kw.get("network_fine"), H, W, K, kw["N_samples"],
-                                                   trainer.N_importance, kw.get("lindisp", False), kw["white_bkgd"],
-                                                   kw["near"], kw["far"], perturb=float(kw.get("perturb", 0.0)), device=dev)
-    else:
-        dn = kw["depth_network"]
-        gen = None
+        return out + (host_frames,) if return_frames else out
+    return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames, ssim=ssim,
+                       frames=frames)
 
-        def render_frame(c2w, workspace):
-            nonlocal gen
-            noise = None
-            if trainer.sampling_mode == "gaussian" and int(trainer.n_depth_samples) > 1:
-                # the draws come from a generator of the evaluation's own: the global one belongs to the training step
-                if gen is None:
-                    gen = torch.Generator(device=dev)
-                    gen.manual_seed(0)
-                noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=gen)
-            return _depthnet_one_call(dn, net, trainer, camera=(H, W, K, c2w, 0, H), extras=False, device=dev, noise=noise,
-                                      workspace=workspace)["rgb"]
 
-    return score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames, ssim=ssim)
+def write_views(poses, hwf, K, render_kwargs, savedir, return_frames=False, n_buffers=4, workers=4, compress_level=None,
+                device="cuda"):
+    """evaluate_views' loop without a dataset and without scores: every pose rendered in one call by the frame renderer
+    evaluate_views builds and written as ``{k:03d}.png`` under ``savedir`` through a FrameWriter -- the frames of
+    render_path(savedir=...) for poses that have no ground truth (render_only without render_test: the spiral
+    ``render_poses``).  Nothing but the quantised frames leaves the device.  -> the number of views[, the rgb frames as device
+    tensors with ``return_frames``].  A configuration the one-call renderers do not take goes through render_path, with one
+    warning, as evaluate_views' does."""
+    kw = render_kwargs
+    trainer = kw["trainer"]
+    if savedir is None:
+        raise ValueError("write_views writes the frames as PNGs under savedir: savedir is required")
+    if len(poses) == 0:
+        raise ValueError("write_views: at least one pose")
+    H, W = int(hwf[0]), int(hwf[1])
+    dev = torch.device(device)
+    render_frame = _one_call_frame_renderer(kw, H, W, K, dev)
+    if render_frame is None:
+        _warn_render_path_fallback("write_views")
+        os.makedirs(savedir, exist_ok=True)
+        with torch.no_grad():
+            rgbs, _disps, _ = render_path(poses, hwf, K, trainer.chunk, kw, step=0, savedir=savedir)
+        host_frames = [torch.from_numpy(r).reshape(-1, 3).to(dev) for r in rgbs] if return_frames else None
+        return (len(rgbs), host_frames) if return_frames else len(rgbs)
+    workspace = ops.RenderWorkspace()
+    kept_frames = []
+    with torch.no_grad(), FrameWriter(savedir, H, W, n_buffers=n_buffers, workers=workers, compress_level=compress_level,
+                                      device=dev) as writer:
+        for k, c2w in enumerate(poses):
+            rgb = render_frame(c2w[:3, :4], workspace)
+            writer.put(k, rgb)
+            if return_frames:
+                kept_frames.append(rgb)
+    return (len(poses), kept_frames) if return_frames else len(poses)
 
 
 # ---- the scene's point cloud selected on the device (the reference: scene_data.pt on the host, then experiments/plot.py) ----

@@ -367,6 +367,48 @@ class PointCloud:
         return self.pts[:M], self.weights[:M], (self.rgb[:M] if self.colours else None)
 
 
+# ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b, quantised on the device) -----------------------------
+def frame_to8b(rgb, alpha=None, out=None, channels: int = 3):
+    """ns_frame_to8b: ``run_nerf_helpers.to8b`` of a rendered frame on the device -- (uint8) trunc(255 * clip(x, 0, 1)), one fp32
+    multiply, numpy's bits for every finite x; NaN gives 0.  ``rgb``: what DeviceRayDataset.image_sqerr accepts, fp32 [R,3] on
+    the device, contiguous or the ``[:, :3]`` view of a contiguous [R,4] shard.  ``channels``: 3 or 4; with 4 the fourth byte
+    is the same map of ``alpha`` (contiguous fp32 [R] or [R,1] on rgb's device), or 255 without one; ``alpha`` with 3 channels
+    is ignored.  ``out``: a contiguous uint8 tensor of R * channels elements on rgb's device (a slot of a ring of frames; it
+    may start at any byte); None: allocated.  Returns the bytes as a uint8 tensor [R, channels].  Asynchronous on the current
+    stream, nothing is read back; what is wrong with the arguments raises before the launch."""
+    if not isinstance(rgb, Tensor):
+        raise TypeError("rgb must be a torch.Tensor")
+    if not rgb.is_cuda:
+        raise RuntimeError(f"rgb must live on the GPU (got {rgb.device}); this path has no CPU fallback")
+    if not (rgb.dtype == torch.float32 and rgb.dim() == 2 and rgb.shape[1] == 3):
+        raise ValueError("rgb: a float32 device tensor of shape (R, 3)")
+    R = int(rgb.shape[0])
+    if rgb.is_contiguous():
+        stride = 3
+    elif tuple(rgb.stride()) == (4, 1):
+        stride = 4
+    else:
+        raise ValueError("rgb: contiguous [R,3], or the [:, :3] view of a contiguous [R,4] shard")
+    channels = int(channels)
+    if channels not in (3, 4):
+        raise ValueError(f"channels: 3 or 4, got {channels}")
+    if R * 4 >= 2 ** 31:
+        raise ValueError(f"rgb: R * 4 = {R * 4} is not below 2^31")
+    if alpha is not None and not (isinstance(alpha, Tensor) and alpha.is_cuda and alpha.device == rgb.device
+                                  and alpha.dtype == torch.float32 and tuple(alpha.shape) in ((R,), (R, 1))
+                                  and alpha.is_contiguous()):
+        raise ValueError(f"alpha: a contiguous float32 tensor of shape ({R},) or ({R}, 1) on rgb's device")
+    if out is None:
+        out = torch.empty((R, channels), dtype=torch.uint8, device=rgb.device)
+    elif not (isinstance(out, Tensor) and out.dtype == torch.uint8 and out.device == rgb.device and out.is_contiguous()
+              and out.numel() == R * channels):
+        raise ValueError(f"out: a contiguous uint8 tensor of {R * channels} elements on rgb's device")
+    if R > 0:
+        check(_lib.load().ns_frame_to8b(_ptr(rgb), stride, _ptr(alpha) if channels == 4 else None, R, _ptr(out), channels,
+                                        _stream(rgb.device)), "ns_frame_to8b")
+    return out.view(R, channels)
+
+
 # ---- a2 -------------------------------------------------------------------------------------------
 def sphere_intersect(o: Tensor, d: Tensor, radius: float) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()

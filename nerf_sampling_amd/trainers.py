@@ -28,8 +28,9 @@ class Trainer:
     evaluation of held-out views -- ``device_eval`` (psnr.txt scored on the device, i_testset honoured by train()), with it
     ``device_ssim`` (ssim.txt) and ``device_depth`` (depth.txt: per view the MSE of the DepthNet's placed samples and of its
     own depth against the field's max-weight depth, "[TRAIN] Iter: i test depth MSE: x mean MSE: y"; the field's depth maps
-    of the i_test views are rendered once while train_depth_net_only keeps the field frozen and the test perturb is 0).
-    Both need device_eval."""
+    of the i_test views are rendered once while train_depth_net_only keeps the field frozen and the test perturb is 0) and
+    ``device_frames`` (NNN.png beside every psnr.txt, quantised on the device and encoded by nerf_utils.FrameWriter's threads).
+    All three need device_eval."""
 
     def __init__(self, dataset_type, basedir, expname, no_batching, datadir, device="cpu", render_test=False,
                  config_path=None, N_rand=32 * 32 * 4, render_only=False, chunk=1024 * 32, render_factor=0,
@@ -42,7 +43,7 @@ class Trainer:
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
                  hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False,
                  device_ssim: bool = False, device_depth: bool = False, device_cloud: bool = False,
-                 cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None):
+                 cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -87,6 +88,12 @@ class Trainer:
         self.cloud_points = None if cloud_points is None else int(cloud_points)
         if self.cloud_points is not None and self.cloud_points < 0:
             raise ValueError("cloud_points must be >= 0")
+        # device_frames (not in the reference; default off): the device evaluation also writes its frames as NNN.png beside
+        # psnr.txt -- render_path's files -- through nerf_utils.FrameWriter: quantised on the device (ns_frame_to8b), copied as
+        # bytes and encoded off the rendering thread.  render() and evaluate_testset() honour it; the scores keep their bits.
+        self.device_frames = bool(device_frames)
+        if self.device_frames and not self.device_eval:
+            raise ValueError("device_frames writes the frames of the device evaluation: it needs device_eval=True")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -206,8 +213,14 @@ class Trainer:
                 if ds is None:          # called on its own: the test views alone go to the device
                     ds, ids = ops.ray_dataset(np.asarray(images, dtype=np.float32), render_poses, self.K, [0]), range(len(i_test))
                 scores = nerf_utils.evaluate_views(ds, ids, render_poses, hwf, self.K, render_kwargs_test,
-                                                   savedir=testsavedir, ssim=self.device_ssim, depth=self.device_depth)
+                                                   savedir=testsavedir, ssim=self.device_ssim, depth=self.device_depth,
+                                                   frames=self.device_frames)
                 return scores[1]
+            if self.device_eval and self.device_frames and not render_test and self.render_factor == 0:
+                # poses without ground truth (the spiral): the same loop without scores; render_path's average is 0 there
+                nerf_utils.write_views(render_poses, hwf, self.K, render_kwargs_test, testsavedir,
+                                       device="cuda" if self.device == "cuda" else self.device)
+                return 0.0
             _, _, avg_test_psnr = nerf_utils.render_path(
                 render_poses, hwf, self.K, self.chunk, render_kwargs_test, step=self.global_step,
                 save_scene_data=save_scene_data, gt_imgs=images, savedir=testsavedir, render_factor=self.render_factor)
@@ -221,12 +234,13 @@ class Trainer:
         savedir = os.path.join(self.basedir, self.expname, "testset_{:06d}".format(i))
         if not self.device_depth:
             scores = nerf_utils.evaluate_views(self._ray_dataset, i_test, test_poses, hwf, self.K, render_kwargs_test,
-                                               savedir=savedir, ssim=self.device_ssim)
+                                               savedir=savedir, ssim=self.device_ssim, frames=self.device_frames)
             return (scores[1], scores[3]) if self.device_ssim else scores[1]
         keep = bool(self.train_depth_net_only) and float(render_kwargs_test.get("perturb", 0.0)) == 0.0
         scores = nerf_utils.evaluate_views(self._ray_dataset, i_test, test_poses, hwf, self.K, render_kwargs_test,
                                            savedir=savedir, ssim=self.device_ssim, depth=True,
-                                           field_depths=self._field_depths if keep else None, return_depths=keep)
+                                           field_depths=self._field_depths if keep else None, return_depths=keep,
+                                           frames=self.device_frames)
         if keep and self._field_depths is None:
             self._field_depths = [max_z for _z, _mean, max_z in scores[-1]]
         averages = scores[1:4 if self.device_ssim else 2:2]           # (PSNR[, SSIM]): every second element is an average
@@ -660,19 +674,22 @@ class FieldFitter:
         draw.dataset, draw.poses, draw.hwf, draw.K, draw.i_test = dataset, np.asarray(poses, dtype=np.float32), hwf, tr.K, i_test
         return draw
 
-    def evaluate_views(self, dataset, image_ids, poses, hwf, K, savedir=None, return_frames=False, ssim=False):
+    def evaluate_views(self, dataset, image_ids, poses, hwf, K, savedir=None, return_frames=False, ssim=False,
+                       frames=False):
         """The PSNR of held-out views on the device (nerf_utils.score_views): every view through the hierarchical renderer in
         one call, with this fitter's N_samples / N_importance, white_bkgd / lindisp / bounds and perturb 0, scored against
         ``dataset``'s images.  Call repack() first if the weights have moved.  -> (psnr per view, their mean[, frames]); with
-        ``ssim`` (psnr per view, their mean, ssim per view, their mean[, frames]) and ssim.txt beside psnr.txt."""
+        ``ssim`` (psnr per view, their mean, ssim per view, their mean[, frames]) and ssim.txt beside psnr.txt.  ``frames``
+        (needs ``savedir``): the views also as NNN.png beside psnr.txt (nerf_utils.FrameWriter)."""
         render_frame = nerf_utils.hierarchical_frame_renderer(
             self.network_fn, self.network_fine, int(hwf[0]), int(hwf[1]), K, self.N_samples, self.N_importance, self.lindisp,
             self.white_bkgd, self.near, self.far, perturb=0.0, device=dataset.device)
         return nerf_utils.score_views(dataset, image_ids, poses, render_frame, savedir=savedir, return_frames=return_frames,
-                                      ssim=ssim)
+                                      ssim=ssim, frames=frames)
 
     def fit(self, rays_source, n_iters, N_rand=1024, basedir=None, expname="field", i_weights=10000, i_print=100,
-            evaluate=None, device_batches=False, batch_seed=0, i_testset=0, test_ids=None, test_ssim=False):
+            evaluate=None, device_batches=False, batch_seed=0, i_testset=0, test_ids=None, test_ssim=False,
+            test_frames=False):
         """``n_iters`` steps on batches from ``rays_source``: a loaded Blender split (see _blender_source) or a callable
         returning (batch_rays [2,B,3], target [B,3]).  With ``basedir`` a checkpoint {basedir}/{expname}/{step:06d}.tar is written
         every ``i_weights`` steps and at the end.  ``evaluate(fitter)``, if given, runs at every ``i_print`` steps after repack().
@@ -680,8 +697,11 @@ class FieldFitter:
         are made (_blender_source).  ``i_testset`` > 0 (a Blender split only): every ``i_testset`` steps and at the end the views
         ``test_ids`` (default: the split's i_test) are scored on the device (``evaluate_views``), "[FIT] Iter: .. test PSNR:
         .." is printed and, with ``basedir``, {basedir}/{expname}/testset_{step:06d}/psnr.txt written; ``test_ssim`` adds
-        " SSIM: .." to that line and ssim.txt to that directory.  Returns the last (loss, psnr, psnr0)."""
+        " SSIM: .." to that line and ssim.txt to that directory, ``test_frames`` (needs ``basedir``) the views as NNN.png.
+        Returns the last (loss, psnr, psnr0)."""
         i_testset = int(i_testset or 0)
+        if test_frames and i_testset > 0 and basedir is None:
+            raise ValueError("test_frames writes the test views under basedir: basedir is required")
         if callable(rays_source):
             if device_batches:
                 raise ValueError("device_batches applies to a Blender split, not to a callable ray source")
@@ -701,7 +721,7 @@ class FieldFitter:
             self.repack()
             savedir = None if basedir is None else os.path.join(basedir, expname, "testset_{:06d}".format(self.global_step))
             scores = self.evaluate_views(draw.dataset, test_ids, draw.poses[test_ids], draw.hwf, draw.K, savedir=savedir,
-                                         ssim=bool(test_ssim))
+                                         ssim=bool(test_ssim), frames=bool(test_frames))
             print(f"[FIT] Iter: {self.global_step} test PSNR: {scores[1]}" + (f" SSIM: {scores[3]}" if test_ssim else ""))
 
         out = None

@@ -4,9 +4,12 @@ fitted scene at 800 x 800 x 64, bf16 field with the PSNR guard; and the scoring 
 median of three alternations on one box, with the spread of the first path beside it.  --ssim: evaluate_views without and
 with ssim=True instead (the host path is not run), and ns_image_ssim alone beside ns_image_sqerr.  --depth: evaluate_views
 without depth, with depth=True and the field's depth maps rendered afresh, and with them passed in as field_depths, the three
-alternating; then ns_depth_sqerr alone at (640 000, 64) and (640 000, 1).
+alternating; then ns_depth_sqerr alone at (640 000, 64) and (640 000, 1).  --frames: render_path(gt_imgs=..., savedir=...),
+evaluate_views without frames and evaluate_views(frames=True) -- the PNGs written by nerf_utils.FrameWriter -- the three
+alternating; then evaluate_views(frames=...) at workers = 1, 2, 4, 8 with PIL's default compress_level and with 1; then
+ns_frame_to8b alone beside ns_image_sqerr.
 
-    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim | --depth]
+    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim | --depth | --frames]
 """
 import argparse
 import os
@@ -35,6 +38,9 @@ def main():
     ap.add_argument("--ssim", action="store_true", help="evaluate_views with ssim=True against without; ns_image_ssim alone")
     ap.add_argument("--depth", action="store_true",
                     help="evaluate_views without depth, with depth=True and fresh field depths, with cached ones; ns_depth_sqerr alone")
+    ap.add_argument("--frames", action="store_true",
+                    help="render_path with PNGs, evaluate_views without and with frames=True; the workers x compress_level "
+                         "table; ns_frame_to8b alone")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _coarse, fine, dn, _params = bench.build_modules("shapes_fit", dev)
@@ -76,6 +82,8 @@ def main():
 
     if a.depth:
         return bench_depth(a, dev, ds, ids, poses, [H, W, focal], K, kw, timed)
+    if a.frames:
+        return bench_frames(a, dev, ds, ids, poses, [H, W, focal], K, kw, timed, host_path, device_path)
     # the first path of the pair is the one the second is measured against
     first, second = ((device_path, device_ssim_path) if a.ssim else (host_path, device_path))
     timed(first), timed(second)                              # warm-up: pinned buffers, packed streams, workspaces
@@ -121,6 +129,59 @@ def main():
             torch.cuda.synchronize()
             per.append(1e3 * e0.elapsed_time(e1_) / reps)
         print(f"  ns_image_ssim alone       {statistics.median(per):8.2f} us per {H} x {W} frame   (spread {max(per) - min(per):.2f})")
+
+
+def bench_frames(a, dev, ds, ids, poses, hwf, K, kw, timed, host_path, device_path):
+    """--frames: the host path, the device path and the device path with its PNGs in alternation; the device path with its PNGs
+    per worker count and compress_level; ns_frame_to8b alone (one launch) beside ns_image_sqerr (two) on an 800 x 800 frame"""
+    H, W = hwf[0], hwf[1]
+
+    def with_frames(**writer):
+        return lambda d: nerf_utils.evaluate_views(ds, ids, poses, hwf, K, kw, savedir=d, frames=writer or True)[1]
+
+    paths = [("render_path(gt_imgs, savedir)", host_path), ("evaluate_views", device_path),
+             ("evaluate_views(frames=True)", with_frames())]
+    for _name, fn in paths:
+        timed(fn)                                            # warm-up: pinned buffers, packed streams, workspaces
+    runs = [[] for _ in paths]
+    for _ in range(a.alternations):
+        for r, (_name, fn) in zip(runs, paths):
+            r.append(timed(fn))
+    print(f"{H} x {W} x {a.samples}, bf16 + PSNR guard, {a.views} views; ms per view, median of {a.alternations} alternations")
+    for (name, _fn), r in zip(paths, runs):
+        t = [ms for ms, _ in r]
+        print(f"  {name:<32s} {statistics.median(t):8.2f}   (spread {max(t) - min(t):.2f})   avg PSNR {r[-1][1]:.4f}")
+    print("  evaluate_views(frames=dict(workers=w, compress_level=c)), n_buffers = 4:")
+    table = [(w, c) for c in (None, 1) for w in (1, 2, 4, 8)]
+    runs = [[] for _ in table]
+    for _ in range(a.alternations):
+        for r, (w, c) in zip(runs, table):
+            r.append(timed(with_frames(workers=w, compress_level=c))[0])
+    for (w, c), r in zip(table, runs):
+        print(f"    workers {w}  compress_level {'default' if c is None else c}   {statistics.median(r):8.2f}   "
+              f"(spread {max(r) - min(r):.2f})")
+    rgb = torch.rand((H * W, 3), device=dev)
+    shard = torch.rand((H * W, 4), device=dev)[:, :3]
+    out8 = torch.empty((H * W, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty((1,), dtype=torch.float64, device=dev)
+    ws = torch.empty((ds.sqerr_workspace_bytes(H * W),), dtype=torch.uint8, device=dev)
+    calls = [("ns_frame_to8b alone, packed rgb", lambda: ops.frame_to8b(rgb, out=out8)),
+             ("ns_frame_to8b alone, [R,4] shard", lambda: ops.frame_to8b(shard, out=out8)),
+             ("ns_image_sqerr alone", lambda: ds.image_sqerr(0, rgb, out=out, workspace=ws))]
+    reps = 200
+    for name, call in calls:
+        for _ in range(10):
+            call()
+        per = []
+        for _ in range(a.alternations):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                call()
+            e1.record()
+            torch.cuda.synchronize()
+            per.append(1e3 * e0.elapsed_time(e1) / reps)
+        print(f"  {name:<34s} {statistics.median(per):8.2f} us per {H} x {W} frame   (spread {max(per) - min(per):.2f})")
 
 
 def bench_depth(a, dev, ds, ids, poses, hwf, K, kw, timed):
