@@ -229,6 +229,42 @@ int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, 
 int ns_frame_to8b(const float* rgb_dev, int64_t rgb_stride, const float* alpha_dev, int64_t n_pixels, uint8_t* out_dev,
                   int out_channels, void* stream);
 
+/* ---- the maximum of per-ray maps, kept on the device  (Trainer.py:371-376: the i_video branch writes
+ * to8b(disps / np.max(disps)), one divisor for ALL frames of the spiral) ----  state_dev is two floats in device memory:
+ *   state[0] = the maximum over the values seen that are not NaN, -inf when there are none,
+ *   state[1] = 1.0f if a NaN was seen, otherwise 0.0f.
+ * map_dev[i * stride], i in [0, n), is a per-ray fp32 map; stride is in floats: 1 = packed [R], 4 = the [:, 3] column of the
+ * interleaved [R,4] shard, whose base lies 12 bytes into the shard -- map_dev needs no more than a float's alignment (a packed
+ * map on a 16-byte boundary is read as float4s, everything else one dword per value).  accumulate == 0 initialises the state
+ * from this map alone; accumulate != 0 folds this map into the state already there, so that calls over the frames of a
+ * sequence leave the state of their concatenation and nothing is read back in between.  n == 0 writes (-inf, 0) under
+ * accumulate == 0 and leaves the state as it is otherwise (map_dev and workspace_dev may then be NULL).  (np.max itself
+ * returns NaN when any value is NaN -- a ray without opacity has disparity 0 / 0 -- and the reference's disp.mp4 is then
+ * black; the flag reports that case and the maximum stays usable.)  The sign of a zero maximum is not specified.
+ * Shaped as ns_image_sqerr: workgroup g folds the 2048 values from g * 2048 on into one (max, flag) pair of workspace_dev
+ * (ns_map_max_workspace_bytes(n) bytes, 8-byte aligned), and a second launch of ONE workgroup folds the pairs and, under
+ * accumulate, the old state.  A maximum does not depend on the order of its comparisons: no atomics, the same bits on every
+ * call.  Checked before any HIP call (NS_E_INVALID): n < 0, n >= 2^31, a stride other than 1 or 4, state_dev NULL or not
+ * 4-byte aligned, workspace_dev not 8-byte aligned, and for n > 0 map_dev or workspace_dev NULL.
+ * ns_map_max_workspace_bytes is 0 for n <= 0 and for a count that would be refused.                                        */
+int64_t ns_map_max_workspace_bytes(int64_t n);
+int ns_map_max(const float* map_dev, int64_t stride, int64_t n, int accumulate, float* state_dev, void* workspace_dev,
+               void* stream);
+
+/* ---- a per-ray map as 8-bit pixels, divided by a number in device memory  (Trainer.py:371-376
+ * to8b(disps / np.max(disps)); run_nerf_helpers.py:11 to8b) ----
+ *   out_dev[i] = (uint8) trunc(255.0f * min(max(q, 0), 1)),  q = map_dev[i * stride] / *denom_dev,  i in [0, n):
+ * ONE correctly rounded fp32 division -- numpy's float32 / float32, never a reciprocal and a multiply, which differ in the
+ * last bit often enough to move a pixel -- then ns_frame_to8b's clip (comparisons), multiply and truncation.  A NaN quotient
+ * gives 0: a NaN value, 0 / 0, inf / inf, a NaN divisor.  denom_dev == NULL: no division (q is the value itself).  denom_dev
+ * is any 4-byte aligned float in device memory, read by the kernel -- the state of ns_map_max itself, so that the divisor of
+ * a sequence never crosses to the host.  stride as ns_map_max's.  A thread converts four consecutive values and stores their
+ * bytes as one dword when out_dev is 4-byte aligned, and as bytes otherwise and for the last values of a count that is no
+ * multiple of 4; nothing outside out_dev[0 .. n) is written.  One launch on `stream`.  Checked before the launch
+ * (NS_E_INVALID): n < 0, n >= 2^31, a stride other than 1 or 4, denom_dev not 4-byte aligned, and for n > 0 map_dev or
+ * out_dev NULL.  n == 0 does nothing and returns NS_OK.                                                                    */
+int ns_map_to8b(const float* map_dev, int64_t stride, int64_t n, const float* denom_dev, uint8_t* out_dev, void* stream);
+
 /* ---- a2 find_intersection_points_with_sphere / solve_quadratic_equation (utils.py:159-217)
  * t [R,2] (minus-sqrt root first) and points [R,2,3]; NaN where the line misses the sphere.  */
 int ns_sphere_intersect(const float* o_dev, const float* d_dev, int64_t R, float radius,

@@ -126,6 +126,9 @@ SIGNATURES = {
     "ns_cloud_workspace_bytes": (_i64, [_i64, _i]),
     "ns_cloud_append": (_i, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i, _f, _p, _p, _p, _i64, _p, _p, _p]),
     "ns_frame_to8b": (_i, [_p, _i64, _p, _i64, _p, _i, _p]),
+    "ns_map_max_workspace_bytes": (_i64, [_i64]),
+    "ns_map_max": (_i, [_p, _i64, _i64, _i, _p, _p, _p]),
+    "ns_map_to8b": (_i, [_p, _i64, _i64, _p, _p, _p]),
     "ns_sphere_intersect": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "ns_solve_quadratic": (_i, [_p, _p, _p, _i64, _p, _p]),
     "ns_posenc": (_i, [_p, _i64, _i, _i, _p, _p]),

@@ -10,6 +10,11 @@
 // Loads: rgb_dev is only known to be 4-byte aligned (a band of packed-3 data), so the default is one dword per value; when the
 // base happens to be 16-byte aligned (whole frames are) a group of packed-3 pixels is three float4 loads, and a pixel of the
 // interleaved [R,4] layout one -- except the last pixel of the buffer, whose fourth float nobody promised exists.
+//
+// Below it, the disparity sequence of the turntable (Trainer.py:371-376 to8b(disps / np.max(disps))): ns_map_max keeps the
+// maximum of the frames' maps on the device, ns_map_to8b divides by it where it lies and quantises with the same to8b.
+#include <cmath>
+
 #include "ns_common.h"
 
 namespace {
@@ -79,6 +84,148 @@ frame_to8b_kernel(const float* __restrict__ rgb, int stride, const float* __rest
   }
 }
 
+// ---- a per-ray map as 8-bit pixels, divided by a number in device memory (ns_map_to8b) -------------------------------------
+// Trainer.py:371-376: to8b(disps / np.max(disps)).  numpy divides float32 by float32 with ONE correctly rounded division, so
+// the quotient here is the `/` operator (hipcc's default for HIP: v_div_scale / v_rcp / the fma refinement / v_div_fmas /
+// v_div_fixup, 0.5 ulp), never x * (1 / d); then to8b above.  0 / 0, inf / inf and a NaN divisor give NaN, and NaN gives 0.
+// Thread t owns the kGroup pixels 4 t .. 4 t + 3 and their four output bytes: ONE dword where out_dev is 4-byte aligned and
+// the group is whole, bytes otherwise; a thread writes only the bytes of its own pixels p < n.
+// Loads: a packed map whose base is 16-byte aligned gives a whole group as one float4; any other packed base and the [:, 3]
+// column of an [R,4] shard -- 12 bytes into the shard, so never 16-byte aligned -- are read one dword per value.
+__global__ void __launch_bounds__(kBlock)
+map_to8b_kernel(const float* __restrict__ map, int stride, int64_t n, const float* __restrict__ denom, uint8_t* __restrict__ out,
+                int wide_loads, int dword_stores) {
+  const int64_t p0 = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * kGroup;
+  if (p0 >= n) return;
+  const int m = n - p0 < kGroup ? static_cast<int>(n - p0) : kGroup;     // pixels of this group that exist
+  float v[kGroup];
+  if (m == kGroup && wide_loads) {                                        // stride == 1 and 4 p0 floats = 16 p0 bytes on
+    const float4 a = *reinterpret_cast<const float4*>(map + p0);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) v[i] = i < m ? map[(p0 + i) * stride] : 0.0f;
+  }
+  uint32_t b[kGroup];
+  if (denom != nullptr) {
+    const float d = *denom;
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) b[i] = to8b(v[i] / d);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) b[i] = to8b(v[i]);
+  }
+  uint8_t* o = out + p0;
+  if (m == kGroup && dword_stores) {
+    *reinterpret_cast<uint32_t*>(o) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);    // out is 4-byte aligned, p0 = 4 t
+  } else {
+#pragma unroll
+    for (int i = 0; i < kGroup; ++i) {
+      if (i < m) o[i] = static_cast<uint8_t>(b[i]);
+    }
+  }
+}
+
+// ---- the running maximum of per-ray maps (ns_map_max) ---------------------------------------------------------------------
+// np.max(disps) over all frames, kept on the device as state = (max over the values that are not NaN, 1.0f if a NaN was
+// seen).  Shaped as ns_image_sqerr: workgroup g owns the kMaxShare values from g * kMaxShare on and leaves (max, flag) in
+// partial[g]; a second launch of ONE workgroup folds the partials, and under `accumulate` the state already there, into the
+// state.  A maximum does not depend on the order of its comparisons: no atomics.  (-0.0 against +0.0 is whichever came first.)
+constexpr int kMaxPerThread = 8;
+constexpr int kMaxShare = kBlock * kMaxPerThread;
+
+struct MaxState {
+  float max, nan;
+};
+
+__device__ __forceinline__ void fold(MaxState& s, float x) {
+  if (x == x) s.max = x > s.max ? x : s.max;
+  else s.nan = 1.0f;
+}
+
+__device__ __forceinline__ void fold(MaxState& s, const MaxState& o) {
+  s.max = o.max > s.max ? o.max : s.max;                     // o.max is never NaN
+  s.nan = o.nan != 0.0f ? 1.0f : s.nan;
+}
+
+__device__ __forceinline__ MaxState block_fold(MaxState s, MaxState* wave_states) {   // valid in thread 0
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    MaxState o;
+    o.max = __shfl_xor(s.max, off, 64);
+    o.nan = __shfl_xor(s.nan, off, 64);
+    fold(s, o);
+  }
+  if ((threadIdx.x & 63) == 0) wave_states[threadIdx.x >> 6] = s;
+  __syncthreads();
+  MaxState r = wave_states[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / 64; ++w) fold(r, wave_states[w]);
+  return r;
+}
+
+__global__ void __launch_bounds__(kBlock)
+map_max_kernel(const float* __restrict__ map, int stride, int64_t n, MaxState* __restrict__ partial, int wide_loads) {
+  __shared__ MaxState wave_states[kBlock / 64];
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * kMaxShare;
+  MaxState s = {-INFINITY, 0.0f};
+  if (wide_loads) {                                          // packed, 16-byte aligned base: kMaxShare / 4 float4s per share
+#pragma unroll
+    for (int k = 0; k < kMaxPerThread / 4; ++k) {
+      const int64_t e = base + (static_cast<int64_t>(k) * kBlock + threadIdx.x) * 4;
+      if (e + 3 < n) {
+        const float4 a = *reinterpret_cast<const float4*>(map + e);
+        fold(s, a.x), fold(s, a.y), fold(s, a.z), fold(s, a.w);
+      } else {
+        for (int64_t j = e; j < n; ++j) fold(s, map[j]);     // the map's last, partial group of four
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < kMaxPerThread; ++k) {
+      const int64_t e = base + k * kBlock + threadIdx.x;
+      if (e < n) fold(s, map[e * stride]);
+    }
+  }
+  const MaxState r = block_fold(s, wave_states);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+__global__ void __launch_bounds__(kBlock)
+map_max_combine_kernel(const MaxState* __restrict__ partial, int n_partial, int accumulate, MaxState* state) {
+  __shared__ MaxState wave_states[kBlock / 64];
+  MaxState s = {-INFINITY, 0.0f};
+  for (int i = threadIdx.x; i < n_partial; i += kBlock) fold(s, partial[i]);
+  MaxState r = block_fold(s, wave_states);
+  if (threadIdx.x == 0) {
+    if (accumulate) {
+      const MaxState old = *state;
+      fold(r, old.max);                                      // a NaN in the old maximum (never written here) is a NaN seen
+      r.nan = old.nan != 0.0f ? 1.0f : r.nan;
+    }
+    *state = r;
+  }
+}
+
+int64_t map_max_groups(int64_t n) { return (n + kMaxShare - 1) / kMaxShare; }
+
+// what both map entries ask of (stride, n); `who` is the entry's name
+int check_map(const char* who, int64_t stride, int64_t n) {
+  if (n < 0) {
+    ns::set_error("%s: negative n", who);
+    return NS_E_INVALID;
+  }
+  if (n >= (int64_t(1) << 31)) {
+    ns::set_error("%s: n must be below 2^31", who);
+    return NS_E_INVALID;
+  }
+  if (stride != 1 && stride != 4) {
+    ns::set_error("%s: stride is 1 (a packed map) or 4 floats (a column of the [R,4] shard)", who);
+    return NS_E_INVALID;
+  }
+  return NS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -102,6 +249,49 @@ int ns_frame_to8b(const float* rgb_dev, int64_t rgb_stride, const float* alpha_d
     frame_to8b_kernel<3><<<grid, kBlock, 0, s>>>(rgb_dev, stride, alpha_dev, n, out_dev, wide_loads, dword_stores);
   else
     frame_to8b_kernel<4><<<grid, kBlock, 0, s>>>(rgb_dev, stride, alpha_dev, n, out_dev, wide_loads, dword_stores);
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+int64_t ns_map_max_workspace_bytes(int64_t n) {
+  if (n <= 0 || n >= (int64_t(1) << 31)) return 0;
+  return (map_max_groups(n) * static_cast<int64_t>(sizeof(MaxState)) + 255) / 256 * 256;
+}
+
+int ns_map_max(const float* map_dev, int64_t stride, int64_t n, int accumulate, float* state_dev, void* workspace_dev,
+               void* stream) {
+  const int rc = check_map(__func__, stride, n);
+  if (rc != NS_OK) return rc;
+  NS_REQUIRE(state_dev, "null pointer");
+  NS_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 3) == 0, "state_dev must be 4-byte aligned");
+  NS_REQUIRE(n == 0 || (map_dev && workspace_dev), "null pointer");
+  NS_REQUIRE((reinterpret_cast<uintptr_t>(workspace_dev) & 7) == 0, "workspace_dev must be 8-byte aligned");
+  if (n == 0 && accumulate) return NS_OK;                    // nothing to fold: the state stays
+  const int groups = static_cast<int>(map_max_groups(n));    // at most 2^20
+  MaxState* partial = static_cast<MaxState*>(workspace_dev);
+  hipStream_t s = ns::as_stream(stream);
+  if (n > 0) {
+    const int wide_loads = stride == 1 && (reinterpret_cast<uintptr_t>(map_dev) & 15) == 0;
+    map_max_kernel<<<groups, kBlock, 0, s>>>(map_dev, static_cast<int>(stride), n, partial, wide_loads);
+    NS_LAUNCH_CHECK();
+  }
+  map_max_combine_kernel<<<1, kBlock, 0, s>>>(partial, groups, accumulate != 0, reinterpret_cast<MaxState*>(state_dev));
+  NS_LAUNCH_CHECK();
+  return NS_OK;
+}
+
+int ns_map_to8b(const float* map_dev, int64_t stride, int64_t n, const float* denom_dev, uint8_t* out_dev, void* stream) {
+  const int rc = check_map(__func__, stride, n);
+  if (rc != NS_OK) return rc;
+  NS_REQUIRE((reinterpret_cast<uintptr_t>(denom_dev) & 3) == 0, "denom_dev must be 4-byte aligned");
+  if (n == 0) return NS_OK;
+  NS_REQUIRE(map_dev && out_dev, "null pointer");
+  const int64_t groups = (n + kGroup - 1) / kGroup;
+  const int grid = static_cast<int>((groups + kBlock - 1) / kBlock);          // at most 2^21 workgroups
+  const int wide_loads = stride == 1 && (reinterpret_cast<uintptr_t>(map_dev) & 15) == 0;
+  const int dword_stores = (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+  map_to8b_kernel<<<grid, kBlock, 0, ns::as_stream(stream)>>>(map_dev, static_cast<int>(stride), n, denom_dev, out_dev,
+                                                              wide_loads, dword_stores);
   NS_LAUNCH_CHECK();
   return NS_OK;
 }

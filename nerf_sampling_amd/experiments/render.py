@@ -58,6 +58,12 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="(not in the reference) --device-psnr, and the frames as NNN.png beside psnr.txt after all: quantised on the "
                    "device (ns_frame_to8b, to8b's bits), copied as bytes and encoded by nerf_utils.FrameWriter's threads while "
                    "the next view renders (Trainer(device_frames=True)).")
+@click.option("--device-video", "device_video", is_flag=True, default=False,
+              help="(not in the reference) --device-psnr, and instead of the test views the spiral render_poses, as the "
+                   "training's i_video branch writes it: renderonly_path_*/rgb/NNN.png and disp/NNN.png (rgb.mp4 / disp.mp4 too "
+                   "where imageio is installed) through nerf_utils.write_video -- one render per pose, the disparity divided by "
+                   "its maximum over all frames, which stays on the device (ns_map_max, ns_map_to8b; "
+                   "Trainer(device_video=True)).  There is no ground truth on the spiral: the PSNR printed is 0.")
 @click.option("--device-cloud", "device_cloud", is_flag=True, default=False,
               help="(not in the reference) Also select the scene's point cloud of the rendered views on the device "
                    "(ns_cloud_append, Trainer(device_cloud=True), nerf_utils.scene_cloud): scene_cloud.pt and scene_cloud.ply "
@@ -79,8 +85,10 @@ def main(**kw):
     k.update(single_image=kw["single_image"], single_ray=kw["single_ray"], save_scene_data=kw["save_scene_data"],
              i_print=kw["i_print"], compare_nerf=kw["nerf_compare"], use_nerf_max_pts=kw["nerf_max"],
              use_full_nerf=kw["nerf_full"], render_only=True, render_test=True)
-    if kw["device_psnr"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"]:
+    if kw["device_psnr"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"] or kw["device_video"]:
         k["device_eval"] = True
+    if kw["device_video"]:
+        k.update(device_video=True, render_test=False)
     if kw["device_frames"]:
         k["device_frames"] = True
     if kw["device_ssim"]:

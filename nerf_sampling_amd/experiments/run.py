@@ -58,6 +58,12 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="--device-eval, and the test views as NNN.png next to every psnr.txt (ns_frame_to8b on the device, "
                    "nerf_utils.FrameWriter's threads for the PNGs; Trainer(device_frames=True) / "
                    "FieldFitter.fit(test_frames=True)).")
+@click.option("--device-video", "device_video", is_flag=True, default=False,
+              help="--device-eval, and the reference's i_video branch: every i_video iterations the spiral render_poses as "
+                   "{expname}_spiral_{i:06d}_rgb/NNN.png and ..._disp/NNN.png (rgb.mp4 / disp.mp4 too where imageio is "
+                   "installed) through nerf_utils.write_video -- one render per pose, the disparity's maximum over all frames "
+                   "kept on the device (ns_map_max, ns_map_to8b; Trainer(device_video=True)).  Not with --fit-field, which "
+                   "renders no spiral.")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -83,8 +89,10 @@ def main(**kw):
         k["fused_step"] = True
     if kw["device_batches"]:
         k["device_batches"] = kw["device_batches"]
-    if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"]:
+    if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"] or kw["device_video"]:
         k["device_eval"] = True
+    if kw["device_video"]:
+        k["device_video"] = True
     if kw["device_frames"]:
         k["device_frames"] = True
     if kw["device_ssim"]:
@@ -94,6 +102,8 @@ def main(**kw):
     if kw["fit_field"]:
         if kw["device_depth"]:
             raise click.UsageError("--device-depth scores a DepthNet's depth; --fit-field trains none")
+        if kw["device_video"]:
+            raise click.UsageError("--device-video writes the DepthNet training's spiral; --fit-field renders none")
         k.update(ft_path=None)
         return fit_field(load_obj_from_config(cfg=config), kw["iters"], gemm_engine=kw["gemm_engine"])
     trainer = load_obj_from_config(cfg=config)

@@ -414,7 +414,11 @@ class FrameWriter:
 
     ``close()`` drains the queue, joins the workers, releases the buffers and raises the first exception a worker met (the
     other frames are still written); it may be called twice, and a ``with`` block calls it -- quietly when the block itself
-    raised, so that the block's exception is the one that surfaces."""
+    raised, so that the block's exception is the one that surfaces.
+
+    ``channels=1`` is a writer of per-ray maps: a slot is [H,W] uint8, saved as a mode-L PNG, and frames come in through
+    ``put_map(k, map, denom=None)`` -- ops.map_to8b, the map divided by a float that lies in device memory -- instead of
+    ``put``; from the slot on the pipeline is the same."""
 
     MAX_WORKERS = 8
 
@@ -425,8 +429,8 @@ class FrameWriter:
         H, W, channels, n_buffers, workers = int(H), int(W), int(channels), int(n_buffers), int(workers)
         if savedir is None:
             raise ValueError("FrameWriter: a directory to write into")
-        if H < 1 or W < 1 or channels not in (3, 4):
-            raise ValueError(f"FrameWriter: a frame of at least 1 x 1 pixels with 3 or 4 channels, got {H} x {W} x {channels}")
+        if H < 1 or W < 1 or channels not in (1, 3, 4):
+            raise ValueError(f"FrameWriter: a frame of at least 1 x 1 pixels with 1, 3 or 4 channels, got {H} x {W} x {channels}")
         if n_buffers < 1 or workers < 1:
             raise ValueError("FrameWriter: at least one buffer and one worker")
         if compress_level is not None and not 0 <= int(compress_level) <= 9:
@@ -442,9 +446,10 @@ class FrameWriter:
         self.savedir, self.H, self.W, self.channels = savedir, H, W, channels
         self.compress_level = None if compress_level is None else int(compress_level)
         self.device, self.n_buffers, self.workers = device, n_buffers, min(workers, self.MAX_WORKERS)
-        self._dev = torch.empty((n_buffers, H, W, channels), dtype=torch.uint8, device=device)
+        slots = (n_buffers, H, W) if channels == 1 else (n_buffers, H, W, channels)      # [H,W] is PIL's mode L
+        self._dev = torch.empty(slots, dtype=torch.uint8, device=device)
         # device="cpu" explicitly: the experiment scripts switch torch's default device to cuda
-        self._host = torch.empty((n_buffers, H, W, channels), dtype=torch.uint8, device="cpu", pin_memory=True)
+        self._host = torch.empty(slots, dtype=torch.uint8, device="cpu", pin_memory=True)
         self._quantised = [torch.cuda.Event() for _ in range(n_buffers)]
         self._copied = [torch.cuda.Event() for _ in range(n_buffers)]
         self._stream = torch.cuda.Stream(device)
@@ -486,18 +491,40 @@ class FrameWriter:
     def put(self, k, rgb, alpha=None):
         """Queue frame ``k``: ``rgb`` fp32 [H*W,3] on the writer's device (contiguous, or the [:, :3] view of a [H*W,4] shard),
         ``alpha`` fp32 [H*W] for the fourth channel of a 4-channel writer (None: opaque)."""
-        if self._closed:
-            raise RuntimeError("FrameWriter.put after close()")
-        k = int(k)
-        if k < 0:
-            raise ValueError("FrameWriter.put: a frame number >= 0")
+        k = self._check_put("put", k)
+        if self.channels == 1:
+            raise ValueError("FrameWriter.put: a one-channel writer takes maps (put_map)")
         if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.device == self.device
                 and tuple(rgb.shape) == (self.H * self.W, 3)):
             raise ValueError(f"FrameWriter.put: rgb is a float32 tensor of shape ({self.H * self.W}, 3) on {self.device}")
+        self._submit(k, lambda slot: ops.frame_to8b(rgb, alpha=alpha, out=slot, channels=self.channels))
+
+    def put_map(self, k, map, denom=None):
+        """Queue frame ``k`` of a one-channel writer: ``map`` fp32 [H*W] on the writer's device (contiguous, or the [:, 3] view of
+        a [H*W,4] shard), quantised as ops.map_to8b does -- divided by ``denom``, one float32 element in device memory that the
+        kernel reads (None: no division)."""
+        k = self._check_put("put_map", k)
+        if self.channels != 1:
+            raise ValueError(f"FrameWriter.put_map: a {self.channels}-channel writer takes rgb frames (put)")
+        if not (isinstance(map, torch.Tensor) and map.is_cuda and map.device == self.device
+                and tuple(map.shape) == (self.H * self.W,)):
+            raise ValueError(f"FrameWriter.put_map: map is a float32 tensor of shape ({self.H * self.W},) on {self.device}")
+        self._submit(k, lambda slot: ops.map_to8b(map, denom=denom, out=slot))
+
+    def _check_put(self, who, k):
+        if self._closed:
+            raise RuntimeError(f"FrameWriter.{who} after close()")
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"FrameWriter.{who}: a frame number >= 0")
+        return k
+
+    def _submit(self, k, quantise):
+        """a free slot, ``quantise(slot's device tensor)`` on the current stream, the copy on the writer's, the job to the workers"""
         s = self._free.get()                                   # blocks only while every slot is in flight
         queued = False
         try:
-            ops.frame_to8b(rgb, alpha=alpha, out=self._dev[s], channels=self.channels)
+            quantise(self._dev[s])
             compute = torch.cuda.current_stream(self.device)
             self._quantised[s].record(compute)
             self._stream.wait_event(self._quantised[s])
@@ -640,10 +667,11 @@ def score_views(dataset, image_ids, poses, render_frame, savedir=None, return_fr
 
 
 def hierarchical_frame_renderer(network_fn, network_fine, H, W, K, N_samples, N_importance, lindisp, white_bkgd, near, far,
-                                perturb=0.0, device="cuda"):
+                                perturb=0.0, device="cuda", with_disp=False):
     """``render_frame`` of score_views through ops.render_rays_hierarchical: the vanilla coarse + fine pass of a whole view from
     its camera, one call, no per-sample outputs.  The random draws of ``perturb`` > 0 come from a generator of this renderer's
-    own, in _vanilla_one_call's order."""
+    own, in _vanilla_one_call's order.  ``with_disp``: ``render_frame`` returns (rgb, disp [H*W]) -- the same call's second
+    output, which it writes anyway."""
     gen = None
 
     def draw(n):
@@ -657,10 +685,11 @@ def hierarchical_frame_renderer(network_fn, network_fine, H, W, K, N_samples, N_
         t_rand = draw(int(N_samples)) if perturb > 0.0 else None
         u = draw(int(N_importance)) if perturb != 0.0 and int(N_importance) > 0 else None
         fine = network_fine.packed() if (network_fine is not None and int(N_importance) > 0) else None
-        return ops.render_rays_hierarchical(network_fn.packed(), fine, camera=(H, W, K, c2w, 0, H), n_coarse=int(N_samples),
-                                            n_importance=int(N_importance), lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
-                                            near=float(near), far=float(far), t_rand=t_rand, u=u, extras=False, device=device,
-                                            workspace=workspace)["rgb"]
+        out = ops.render_rays_hierarchical(network_fn.packed(), fine, camera=(H, W, K, c2w, 0, H), n_coarse=int(N_samples),
+                                           n_importance=int(N_importance), lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
+                                           near=float(near), far=float(far), t_rand=t_rand, u=u, extras=False, device=device,
+                                           workspace=workspace)
+        return (out["rgb"], out["disp"]) if with_disp else out["rgb"]
 
     return render_frame
 
@@ -721,10 +750,12 @@ def _depth_frame_renderer(kw, trainer, net, H, W, K, dev):
     return render_frame
 
 
-def _one_call_frame_renderer(kw, H, W, K, dev):
+def _one_call_frame_renderer(kw, H, W, K, dev, with_disp=False):
     """``render_frame(c2w, workspace)`` -> rgb [H*W,3] of score_views / write_views for the configuration ``kw`` (a trainer's
     render_kwargs): ops.render_rays_hierarchical under trainer.use_full_nerf, otherwise ops.render_rays_depthnet with the
-    choices of render_rays_test's one-call branch; None when the configuration is neither's."""
+    choices of render_rays_test's one-call branch; None when the configuration is neither's.  ``with_disp`` (write_video):
+    ``render_frame`` returns (rgb, disp [H*W]) -- the disparity map every one-call render writes beside its rgb
+    (ops._rgb_disp_outputs), handed back instead of dropped: no further render and no copy."""
     trainer = kw["trainer"]
     net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
     with torch.no_grad():
@@ -739,7 +770,8 @@ def _one_call_frame_renderer(kw, H, W, K, dev):
     if trainer.use_full_nerf:
         return hierarchical_frame_renderer(kw["network_fn"], kw.get("network_fine"), H, W, K, kw["N_samples"],
                                            trainer.N_importance, kw.get("lindisp", False), kw["white_bkgd"],
-                                           kw["near"], kw["far"], perturb=float(kw.get("perturb", 0.0)), device=dev)
+                                           kw["near"], kw["far"], perturb=float(kw.get("perturb", 0.0)), device=dev,
+                                           with_disp=with_disp)
     dn = kw["depth_network"]
     gen = None
 
@@ -752,8 +784,9 @@ def _one_call_frame_renderer(kw, H, W, K, dev):
                 gen = torch.Generator(device=dev)
                 gen.manual_seed(0)
             noise = torch.randn(H * W, int(trainer.n_depth_samples) - 1, device=dev, generator=gen)
-        return _depthnet_one_call(dn, net, trainer, camera=(H, W, K, c2w, 0, H), extras=False, device=dev, noise=noise,
-                                  workspace=workspace)["rgb"]
+        out = _depthnet_one_call(dn, net, trainer, camera=(H, W, K, c2w, 0, H), extras=False, device=dev, noise=noise,
+                                 workspace=workspace)
+        return (out["rgb"], out["disp"]) if with_disp else out["rgb"]
 
     return render_frame
 
@@ -889,6 +922,130 @@ def write_views(poses, hwf, K, render_kwargs, savedir, return_frames=False, n_bu
             if return_frames:
                 kept_frames.append(rgb)
     return (len(poses), kept_frames) if return_frames else len(poses)
+
+
+VIDEO_MAX_DEVICE_BYTES = 2 ** 31              # write_video's default budget for the fp32 disparity maps it holds
+_video_png_notice_given = False
+
+
+def disp_to8b_host(disps, m):
+    """write_video's disparity bytes in numpy: to8b(disps / m) of Trainer.py:371-376 -- numpy's float32 division, clip,
+    multiply and cast -- with a NaN quotient written as 0 (numpy leaves that cast to the platform)"""
+    import numpy as np
+
+    with np.errstate(all="ignore"):
+        q = np.asarray(disps, dtype=np.float32) / np.float32(m)
+        return np.where(np.isnan(q), 0, 255 * np.clip(q, 0, 1)).astype(np.uint8)
+
+
+def _write_mp4s(base, n_views):
+    """{base}rgb.mp4 and {base}disp.mp4 by the reference's imageio.mimwrite(..., fps=30, quality=8) (Trainer.py:365-376), from
+    the bytes of the PNG sequences; without imageio the PNGs are the deliverable, said once.  -> whether they were written"""
+    global _video_png_notice_given
+    import numpy as np
+
+    try:
+        import imageio
+    except ImportError:
+        if not _video_png_notice_given:
+            print("write_video: imageio is not installed; the PNG sequences under rgb/ and disp/ are the deliverable "
+                  "(no rgb.mp4 / disp.mp4)")
+            _video_png_notice_given = True
+        return False
+    from PIL import Image
+
+    for name in ("rgb", "disp"):
+        frames = []
+        for k in range(n_views):
+            with Image.open(os.path.join(base + name, "{:03d}.png".format(k))) as im:
+                frames.append(np.array(im))
+        imageio.mimwrite(base + name + ".mp4", np.stack(frames, 0), fps=30, quality=8)
+    return True
+
+
+def write_video(poses, hwf, K, render_kwargs, base, n_buffers=4, workers=4, compress_level=None, device="cuda",
+                max_device_bytes=VIDEO_MAX_DEVICE_BYTES, return_maps=False):
+    """The two sequences of the reference's i_video branch (Trainer.py:350-376: ``to8b(rgbs)`` and
+    ``to8b(disps / np.max(disps))`` of render_path over the spiral) without render_path: every pose is ONE one-call render (the
+    frame renderer of evaluate_views, handing back the disparity map it writes anyway).  The rgb frame goes at once through a
+    3-channel FrameWriter to ``{base}rgb/{k:03d}.png``.  The disparity is divided by the maximum over ALL frames, so no frame
+    can be quantised before the last one is rendered: the fp32 map is copied device-to-device into slot k of one preallocated
+    [n_views, H*W] stack and folded into a two-float state on the device (ops.map_max, accumulate from the second view on).
+    After the last view every slot goes through a one-channel FrameWriter (put_map: ops.map_to8b with ``state[:1]`` as the
+    divisor, read by the kernel) to ``{base}disp/{k:03d}.png``.  Nothing is read back until the writers are closed; then the
+    state, once.  -> {"n_views", "disp_max", "has_nan"}, and with ``return_maps`` "maps": the stack, on the device.
+
+    A disparity can be NaN here and in the reference: torch.max(1e-10, depth / acc) propagates a NaN depth (finish_totals in
+    ns_composite_ray.h; a DepthNet ray that misses the sphere has one).  np.max of the reference is then NaN and its disp.mp4
+    black.  This path divides by the maximum over the values that are not NaN (``disp_max``; -inf when there are none), writes
+    NaN pixels as 0 and reports ``has_nan``.  Where no disparity is NaN the files hold the reference's expression bit for bit
+    (``disp_to8b_host`` states it in numpy) -- its weakness included: a ray without any opacity has depth 0 and disparity
+    1 / 1e-10 = 1e10, which is then the maximum of the sequence, and every other pixel is 0, as in the reference's video.
+
+    The stack costs n_views * H * W * 4 bytes (102 MB for the 40-pose spiral at 800 x 800); more than ``max_device_bytes``
+    raises ValueError naming the bytes needed before anything is rendered or any directory is made.  With imageio installed
+    ``{base}rgb.mp4`` and ``{base}disp.mp4`` are also written, as the reference does, from the PNGs' bytes; without it the PNG
+    sequences are the deliverable.  ``n_buffers`` / ``workers`` / ``compress_level``: each FrameWriter's (workers are capped by
+    FrameWriter.MAX_WORKERS, never sized by the CPU count).  A configuration the one-call renderers do not take goes through
+    render_path and numpy, with evaluate_views' one warning, and writes the same files."""
+    import numpy as np
+
+    if base is None:
+        raise ValueError("write_video writes {base}rgb/ and {base}disp/: base is required")
+    n_views = len(poses)
+    if n_views == 0:
+        raise ValueError("write_video: at least one pose")
+    H, W = int(hwf[0]), int(hwf[1])
+    need = n_views * H * W * 4
+    if need > int(max_device_bytes):
+        raise ValueError(f"write_video: the disparity maps of {n_views} views of {H} x {W} need {need} bytes on the device, "
+                         f"more than max_device_bytes = {int(max_device_bytes)}")
+    kw = render_kwargs
+    trainer = kw["trainer"]
+    base = str(base)
+    rgb_dir, disp_dir = base + "rgb", base + "disp"
+    dev = torch.device(device)
+    writer_kw = dict(n_buffers=n_buffers, workers=workers, compress_level=compress_level)
+    render_frame = _one_call_frame_renderer(kw, H, W, K, dev, with_disp=True)
+    if render_frame is None:
+        _warn_render_path_fallback("write_video")
+        from PIL import Image
+
+        save_kw = {} if compress_level is None else {"compress_level": int(compress_level)}
+        for d in (rgb_dir, disp_dir):
+            os.makedirs(d, exist_ok=True)
+        with torch.no_grad():
+            rgbs, disps, _ = render_path(poses, hwf, K, trainer.chunk, kw, step=0, savedir=rgb_dir)
+        disps = np.asarray(disps, dtype=np.float32)
+        nan = np.isnan(disps)
+        disp_max = float(disps[~nan].max()) if not nan.all() else float("-inf")
+        for k, d8 in enumerate(disp_to8b_host(disps, disp_max)):
+            Image.fromarray(d8.reshape(H, W)).save(os.path.join(disp_dir, "{:03d}.png".format(k)), **save_kw)
+        _write_mp4s(base, n_views)
+        out = {"n_views": n_views, "disp_max": disp_max, "has_nan": bool(nan.any())}
+        if return_maps:
+            out["maps"] = torch.from_numpy(disps.reshape(n_views, H * W)).to(dev)
+        return out
+    workspace = ops.RenderWorkspace()
+    stack = torch.empty((n_views, H * W), dtype=torch.float32, device=dev)
+    state = torch.empty((2,), dtype=torch.float32, device=dev)
+    max_ws = torch.empty((max(ops.map_max_workspace_bytes(H * W), 8),), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        with FrameWriter(rgb_dir, H, W, device=dev, **writer_kw) as writer:
+            for k, c2w in enumerate(poses):
+                rgb, disp = render_frame(c2w[:3, :4], workspace)
+                writer.put(k, rgb)
+                stack[k].copy_(disp)                                   # device to device; disp is this call's own tensor
+                ops.map_max(stack[k], state=state, accumulate=k > 0, workspace=max_ws)
+        with FrameWriter(disp_dir, H, W, channels=1, device=dev, **writer_kw) as writer:
+            for k in range(n_views):
+                writer.put_map(k, stack[k], denom=state[:1])           # the divisor stays where it is
+    disp_max, has_nan = (float(v) for v in state.cpu())                # the one read-back, after the writers are closed
+    _write_mp4s(base, n_views)
+    out = {"n_views": n_views, "disp_max": disp_max, "has_nan": has_nan != 0.0}
+    if return_maps:
+        out["maps"] = stack
+    return out
 
 
 # ---- the scene's point cloud selected on the device (the reference: scene_data.pt on the host, then experiments/plot.py) ----

@@ -409,6 +409,84 @@ def frame_to8b(rgb, alpha=None, out=None, channels: int = 3):
     return out.view(R, channels)
 
 
+# ---- the turntable's disparity sequence (Trainer.py:371-376 to8b(disps / np.max(disps)), the divisor kept on the device) ----
+def _map_layout(t, name: str):
+    """(R, stride in floats) of a per-ray map: a contiguous fp32 [R] on the device, or the [:, 3] view of a contiguous [R,4]
+    shard (the one-call renderers' interleaved layout)"""
+    if not isinstance(t, Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); this path has no CPU fallback")
+    if not (t.dtype == torch.float32 and t.dim() == 1):
+        raise ValueError(f"{name}: a float32 device tensor of shape (R,)")
+    R = int(t.shape[0])
+    if R >= 2 ** 31:
+        raise ValueError(f"{name}: R = {R} is not below 2^31")
+    if t.is_contiguous():
+        return R, 1
+    if int(t.stride(0)) == 4:
+        return R, 4
+    raise ValueError(f"{name}: contiguous [R], or the [:, 3] view of a contiguous [R,4] shard")
+
+
+def map_max_workspace_bytes(n: int) -> int:
+    """ns_map_max_workspace_bytes: the per-workgroup (max, flag) pairs ``map_max`` needs for a map of ``n`` values"""
+    return int(_lib.load().ns_map_max_workspace_bytes(int(n)))
+
+
+def map_max(map, state=None, accumulate: bool = False, workspace=None):
+    """ns_map_max: the maximum of a per-ray map folded into a two-float state on the device -- ``np.max(disps)`` of
+    Trainer.py:371-376 kept where the frames are, so that the divisor of a whole sequence is never read back between views.
+    ``state[0]`` is the maximum over the values that are not NaN (-inf when there are none), ``state[1]`` is 1.0 if a NaN was
+    seen and 0.0 otherwise.  ``map``: fp32 [R] on the device, contiguous or the ``[:, 3]`` view of a contiguous [R,4] shard.
+    ``state``: a contiguous float32 [2] tensor on map's device (None: allocated).  ``accumulate`` False initialises the state
+    from this map alone, True folds the map into the state already there (it needs ``state``): calls over the maps of a
+    sequence leave the state of their concatenation.  ``workspace``: a contiguous 8-byte-aligned device tensor of at least
+    ``map_max_workspace_bytes(R)`` bytes (None: allocated for the call).  Returns the state tensor.  Asynchronous on the
+    current stream, nothing is read back; what is wrong with the arguments raises before the launch."""
+    R, stride = _map_layout(map, "map")
+    accumulate = bool(accumulate)
+    if state is None:
+        if accumulate:
+            raise ValueError("accumulate=True folds the map into a state: state is required")
+        state = torch.empty((2,), dtype=torch.float32, device=map.device)
+    elif not (isinstance(state, Tensor) and state.is_cuda and state.device == map.device and state.dtype == torch.float32
+              and tuple(state.shape) == (2,) and state.is_contiguous()):
+        raise ValueError("state: a contiguous float32 tensor of shape (2,) on map's device")
+    need = map_max_workspace_bytes(R)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=map.device) if need else None
+    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == map.device
+              and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need
+              and workspace.data_ptr() % 8 == 0):
+        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on map's device")
+    check(_lib.load().ns_map_max(_ptr(map) if R else None, stride, R, int(accumulate), _ptr(state),
+                                 _ptr(workspace) if R else None, _stream(map.device)), "ns_map_max")
+    return state
+
+
+def map_to8b(map, denom=None, out=None):
+    """ns_map_to8b: a per-ray map as 8-bit pixels, (uint8) trunc(255 * clip(x / denom, 0, 1)) -- ``to8b(disps / np.max(disps))``
+    of Trainer.py:371-376 with the divisor read from device memory: one correctly rounded fp32 division (numpy's float32 /
+    float32), then ``frame_to8b``'s clip, multiply and truncation; a NaN quotient (a NaN value, 0 / 0, inf / inf, a NaN divisor)
+    gives 0.  ``map``: as ``map_max``'s.  ``denom``: a float32 device tensor of one element on map's device -- ``state[:1]`` of
+    ``map_max`` -- or None: no division.  ``out``: a contiguous uint8 tensor of R elements on map's device (a slot of a ring
+    of frames; it may start at any byte); None: allocated.  Returns the bytes as a uint8 tensor [R].  Asynchronous on the
+    current stream, nothing is read back; what is wrong with the arguments raises before the launch."""
+    R, stride = _map_layout(map, "map")
+    if denom is not None and not (isinstance(denom, Tensor) and denom.is_cuda and denom.device == map.device
+                                  and denom.dtype == torch.float32 and denom.numel() == 1):
+        raise ValueError("denom: a float32 tensor of one element on map's device, or None")
+    if out is None:
+        out = torch.empty((R,), dtype=torch.uint8, device=map.device)
+    elif not (isinstance(out, Tensor) and out.dtype == torch.uint8 and out.device == map.device and out.is_contiguous()
+              and out.numel() == R):
+        raise ValueError(f"out: a contiguous uint8 tensor of {R} elements on map's device")
+    if R > 0:
+        check(_lib.load().ns_map_to8b(_ptr(map), stride, R, _ptr(denom), _ptr(out), _stream(map.device)), "ns_map_to8b")
+    return out.view(R)
+
+
 # ---- a2 -------------------------------------------------------------------------------------------
 def sphere_intersect(o: Tensor, d: Tensor, radius: float) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()

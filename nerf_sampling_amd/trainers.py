@@ -5,7 +5,8 @@ sample_coarse_points :579-649, sample_fine_points :651-710, _sample_points :553-
 core_optimization_loop :506-544, the two batch samplers :232-269 / :400-475), trainers/Blender.py,
 nerf_sampling/trainers/sampling_trainer.py (DepthNetTrainer.raw2outputs :153-230, create_nerf_model :54-122,
 save_rays_data :124-138).  ``train`` renders (render_only) or runs the DepthNet optimisation loop on the HIP backward
-kernels (autograd.py); wandb / optuna logging and the mp4 writer are out of scope.
+kernels (autograd.py); wandb / optuna logging is out of scope, and the i_video branch is honoured under
+device_video (PNG sequences; the mp4s where imageio is installed).
 """
 
 from __future__ import annotations
@@ -29,8 +30,9 @@ class Trainer:
     ``device_ssim`` (ssim.txt) and ``device_depth`` (depth.txt: per view the MSE of the DepthNet's placed samples and of its
     own depth against the field's max-weight depth, "[TRAIN] Iter: i test depth MSE: x mean MSE: y"; the field's depth maps
     of the i_test views are rendered once while train_depth_net_only keeps the field frozen and the test perturb is 0) and
-    ``device_frames`` (NNN.png beside every psnr.txt, quantised on the device and encoded by nerf_utils.FrameWriter's threads).
-    All three need device_eval."""
+    ``device_frames`` (NNN.png beside every psnr.txt, quantised on the device and encoded by nerf_utils.FrameWriter's threads)
+    and ``device_video`` (i_video honoured by train(): the spiral's rgb and disparity sequences through nerf_utils.write_video).
+    All four need device_eval."""
 
     def __init__(self, dataset_type, basedir, expname, no_batching, datadir, device="cpu", render_test=False,
                  config_path=None, N_rand=32 * 32 * 4, render_only=False, chunk=1024 * 32, render_factor=0,
@@ -43,7 +45,8 @@ class Trainer:
                  save_scene_data=False, compare_nerf=False, use_nerf_max_pts=False, use_full_nerf=False,
                  hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False,
                  device_ssim: bool = False, device_depth: bool = False, device_cloud: bool = False,
-                 cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False):
+                 cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False,
+                 device_video: bool = False):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -94,6 +97,14 @@ class Trainer:
         self.device_frames = bool(device_frames)
         if self.device_frames and not self.device_eval:
             raise ValueError("device_frames writes the frames of the device evaluation: it needs device_eval=True")
+        # device_video (not in the reference's form; default off): train() honours i_video as the reference's i_video branch
+        # does (Trainer.py:350-376) -- every i_video iterations render_poses, the spiral, goes through nerf_utils.write_video:
+        # {expname}_spiral_{i:06d}_rgb/NNN.png and ..._disp/NNN.png (and the two mp4s where imageio is installed), one one-call
+        # render per pose, the disparity's maximum kept on the device (ns_map_max, ns_map_to8b).  render() without render_test
+        # writes the spiral the same way.  Off, i_video stays unused.
+        self.device_video = bool(device_video)
+        if self.device_video and not self.device_eval:
+            raise ValueError("device_video renders the spiral as the device evaluation renders its views: it needs device_eval=True")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -192,8 +203,8 @@ class Trainer:
 
     def render(self, render_test, save_scene_data, images, i_test, render_poses, hwf, render_kwargs_test):
         """renderonly_{test|path}_{step:06d}/ with NNN.png, psnr.txt[, scene_data.pt] -- Trainer.py:181-230
-        (the mp4 of the reference needs imageio-ffmpeg and is not written).  Under device_cloud also scene_cloud.pt and
-        scene_cloud.ply of the same poses (nerf_utils.scene_cloud)."""
+        (no mp4; under device_video without render_test: rgb/NNN.png and disp/NNN.png through nerf_utils.write_video).  Under
+        device_cloud also scene_cloud.pt and scene_cloud.ply of the same poses (nerf_utils.scene_cloud)."""
         with torch.no_grad():
             images = images[i_test] if render_test else None
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
@@ -216,6 +227,11 @@ class Trainer:
                                                    savedir=testsavedir, ssim=self.device_ssim, depth=self.device_depth,
                                                    frames=self.device_frames)
                 return scores[1]
+            if self.device_eval and self.device_video and not render_test and self.render_factor == 0:
+                # the spiral as the i_video branch writes it: rgb/NNN.png and disp/NNN.png under the directory
+                nerf_utils.write_video(render_poses, hwf, self.K, render_kwargs_test, os.path.join(testsavedir, ""),
+                                       device="cuda" if self.device == "cuda" else self.device)
+                return 0.0
             if self.device_eval and self.device_frames and not render_test and self.render_factor == 0:
                 # poses without ground truth (the spiral): the same loop without scores; render_path's average is 0 there
                 nerf_utils.write_views(render_poses, hwf, self.K, render_kwargs_test, testsavedir,
@@ -251,7 +267,8 @@ class Trainer:
         """Trainer.train (Trainer.py:712-787): load data, build / reload the networks; render_only: render the test
         (or spiral) poses and return the average PSNR; otherwise the DepthNet optimisation loop (random ray batches from
         one image, or -- use_batching -- from the shuffled rays of all training images), checkpoints every i_weights.
-        With device_eval the i_test views are scored every i_testset iterations (evaluate_testset)."""
+        With device_eval the i_test views are scored every i_testset iterations (evaluate_testset); with device_video the
+        spiral is written every i_video iterations (nerf_utils.write_video)."""
         hwf, poses, i_test, i_val, i_train, images, render_poses = self.load_data()
         dev = "cuda" if self.device == "cuda" else self.device
         if self.render_test:
@@ -306,6 +323,11 @@ class Trainer:
                     avg, avg_ssim = avg
                     print(f"[TRAIN] Iter: {i} test SSIM: {avg_ssim}")
                 print(f"[TRAIN] Iter: {i} test PSNR: {avg}")
+            if self.device_video and dev == "cuda" and self.i_video and i % self.i_video == 0 and i > 0:
+                moviebase = os.path.join(self.basedir, self.expname, "{}_spiral_{:06d}_".format(self.expname, i))
+                video = nerf_utils.write_video(render_poses, hwf, self.K, render_kwargs_test, moviebase, device=dev)
+                print(f"[TRAIN] Iter: {i} spiral of {video['n_views']} views written to {moviebase}rgb/ and {moviebase}disp/ "
+                      f"(max disparity {video['disp_max']}{', NaN pixels written as 0' if video['has_nan'] else ''})")
             if i % self.i_weights == 0:
                 path = os.path.join(self.basedir, self.expname, "{:06d}.tar".format(i))
                 utils.save_state(self.global_step, render_kwargs_train["network_fn"],

@@ -7,9 +7,11 @@ without depth, with depth=True and the field's depth maps rendered afresh, and w
 alternating; then ns_depth_sqerr alone at (640 000, 64) and (640 000, 1).  --frames: render_path(gt_imgs=..., savedir=...),
 evaluate_views without frames and evaluate_views(frames=True) -- the PNGs written by nerf_utils.FrameWriter -- the three
 alternating; then evaluate_views(frames=...) at workers = 1, 2, 4, 8 with PIL's default compress_level and with 1; then
-ns_frame_to8b alone beside ns_image_sqerr.
+ns_frame_to8b alone beside ns_image_sqerr.  --video: the 40-pose spiral as the reference's i_video branch writes it -- render_path,
+numpy's to8b(rgbs) and to8b(disps / np.max(disps)), PIL saves of both sequences -- against nerf_utils.write_video, the two
+alternating; then ns_map_max and ns_map_to8b alone on a packed map and on the [:, 3] column of a shard.
 
-    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim | --depth | --frames]
+    python tools/bench_device_eval.py [--views 6] [--size 800] [--samples 64] [--ssim | --depth | --frames | --video]
 """
 import argparse
 import os
@@ -41,14 +43,21 @@ def main():
     ap.add_argument("--frames", action="store_true",
                     help="render_path with PNGs, evaluate_views without and with frames=True; the workers x compress_level "
                          "table; ns_frame_to8b alone")
+    ap.add_argument("--video", action="store_true",
+                    help="the 40-pose spiral: render_path + numpy + PIL saves of the rgb and disparity sequences against "
+                         "write_video; ns_map_max and ns_map_to8b alone")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     _coarse, fine, dn, _params = bench.build_modules("shapes_fit", dev)
     H = W = a.size
     focal, K = synthetic.blender_intrinsics(H, W)
+    if a.video:                                              # the whole spiral, and no ground truth: nothing is scored
+        a.views = 40
     poses = synthetic.render_poses(40)[:: 40 // a.views][: a.views].cpu()
-    gt = np.stack([analytic_scene.frame(H, W, K, p[:3, :4], device=dev)[0].float().cpu().numpy() for p in poses])
-    ds = DeviceRayDataset(gt, poses.numpy().astype(np.float32), K, [0])
+    gt = ds = None
+    if not a.video:
+        gt = np.stack([analytic_scene.frame(H, W, K, p[:3, :4], device=dev)[0].float().cpu().numpy() for p in poses])
+        ds = DeviceRayDataset(gt, poses.numpy().astype(np.float32), K, [0])
     ops.set_compute_dtype("bf16")
     ops.set_psnr_guard(True)
     tr = DepthNetTrainer(dataset_type="blender", basedir="/tmp", expname="x", no_batching=True, datadir="", half_res=False,
@@ -80,6 +89,8 @@ def main():
             torch.cuda.synchronize()
             return 1e3 * (time.perf_counter() - t0) / a.views, float(psnr)
 
+    if a.video:
+        return bench_video(a, dev, poses, [H, W, focal], K, kw, tr, timed)
     if a.depth:
         return bench_depth(a, dev, ds, ids, poses, [H, W, focal], K, kw, timed)
     if a.frames:
@@ -182,6 +193,70 @@ def bench_frames(a, dev, ds, ids, poses, hwf, K, kw, timed, host_path, device_pa
             torch.cuda.synchronize()
             per.append(1e3 * e0.elapsed_time(e1) / reps)
         print(f"  {name:<34s} {statistics.median(per):8.2f} us per {H} x {W} frame   (spread {max(per) - min(per):.2f})")
+
+
+def bench_video(a, dev, poses, hwf, K, kw, tr, timed):
+    """--video: the host route of the reference's i_video branch (Trainer.py:350-376, the mp4 encoder replaced by PIL saves of
+    the same bytes) and write_video in alternation, ms per view of the 40-pose spiral; then ns_map_max (both launches) and
+    ns_map_to8b alone on an 800 x 800 map in both layouts"""
+    from PIL import Image
+
+    from nerf_sampling_amd.run_nerf_helpers import to8b
+
+    H, W = hwf[0], hwf[1]
+
+    def host_route(d):
+        with torch.no_grad():
+            rgbs, disps, _ = nerf_utils.render_path(poses, hwf, K, tr.chunk, kw, step=0)
+        with np.errstate(all="ignore"):
+            rgb8, disp8 = to8b(rgbs), to8b(disps / np.max(disps))
+        for name, frames in (("rgb", rgb8), ("disp", disp8)):
+            os.makedirs(os.path.join(d, name))
+            for k, f in enumerate(frames):
+                Image.fromarray(f).save(os.path.join(d, name, "{:03d}.png".format(k)))
+        return float(np.max(disps))
+
+    def device_route(d):
+        return nerf_utils.write_video(poses, hwf, K, kw, os.path.join(d, ""))["disp_max"]
+
+    paths = [("render_path + numpy + PIL", host_route), ("write_video", device_route)]
+    for _name, fn in paths:
+        timed(fn)                                            # warm-up: pinned buffers, packed streams, workspaces
+    runs = [[] for _ in paths]
+    for _ in range(a.alternations):
+        for r, (_name, fn) in zip(runs, paths):
+            r.append(timed(fn))
+    print(f"{H} x {W} x {a.samples}, bf16 + PSNR guard, the {a.views}-pose spiral, rgb and disparity sequences as PNGs; "
+          f"ms per view, median of {a.alternations} alternations")
+    for (name, _fn), r in zip(paths, runs):
+        t = [ms for ms, _ in r]
+        print(f"  {name:<28s} {statistics.median(t):8.2f}   (spread {max(t) - min(t):.2f})   max disparity {r[-1][1]:.6g}")
+    packed = torch.rand((H * W,), device=dev)
+    column = torch.rand((H * W, 4), device=dev)[:, 3]
+    state = torch.empty((2,), dtype=torch.float32, device=dev)
+    ws = torch.empty((ops.map_max_workspace_bytes(H * W),), dtype=torch.uint8, device=dev)
+    out8 = torch.empty((H * W,), dtype=torch.uint8, device=dev)
+    calls = [("ns_map_max alone, packed map", lambda: ops.map_max(packed, state=state, accumulate=True, workspace=ws)),
+             ("ns_map_max alone, [:, 3] column", lambda: ops.map_max(column, state=state, accumulate=True, workspace=ws)),
+             ("ns_map_to8b alone, packed map", lambda: ops.map_to8b(packed, denom=state[:1], out=out8)),
+             ("ns_map_to8b alone, [:, 3] column", lambda: ops.map_to8b(column, denom=state[:1], out=out8)),
+             ("ns_frame_to8b alone, packed rgb", lambda rgb=torch.rand((H * W, 3), device=dev),
+              o=torch.empty((H * W, 3), dtype=torch.uint8, device=dev): ops.frame_to8b(rgb, out=o))]
+    ops.map_max(packed, state=state, workspace=ws)
+    reps = 200
+    for name, call in calls:
+        for _ in range(10):
+            call()
+        per = []
+        for _ in range(a.alternations):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                call()
+            e1.record()
+            torch.cuda.synchronize()
+            per.append(1e3 * e0.elapsed_time(e1) / reps)
+        print(f"  {name:<34s} {statistics.median(per):8.2f} us per {H} x {W} map   (spread {max(per) - min(per):.2f})")
 
 
 def bench_depth(a, dev, ds, ids, poses, hwf, K, kw, timed):
