@@ -211,7 +211,51 @@ int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, 
                     float* pts_out, float* w_out, float* rgb_out, int64_t capacity, int64_t* count_dev, void* workspace_dev,
                     void* stream);
 
-/* ---- a rendered frame as 8-bit pixels  (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
+/* ---- the field's isosurface mesh  (the original NeRF code's extract_mesh notebook: marching cubes of a density lattice on the
+ * host; not in the reference) ----  Marching TETRAHEDRA on the Kuhn split of every lattice cell: a 16-entry case table without
+ * ambiguous cases, and a split that is translation-invariant and face-compatible, so the surface is a closed oriented manifold
+ * wherever it stays off the lattice boundary.  An ordered stream compaction, the sibling of ns_cloud_append.
+ * LATTICE: point (i, j, k), i in [0, Gx), j in [0, Gy), k in [0, Gz), has lattice index lin = (k * Gy + j) * Gx + i, value
+ * sigma_dev[lin * sigma_stride] (the stride in floats; 0 or 1 = packed, 4 = the sigma column of a raw [., 4] array) and position
+ * lo + (float)idx * h per axis, the multiply and the add rounded separately in fp32.
+ * CELLS: cell (i, j, k), i < Gx - 1, j < Gy - 1, k < Gz - 1, has the flat index e = (k * (Gy - 1) + j) * (Gx - 1) + i and eight
+ * corners, named by their code dx + 2 dy + 4 dz.  Its six tetrahedra t = 0 .. 5 belong to the permutations pi of the axes
+ * (x, y, z) in lexicographic order -- xyz, xzy, yxz, yzx, zxy, zyx --: tetrahedron t has the corners w0 = 000, w1 = w0 + e_pi0,
+ * w2 = w1 + e_pi1, w3 = 111.  A corner is INSIDE iff its value >= iso.  A cell with a corner that is NaN or +-inf emits nothing
+ * and is counted as skipped.
+ * TRIANGLES of a tetrahedron, by its inside corners (numbered 0 .. 3 as w0 .. w3): none or all four, no triangle; one (a) and
+ * three outside (b0 < b1 < b2), the triangle (a b0, a b1, a b2) of the crossed edges; three (a0 < a1 < a2) and one outside (b),
+ * the triangle (a0 b, a1 b, a2 b); two (a0 < a1) and two outside (b0 < b1), the quad (a0 b0, a0 b1, a1 b1, a1 b0) split as
+ * (0, 1, 2) and (0, 2, 3).  WINDING: vertices 1 and 2 of a triangle are exchanged iff the normal (m1 - m0) x (m2 - m0) through
+ * the MIDPOINTS m of its three lattice edges has a negative dot product with (mean of the tetrahedron's outside corners - mean of
+ * its inside corners): a function of (t, inside corners) alone, a table (csrc/ns_mesh_table.h), never of the vertex positions --
+ * a corner exactly at iso gives triangles of zero area, whose own normal says nothing.  The surface faces from inside to outside.
+ * VERTEX on the lattice edge between points a and b, lin(a) < lin(b), with values s_a and s_b:
+ *   tt = (iso - s_a) / (s_b - s_a)       one correctly rounded fp32 division,
+ *   p  = p_a + tt * (p_b - p_a)          per axis, every operation rounded separately,
+ *   key = lin(a) * 8 + (dx + 2 dy + 4 dz),  d = b - a in {0, 1}^3:
+ * a function of the edge alone, so every triangle around an edge carries the same position bits under the same key.
+ * ORDER: triangles are numbered by (e, t, triangle within the tetrahedron).  Triangle n is written iff n < capacity -- nothing is
+ * ever written at or beyond capacity --: tri_out[n * 9 ..] its three vertices xyz, key_out[n * 3 ..] their keys.  capacity == 0
+ * (the outputs may then be NULL) is a pure count.  count_dev[0] = the number of ALL triangles, those that did not fit included,
+ * count_dev[1] = the number of skipped cells; both are overwritten, not accumulated.
+ * Three launches on `stream`, no atomics: (1) workgroup g counts the triangles and the skipped cells among its NS_MESH_SHARE
+ * cells from g * NS_MESH_SHARE on (thread t takes g * NS_MESH_SHARE + s * 256 + t) into workspace_dev (two int64 per share,
+ * ns_mesh_workspace_bytes(Gx, Gy, Gz) bytes; what it holds before the call does not matter); (2) ONE workgroup turns the
+ * triangle counts into absolute triangle indices in the order of g and writes the two totals; (3) every workgroup evaluates its
+ * cells again and emits: the share's index + the triangles of its earlier steps s and waves (LDS) + those of the lanes below (a
+ * cell has 0 .. 12 triangles: an integer exclusive scan over the wave).  The result depends on the inputs alone.  Values whose
+ * differences overflow fp32 give NaN positions.  Checked before any launch (NS_E_INVALID): a dimension below 2,
+ * Gx * Gy * Gz >= 2^31 (lattice and cell indices are 32-bit), a negative stride, a negative capacity, capacity > 0 without
+ * tri_out / key_out, count_dev / sigma_dev / workspace_dev NULL, count_dev / key_out / workspace_dev not 8-byte aligned, a
+ * non-finite iso, lo or h, and h <= 0.  ns_mesh_workspace_bytes is 0 for a shape that would be refused.                      */
+#define NS_MESH_SHARE 1024
+int64_t ns_mesh_workspace_bytes(int Gx, int Gy, int Gz);
+int ns_mesh_extract(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy, int Gz, float iso, float lo_x, float lo_y,
+                    float lo_z, float h_x, float h_y, float h_z, float* tri_out, int64_t* key_out, int64_t capacity,
+                    int64_t* count_dev, void* workspace_dev, void* stream);
+
+/* ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
  * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a
  * quarter of the frame's bytes cross to the host:
  *   out_dev[p * C + c] = (uint8) trunc(255.0f * min(max(x, 0), 1)),  x = rgb_dev[p * rgb_stride + c],  c = 0, 1, 2,

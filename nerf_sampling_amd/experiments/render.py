@@ -75,6 +75,17 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--cloud-points", "cloud_points", default=None, type=int, show_default=True,
               help="(not in the reference) --device-cloud writes at most this many of the kept samples, drawn uniformly "
                    "(plot.py draws 5e4).")
+@click.option("--device-mesh", "device_mesh", is_flag=True, default=False,
+              help="(not in the reference) Also extract a triangle mesh of the field's density on the device (ns_mesh_extract, "
+                   "Trainer(device_mesh=True), nerf_utils.scene_mesh): scene_mesh.ply beside the frames -- marching tetrahedra "
+                   "on a lattice of the fine network's density, a closed surface facing outwards, coloured by the field.")
+@click.option("--mesh-resolution", "mesh_resolution", default=256, type=int, show_default=True,
+              help="(not in the reference) --device-mesh samples the density at this many lattice points per axis.")
+@click.option("--mesh-threshold", "mesh_threshold", default=50.0, type=float, show_default=True,
+              help="(not in the reference) --device-mesh cuts the density at this value.  50 is a starting value, not a "
+                   "property of a scene: lower it where the surface has holes, raise it where it carries floaters.")
+@click.option("--mesh-bound", "mesh_bound", default=1.5, type=float, show_default=True,
+              help="(not in the reference) --device-mesh covers the cube [-bound, bound]^3 of scene coordinates.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -97,6 +108,9 @@ def main(**kw):
         k["device_depth"] = True
     if kw["device_cloud"]:
         k.update(device_cloud=True, cloud_min_weight=kw["cloud_min_weight"], cloud_points=kw["cloud_points"])
+    if kw["device_mesh"]:
+        k.update(device_mesh=True, mesh_resolution=kw["mesh_resolution"], mesh_threshold=kw["mesh_threshold"],
+                 mesh_bound=kw["mesh_bound"])
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -367,6 +367,92 @@ class PointCloud:
         return self.pts[:M], self.weights[:M], (self.rgb[:M] if self.colours else None)
 
 
+# ---- the field's isosurface mesh (marching tetrahedra on the Kuhn split, on the device; not in the reference) -------------
+def mesh_workspace_bytes(Gx: int, Gy: int, Gz: int) -> int:
+    """ns_mesh_workspace_bytes: the per-share counts ``mesh_extract`` needs for a Gx x Gy x Gz lattice (0: a shape it refuses)"""
+    return int(_lib.load().ns_mesh_workspace_bytes(int(Gx), int(Gy), int(Gz)))
+
+
+def _mesh_lattice(sigma):
+    """(Gx, Gy, Gz, stride in floats) of ``sigma``: float32 [Gz,Gy,Gx] on the device, contiguous or one column of a contiguous
+    [Gz,Gy,Gx,C] array (``raw[..., 3]``)"""
+    if not (isinstance(sigma, Tensor) and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.dim() == 3):
+        raise ValueError("sigma: a float32 device tensor [Gz,Gy,Gx]")
+    Gz, Gy, Gx = (int(v) for v in sigma.shape)
+    if min(Gx, Gy, Gz) < 2:
+        raise ValueError(f"sigma: at least two lattice points along every axis, got {tuple(sigma.shape)}")
+    if Gx * Gy * Gz >= 2 ** 31:
+        raise ValueError(f"sigma: Gx * Gy * Gz = {Gx * Gy * Gz} is not below 2^31")
+    stride = int(sigma.stride(2))
+    if stride < 1 or tuple(sigma.stride()) != (Gy * Gx * stride, Gx * stride, stride):
+        raise ValueError("sigma: contiguous [Gz,Gy,Gx], or one column of a contiguous [Gz,Gy,Gx,C] array")
+    return Gx, Gy, Gz, stride
+
+
+def mesh_extract(sigma, iso, lo, h, capacity: Optional[int] = None, workspace=None):
+    """ns_mesh_extract: the triangles of the isosurface ``sigma == iso`` of a lattice, by marching tetrahedra on the device, in
+    the order (cell, tetrahedron, triangle) and wound from inside (sigma >= iso) to outside.  ``sigma``: fp32 [Gz,Gy,Gx] on the
+    device, contiguous or a column view such as ``raw[..., 3]`` of a contiguous [Gz,Gy,Gx,4] array; lattice point (i, j, k)
+    lies at ``lo + (float32) idx * h`` per axis (``lo``, ``h``: three numbers each, rounded to float32; h > 0).  A cell with a
+    NaN or infinite corner emits nothing and is counted.  ``capacity`` None: a counting call, ONE readback of the two counters,
+    an allocation of exactly that many triangles and the emitting call; given: one emitting call and one readback, and the
+    tensors returned are cut to min(n_triangles, capacity) -- triangles beyond it are counted, never written.  ``workspace``: a
+    contiguous 8-byte-aligned device tensor of at least ``mesh_workspace_bytes(Gx, Gy, Gz)`` bytes (None: allocated).  Returns
+    dict(triangles [n,3,3] fp32, keys [n,3] int64, n_triangles, n_skipped): a vertex's key names its lattice edge, and equal
+    keys carry equal position bits (``mesh_weld``).  What is wrong with the arguments raises ValueError before any launch."""
+    Gx, Gy, Gz, stride = _mesh_lattice(sigma)
+    dev = sigma.device
+    lo3, h3 = [float(np.float32(v)) for v in lo], [float(np.float32(v)) for v in h]
+    if len(lo3) != 3 or len(h3) != 3:
+        raise ValueError("lo and h: three numbers each")
+    if capacity is not None and int(capacity) < 0:
+        raise ValueError("capacity must be >= 0")
+    need = mesh_workspace_bytes(Gx, Gy, Gz)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
+              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
+        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on sigma's device")
+    lib = _lib.load()
+    counters = torch.empty((2,), dtype=torch.int64, device=dev)
+
+    def call(tri, keys, cap):
+        check(lib.ns_mesh_extract(_ptr(sigma), stride, Gx, Gy, Gz, float(iso), *lo3, *h3, _ptr(tri), _ptr(keys), cap,
+                                  _ptr(counters), _ptr(workspace), _stream(dev)), "ns_mesh_extract")
+
+    def outputs(cap):
+        return (torch.empty((cap, 3, 3), dtype=torch.float32, device=dev), torch.empty((cap, 3), dtype=torch.int64, device=dev))
+
+    if capacity is None:
+        call(None, None, 0)
+        n_triangles, n_skipped = (int(v) for v in counters.cpu())              # the one readback
+        capacity = n_triangles
+        tri, keys = outputs(capacity)
+        if capacity > 0:
+            call(tri, keys, capacity)                                          # counts the same lattice again
+    else:
+        capacity = int(capacity)
+        tri, keys = outputs(capacity)
+        call(tri, keys, capacity)
+        n_triangles, n_skipped = (int(v) for v in counters.cpu())              # the one readback
+    n = min(n_triangles, capacity)
+    return {"triangles": tri[:n], "keys": keys[:n], "n_triangles": n_triangles, "n_skipped": n_skipped}
+
+
+def mesh_weld(triangles, keys):
+    """(vertices [V,3], faces [F,3] int64) of ``mesh_extract``'s triangles, on the device: one vertex per distinct key, in
+    ascending key order (``torch.unique(keys, return_inverse=True)``); its position is that of any occurrence, since all
+    occurrences of a key are bit-identical."""
+    if not (isinstance(triangles, Tensor) and isinstance(keys, Tensor) and triangles.dim() == 3 and keys.dim() == 2
+            and tuple(triangles.shape[1:]) == (3, 3) and tuple(keys.shape) == (triangles.shape[0], 3)
+            and keys.dtype == torch.int64 and keys.device == triangles.device):
+        raise ValueError("triangles [n,3,3] and keys [n,3] int64 on one device")
+    unique, inverse = torch.unique(keys.reshape(-1), return_inverse=True)
+    vertices = torch.empty((unique.shape[0], 3), dtype=triangles.dtype, device=triangles.device)
+    vertices[inverse] = triangles.reshape(-1, 3)
+    return vertices, inverse.reshape(-1, 3)
+
+
 # ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b, quantised on the device) -----------------------------
 def frame_to8b(rgb, alpha=None, out=None, channels: int = 3):
     """ns_frame_to8b: ``run_nerf_helpers.to8b`` of a rendered frame on the device -- (uint8) trunc(255 * clip(x, 0, 1)), one fp32

@@ -46,7 +46,8 @@ class Trainer:
                  hip_graph: bool = True, device_batches=False, batch_seed: int = 0, device_eval: bool = False,
                  device_ssim: bool = False, device_depth: bool = False, device_cloud: bool = False,
                  cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False,
-                 device_video: bool = False):
+                 device_video: bool = False, device_mesh: bool = False, mesh_resolution: int = 256,
+                 mesh_threshold: float = 50.0, mesh_bound: float = 1.5):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -105,6 +106,15 @@ class Trainer:
         self.device_video = bool(device_video)
         if self.device_video and not self.device_eval:
             raise ValueError("device_video renders the spiral as the device evaluation renders its views: it needs device_eval=True")
+        # device_mesh (not in the reference; default off): render() also extracts the isosurface of the field's density on the
+        # device (nerf_utils.scene_mesh, ns_mesh_extract) -- scene_mesh.ply beside the frames: the density of the fine network
+        # (the coarse one where there is none) on a mesh_resolution^3 lattice over [-mesh_bound, mesh_bound]^3, cut at
+        # mesh_threshold (50 is a starting value, not a property of a scene: lower or raise it per scene).  The frames and
+        # psnr.txt are those of the run without the switch.
+        self.device_mesh = bool(device_mesh)
+        self.mesh_resolution, self.mesh_threshold, self.mesh_bound = int(mesh_resolution), float(mesh_threshold), float(mesh_bound)
+        if self.mesh_resolution < 2 or not self.mesh_bound > 0.0:
+            raise ValueError("mesh_resolution must be at least 2 and mesh_bound positive")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -204,7 +214,8 @@ class Trainer:
     def render(self, render_test, save_scene_data, images, i_test, render_poses, hwf, render_kwargs_test):
         """renderonly_{test|path}_{step:06d}/ with NNN.png, psnr.txt[, scene_data.pt] -- Trainer.py:181-230
         (no mp4; under device_video without render_test: rgb/NNN.png and disp/NNN.png through nerf_utils.write_video).  Under
-        device_cloud also scene_cloud.pt and scene_cloud.ply of the same poses (nerf_utils.scene_cloud)."""
+        device_cloud also scene_cloud.pt and scene_cloud.ply of the same poses (nerf_utils.scene_cloud); under device_mesh also
+        scene_mesh.ply, the isosurface of the field's density (nerf_utils.scene_mesh)."""
         with torch.no_grad():
             images = images[i_test] if render_test else None
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
@@ -219,6 +230,13 @@ class Trainer:
                                                savedir=testsavedir)
                 print(f"scene cloud: {cloud['n_kept']} of {cloud['n_candidates']} samples with weight >= {self.cloud_min_weight}"
                       f", {cloud['pts'].shape[0]} written to {testsavedir}")
+            if self.device_mesh:
+                fine = render_kwargs_test.get("network_fine")
+                mesh = nerf_utils.scene_mesh(fine if fine is not None else render_kwargs_test["network_fn"],
+                                             bound=self.mesh_bound, resolution=self.mesh_resolution,
+                                             threshold=self.mesh_threshold, savedir=testsavedir)
+                print(f"scene mesh: {mesh['faces'].shape[0]} triangles on {mesh['vertices'].shape[0]} vertices at density "
+                      f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped), written to {testsavedir}")
             if self.device_eval and render_test and self.render_factor == 0:
                 ds, ids = self._ray_dataset, i_test
                 if ds is None:          # called on its own: the test views alone go to the device
