@@ -688,8 +688,7 @@ class HipAdam(torch.optim.Adam):
         self._dev_step = torch.full((1,), self._host_steps, dtype=torch.int32, device=dev)
         self._dev_lr = torch.full((1,), float(self.param_groups[0]["lr"]), dtype=torch.float32, device=dev)
         self._lr_seen = float(self.param_groups[0]["lr"])
-        for p in params:
-            self._init_state(p)
+        # (a parameter gets its state with its first gradient, as in torch: one that never has a gradient keeps none)
         # two row tables, [0] for eager steps and [1] for a captured step (a replayed graph re-reads its pinned rows on
         # every replay, so eager steps taken after a capture must not touch them)
         self._table_host = [torch.empty((5 * len(params),), dtype=torch.int64, device="cpu").pin_memory() for _ in range(2)]
@@ -701,7 +700,7 @@ class HipAdam(torch.optim.Adam):
         def as_int(v):
             return int(v.item()) if isinstance(v, torch.Tensor) else int(v)
 
-        steps = {as_int(self.state[p]["step"]) if len(self.state[p]) else 0 for p in params}
+        steps = {as_int(self.state[p]["step"]) for p in params if len(self.state.get(p, ()))}    # (stateless: no gradient yet)
         if len(steps) > 1 or len(self.param_groups) != 1:
             raise NotImplementedError("the device step counter needs one parameter group and one common step count")
         return steps.pop() if steps else 0
@@ -722,11 +721,17 @@ class HipAdam(torch.optim.Adam):
 
     def claim_capture_table(self):
         """Called once by the (single) captured step of this optimizer: the captured update re-reads row table [1] on every
-        replay, so a second capture from the same optimizer would overwrite the rows the first graph points at."""
+        replay, so a second capture from the same optimizer would overwrite the rows the first graph points at.
+
+        Every parameter gets its moments here, ahead of the capture: allocated and zeroed inside it, they would be zeroed
+        again by every replay."""
         if getattr(self, "_capture_claimed", False):
             raise RuntimeError("this HipAdam already backs a captured step: one hipGraph capture per optimizer "
                                "(build a new optimizer, or reuse the existing GraphedDepthNetStep)")
         self._capture_claimed = True
+        for g in self.param_groups:
+            for p in g["params"]:
+                self._init_state(p)
 
     def note_replayed_step(self):
         """A captured graph containing step() was replayed once."""

@@ -154,7 +154,7 @@ gemm_tall_kernel(const TallArgs p) {
       if (p.bias) v += bj;
       float* c = p.C + row * p.ldc + j;
       if (p.accumulate) v += *c;
-      if (p.act == 1) v = fmaxf(v, 0.f);
+      if (p.act == 1) v = v < 0.f ? 0.f : v;          // NaN stays NaN, as torch.relu (fmaxf would drop it)
       else if (p.act == 2) v = v > 0.f ? v : 0.01f * v;
       else if (p.act == 3) v = 1.f / (1.f + expf(-v));
       if (p.dact) {

@@ -88,7 +88,7 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, int64_t s
       if (bias) v += bias[j];
       float* c = C + static_cast<int64_t>(row) * ldc + j;
       if (accumulate) v += *c;
-      if (ep.act == 1) v = fmaxf(v, 0.f);
+      if (ep.act == 1) v = v < 0.f ? 0.f : v;          // NaN stays NaN, as torch.relu (fmaxf would drop it)
       else if (ep.act == 2) v = v > 0.f ? v : 0.01f * v;
       else if (ep.act == 3) v = 1.f / (1.f + expf(-v));
       if (ep.dact) {
@@ -151,12 +151,13 @@ colsum_kernel(const float* __restrict__ X, int64_t ld, int M, int N, float* __re
   }
 }
 
-// activation forward in place / backward: act 0 none, 1 relu, 2 leaky(0.01), 3 sigmoid
+// activation forward in place / backward: act 0 none, 1 relu, 2 leaky(0.01), 3 sigmoid.  A NaN stays NaN under each of them,
+// as under torch's (relu is a comparison and a select, not fmaxf, which would return 0)
 __global__ void __launch_bounds__(256)
 act_forward_kernel(float* __restrict__ y, int64_t n, int act) {
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float v = y[i];
-    y[i] = act == 1 ? fmaxf(v, 0.f) : act == 2 ? (v > 0.f ? v : 0.01f * v) : act == 3 ? 1.f / (1.f + expf(-v)) : v;
+    y[i] = act == 1 ? (v < 0.f ? 0.f : v) : act == 2 ? (v > 0.f ? v : 0.01f * v) : act == 3 ? 1.f / (1.f + expf(-v)) : v;
   }
 }
 // dy *= act'(.) given the activation OUTPUT y

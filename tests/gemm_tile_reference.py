@@ -8,7 +8,8 @@ The operation, in the kernel's documented order:
 
     acc      = sum_k A[i, k] B[j, k]                     (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums)
     v        = acc (+ bias[j]) (+ C[i, j] if accumulate)
-    v        = act(v)             act 0 none, 1 max(v, 0), 2 v > 0 ? v : float32(0.01) * v, 3 1 / (1 + expf(-v))
+    v        = act(v)             act 0 none, 1 v < 0 ? 0 : v, 2 v > 0 ? v : float32(0.01) * v, 3 1 / (1 + expf(-v))
+                                  (a NaN stays NaN under every one of them, as under torch.relu: row NAN_ROW of the NaN case)
     C[i, j]  = v * act'(dact)     evaluated from the activation OUTPUT y = dact_ref[i, j]:
                                   dact 1: y > 0 ? 1 : 0,  2: y > 0 ? 1 : float32(0.01),  3: y * (1 - y)
     a_rowsum[i] = sum_k A[i, k]
@@ -35,7 +36,8 @@ DYADIC = (0.0, 0.25, 0.5, 0.75, 1.0)
 K_SWEEP = (0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 129, 255, 256, 257, 319, 1020, 1024)
 K_PRODUCT = (7, 64, 300)
 SIZES = ((1, 1), (31, 33), (32, 32), (33, 31), (65, 100), (100, 257), (64, 1))
-WIDE_K = 256          # ns_gemm_fused: K >= WIDE_K runs trips of 64 k per wave, below it trips of 32
+NAN_ROW = 37          # the row of A that holds a NaN in the relu-keeps-NaN cases (not the first row of a 32-row tile)
+WIDE_K = 256        # ns_gemm_fused: K >= WIDE_K runs trips of 64 k per wave, below it trips of 32
 
 
 def trip_length(K):

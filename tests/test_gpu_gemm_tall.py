@@ -77,6 +77,31 @@ def test_integer_inputs_are_exact(N, K):
             assert bool((flat[rows * (N + 7):] == SENTINEL).all()), tag
 
 
+@pytest.mark.parametrize("transposed", [0, 1])
+def test_relu_epilogue_keeps_a_nan_row(transposed):
+    """act = 1 with one NaN in row 37 of A (two slabs: 129 rows): every output of that row is NaN, as torch.relu and nn.Linear
+    give it, and every other row holds the bits of the run without the NaN."""
+    g = torch.Generator().manual_seed(43)
+    rows, N, K, nan_row = 129, 256, 319, 37
+    A, W, bias = _ints((rows, K), g), _ints((N, K), g), _ints((N,), g)
+    bad = A.clone()
+    bad[nan_row, 7] = float("nan")
+    B, sb0, sb1 = (W.t().contiguous(), 1, N) if transposed else (W, K, 1)
+    outs = []
+    for a in (A, bad):
+        flat = torch.full((rows * N + GUARD,), SENTINEL, device="cuda")
+        assert _tall(a, B, sb0, sb1, bias, flat[:rows * N].view(rows, N), rows, N, K, act=1) == 0, _lib.load().ns_last_error()
+        assert bool((flat[rows * N:] == SENTINEL).all())
+        outs.append(flat[:rows * N].view(rows, N))
+    clean, got = outs
+    exp = torch.relu(torch.nn.functional.linear(bad.double(), W.double(), bias.double())).float()
+    others = torch.arange(rows, device="cuda") != nan_row
+    assert bool(torch.isnan(exp[nan_row]).all()) and not bool(torch.isnan(exp[others]).any()), "the reference itself"
+    assert bool(torch.isnan(got[nan_row]).all()), "the NaN row must come out NaN in every column"
+    assert torch.equal(got[others], exp[others]) and torch.equal(got[others], clean[others])
+    assert torch.equal(clean, torch.relu(torch.nn.functional.linear(A.double(), W.double(), bias.double())).float())
+
+
 def test_wrappers_take_column_slices_of_the_cat_buffer():
     from nerf_sampling_amd import autograd as ag
 

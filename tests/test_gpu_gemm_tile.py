@@ -163,6 +163,29 @@ def test_integer_inputs_are_exact_under_every_epilogue(layout, K):
         _settle(pending)
 
 
+@pytest.mark.parametrize("layout", LAYOUTS, ids=LAYOUT_IDS)
+def test_relu_epilogue_keeps_a_nan_row(layout):
+    """act = 1 with one NaN in row G.NAN_ROW of A: every output of that row is NaN, as torch.relu and nn.Linear give it (fmaxf
+    would return the bias-free 0), and every other row holds the bits of the run without the NaN."""
+    g = torch.Generator().manual_seed(41)
+    M, N, K = 65, 100, 64
+    A, B, bias = _ints((M, K), g), _ints((N, K), g), _ints((N,), g)
+    bad = A.clone()
+    bad[G.NAN_ROW, 7] = float("nan")
+    b, bias_d = Operand(B, layout[1]), bias.cuda()
+    clean, out = Output(M, N).reset(M, N), Output(M, N).reset(M, N)
+    assert _fused(Operand(A, layout[0]), b, bias_d, clean, M, N, K, act=1) == 0
+    assert bool(clean.ok(G.expected(A, B, bias, act=1), None))
+    assert _fused(Operand(bad, layout[0]), b, bias_d, out, M, N, K, act=1) == 0
+    got, exp = out.view.cpu(), G.expected(bad, B, bias, act=1)
+    others = torch.arange(M) != G.NAN_ROW
+    assert bool(torch.isnan(exp[G.NAN_ROW]).all()) and not bool(torch.isnan(exp[others]).any()), "the reference itself"
+    assert bool(torch.isnan(got[G.NAN_ROW]).all()), "the NaN row must come out NaN in every column"
+    assert torch.equal(got[others], exp[others]) and torch.equal(got[others], clean.view.cpu()[others])
+    assert bool((out.buf[:, :2] == SENTINEL).all() & (out.buf[:, 2 + N:] == SENTINEL).all()
+                & (out.flat[M * (N + PAD):] == SENTINEL).all() & (out.rs == SENTINEL).all()), "guard bands"
+
+
 # ---- b. the sigmoid epilogue -------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("M,N,K", [(64, 1, 256), (33, 33, 4)])
