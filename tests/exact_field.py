@@ -261,12 +261,13 @@ class _Unfit(Exception):
 
 
 def _draw_layer(rng, inp, rows, permitted, relu, qstar, sbound, *, tbound=None, coarse_only=False, full=False, accept=None,
-                sparse=True, start=64, limit=None):
+                sparse=True, start=64, limit=None, one_seed=False):
     """One layer on the pool input `inp` [P, K]: (weights [rows, K], bias [rows], pre-activations [P, rows]).
     sbound: the bound on a row's sum of magnitudes; tbound: on the pool-row sum of the layer's activations (a layer that full
     rows read); coarse_only: no coefficient 1/2; full: every row reads every permitted column with +-1; sparse: a hidden unit
     stays within AMAX and ACTIVE; start: the widest row; limit: the largest |pre-activation| of a layer without ReLU;
-    accept(columns, coefficients, bias): a further condition on a row."""
+    accept(columns, coefficients, bias): a further condition on a row; one_seed: a row is seeded with one column even where
+    there are more columns than rows."""
     P, K = inp.shape
     # the trial rows are evaluated in fp32 on the transposed pool: every value that passes the bounds below is exact there
     # (a multiple of q* below 2^24 q*), and the conditions are asserted afterwards in float64 (check_c1 .. check_c5)
@@ -325,7 +326,7 @@ def _draw_layer(rng, inp, rows, permitted, relu, qstar, sbound, *, tbound=None, 
     for r in range(rows):
         if full:
             seeds = np.arange(len(permitted))
-        elif len(perm) >= rows:
+        elif len(perm) >= rows and not one_seed:
             seeds = perm[r::rows]
         else:
             seeds = perm[[r % len(perm)]]

@@ -3,6 +3,10 @@ the reference and against the CPU oracle on the same seeded inputs (run with -m 
 
 Tolerances are stated per check.  fp32 paths are held to ~1e-6..1e-5 (different summation order /
 libm only); the bf16/fp16 MFMA paths are held to operand-rounding-sized errors.
+
+The DepthNet forward's exact checks -- every kernel instantiation against the float64 chain on exactly representable
+networks and rays, 8 * 2^-24 * max(|near|, |far|) on every ray -- live in tests/test_gpu_exact_depthnet.py; the gates on
+the DepthNet below are the looser ones for ordinary weights.
 """
 
 import numpy as np
