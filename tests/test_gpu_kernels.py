@@ -7,6 +7,11 @@ libm only); the bf16/fp16 MFMA paths are held to operand-rounding-sized errors.
 The DepthNet forward's exact checks -- every kernel instantiation against the float64 chain on exactly representable
 networks and rays, 8 * 2^-24 * max(|near|, |far|) on every ray -- live in tests/test_gpu_exact_depthnet.py; the gates on
 the DepthNet below are the looser ones for ordinary weights.
+
+The ray front end's exact checks -- ns_get_rays, ns_sphere_intersect, ns_solve_quadratic, ns_place_samples, ns_coarse_z,
+ns_place_samples_backward and ns_argmax_gather bit for bit against fp32 models of their statements and inside derived bounds
+against float64, at grid-stride sizes, on both placement kernels and on adversarial means, tangent rays and NaN / inf rows -- live
+in tests/test_gpu_ray_front.py; sections a1, a2, a5, a11 and test_argmax_gather below are the golden-file checks at 1e-6..2e-5.
 """
 
 import numpy as np
