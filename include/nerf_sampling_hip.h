@@ -255,6 +255,38 @@ int ns_mesh_extract(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy
                     float lo_z, float h_x, float h_y, float h_z, float* tri_out, int64_t* key_out, int64_t capacity,
                     int64_t* count_dev, void* workspace_dev, void* stream);
 
+/* ---- the connected components of a mesh's faces  (what every NeRF mesh export does on the host to drop floaters, the small
+ * closed blobs of stray density around the object; not in the reference) ----  A lock-free union-find over the vertices.
+ * CONNECTIVITY: faces_dev[f * 3 .. f * 3 + 2], f in [0, F), are vertex indices, as ops.mesh_weld returns them.  Two vertices are
+ * connected iff a chain of faces joins them; a face joins its three vertices, so two faces that share a single vertex lie in one
+ * component.  A face with two or three equal indices is legal and joins whatever indices it has.  A face with any index outside
+ * [0, V) joins nothing and is counted; none of its indices is ever used as an address.
+ * OUTPUTS: label_dev[v], v in [0, V), is the smallest vertex index of v's component; a vertex in no face is a component of its
+ * own.  At a root r == label_dev[r], tri_count_dev[r] is the number of valid faces of the component and vert_count_dev[r] the
+ * number of its vertices; every other entry of the two is 0.  count_dev[0] = the number of components, count_dev[1] = the number
+ * of ignored faces; both are overwritten, not accumulated.  Nothing is written outside [0, V) of the three arrays.
+ * Four launches on `stream` (one where V == 0), with label_dev as the parent array: (1) parent[v] = v, the counts and the two
+ * 32-bit counters in workspace_dev zeroed (ns_mesh_components_workspace_bytes(V, F) bytes; what it holds before the call does
+ * not matter); (2) workgroup g takes the NS_MESH_COMPONENTS_SHARE faces from g * NS_MESH_COMPONENTS_SHARE on (thread t takes
+ * g * NS_MESH_COMPONENTS_SHARE + s * 256 + t) and unites (a, b) and (a, c) of each: two walks towards the roots side by side,
+ * halving their paths (atomicMin) and over as soon as they meet, else the larger root linked below the smaller by atomicCAS on
+ * the root's own word; (3) label_dev[v] = the root of v, the vertices counted
+ * per root and the roots counted; (4) the valid faces counted at the label of their first vertex, and the totals written.
+ * A parent never exceeds its vertex and only ever decreases, so every walk visits strictly decreasing indices and ends; no
+ * workgroup waits for memory another one writes, and a CAS is retried only because another thread's CAS succeeded.  Integer
+ * atomics at agent scope (atomicMin, atomicCAS, atomicAdd on 32-bit words), unlike the sibling kernels -- they are what makes
+ * the labelling parallel --, and no floating-point ones: the smallest index, the counts and the totals do not depend on the
+ * order of the atomics, so the result depends on the inputs alone.  Not part of this: per-component area or volume (floating-
+ * point sums whose order is not fixed), and meshes of 2^31 vertices or faces or more.
+ * Checked before any launch (NS_E_INVALID): negative F or V, V >= 2^31 or F >= 2^31, count_dev NULL, faces_dev NULL with F > 0,
+ * label_dev / tri_count_dev / vert_count_dev / workspace_dev NULL with V > 0, count_dev / workspace_dev / faces_dev not 8-byte
+ * aligned, label_dev / tri_count_dev / vert_count_dev not 4-byte aligned.  V == 0 writes only the two counters (0 and F: every
+ * face is out of range).  ns_mesh_components_workspace_bytes is 0 for a shape that would be refused.                          */
+#define NS_MESH_COMPONENTS_SHARE 1024
+int64_t ns_mesh_components_workspace_bytes(int64_t V, int64_t F);
+int ns_mesh_components(const int64_t* faces_dev, int64_t F, int64_t V, int32_t* label_dev, int32_t* tri_count_dev,
+                       int32_t* vert_count_dev, int64_t* count_dev, void* workspace_dev, void* stream);
+
 /* ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
  * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a
  * quarter of the frame's bytes cross to the host:

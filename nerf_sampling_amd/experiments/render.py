@@ -83,9 +83,17 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               help="(not in the reference) --device-mesh samples the density at this many lattice points per axis.")
 @click.option("--mesh-threshold", "mesh_threshold", default=50.0, type=float, show_default=True,
               help="(not in the reference) --device-mesh cuts the density at this value.  50 is a starting value, not a "
-                   "property of a scene: lower it where the surface has holes, raise it where it carries floaters.")
+                   "property of a scene: lower it where the surface has holes; rather than raise it where it carries floaters, drop them "
+                   "with --mesh-keep-largest or --mesh-min-triangles.")
 @click.option("--mesh-bound", "mesh_bound", default=1.5, type=float, show_default=True,
               help="(not in the reference) --device-mesh covers the cube [-bound, bound]^3 of scene coordinates.")
+@click.option("--mesh-min-triangles", "mesh_min_triangles", default=0, type=click.IntRange(min=0), show_default=True,
+              help="(not in the reference) --device-mesh keeps only the connected components of its surface with at least this "
+                   "many triangles (ns_mesh_components, nerf_utils.mesh_filter): floaters, the small closed blobs of stray "
+                   "density around the object, leave scene_mesh.ply.  0: no filter.")
+@click.option("--mesh-keep-largest", "mesh_keep_largest", default=0, type=click.IntRange(min=0), show_default=True,
+              help="(not in the reference) --device-mesh keeps only this many of its surface's connected components, those with "
+                   "the most triangles (among those --mesh-min-triangles leaves).  0: no filter.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -110,7 +118,8 @@ def main(**kw):
         k.update(device_cloud=True, cloud_min_weight=kw["cloud_min_weight"], cloud_points=kw["cloud_points"])
     if kw["device_mesh"]:
         k.update(device_mesh=True, mesh_resolution=kw["mesh_resolution"], mesh_threshold=kw["mesh_threshold"],
-                 mesh_bound=kw["mesh_bound"])
+                 mesh_bound=kw["mesh_bound"], mesh_min_triangles=kw["mesh_min_triangles"],
+                 mesh_keep_largest=kw["mesh_keep_largest"])
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -1283,20 +1283,73 @@ def write_mesh_ply(path, vertices, faces, rgb=None) -> None:
         f.write(face.tobytes())
 
 
+def mesh_component_keep(labels, triangles, min_component_triangles=0, keep_largest=0):
+    """Which components a filter keeps, as a bool [V] that is set at component roots only -- plain torch on the tensors' device.
+    ``labels`` / ``triangles``: ops.mesh_components' (a root r has labels[r] == r and triangles[r] faces).  Kept: the
+    components of at least ``min_component_triangles`` faces and, with ``keep_largest`` = k > 0, among those only the k with
+    the most faces, a tie going to the smaller label; both given, both hold."""
+    min_component_triangles, keep_largest = int(min_component_triangles), int(keep_largest)
+    if min_component_triangles < 0 or keep_largest < 0:
+        raise ValueError("min_component_triangles and keep_largest must be >= 0")
+    V = int(labels.shape[0])
+    keep = (labels.long() == torch.arange(V, device=labels.device)) & (triangles >= min_component_triangles)
+    if keep_largest > 0:
+        roots = torch.nonzero(keep)[:, 0]                                      # ascending label
+        order = torch.sort(triangles[roots], descending=True, stable=True).indices     # stable: a tie keeps that order
+        keep = torch.zeros_like(keep)
+        keep[roots[order[:keep_largest]]] = True
+    return keep
+
+
+def mesh_filter(vertices, faces, rgb=None, min_component_triangles=0, keep_largest=0):
+    """Drop a mesh's floaters on the device: split it into the connected components of its faces (ops.mesh_components; two
+    faces that share a vertex are connected) and keep what mesh_component_keep keeps.  ``vertices`` [V,3] and ``faces`` int64
+    [F,3] on the device, as ops.mesh_weld returns them or from anywhere else; ``rgb`` [V,3] or None is cut as the vertices are.
+    The kept vertices and faces stay in their order, the faces renumbered (ops.mesh_select).  Returns dict(vertices, faces, rgb,
+    index int64 [V]: old -> new vertex, -1 where dropped; n_components; n_kept_components; n_dropped_triangles: the faces that
+    left, those with an index out of range among them; component_triangles: the face counts of all components in label order,
+    an int32 device tensor).  Not part of this: per-component area or volume, normals, simplification."""
+    faces = faces.contiguous()
+    comp = ops.mesh_components(faces, int(vertices.shape[0]))
+    keep = mesh_component_keep(comp["labels"], comp["triangles"], min_component_triangles, keep_largest)
+    got = ops.mesh_select(vertices, faces, comp["labels"], keep, extras=(rgb,))
+    roots = comp["labels"].long() == torch.arange(vertices.shape[0], device=vertices.device)
+    return dict(vertices=got["vertices"], faces=got["faces"], rgb=got["extras"][0], index=got["index"],
+                n_components=comp["n_components"], n_kept_components=int(keep.sum()),
+                n_dropped_triangles=int(faces.shape[0] - got["faces"].shape[0]), component_triangles=comp["triangles"][roots])
+
+
 def scene_mesh(network, bound=1.5, resolution=256, threshold=50.0, colours=True, savedir=None, capacity=None,
                return_grid=False):
+    """A triangle mesh of the field's density, extracted on the device: scene_mesh_filtered without a filter -- its launches,
+    its dict, its scene_mesh.ply.  ``threshold``: 50 is a starting value, not a property of a scene -- lower it where the
+    surface has holes; the floaters that brings are dropped by scene_mesh_filtered's ``min_component_triangles`` and
+    ``keep_largest``, which this signature, kept as it was, does not carry."""
+    return scene_mesh_filtered(network, bound=bound, resolution=resolution, threshold=threshold, colours=colours, savedir=savedir,
+                               capacity=capacity, return_grid=return_grid)
+
+
+def scene_mesh_filtered(network, bound=1.5, resolution=256, threshold=50.0, colours=True, savedir=None, capacity=None,
+                        return_grid=False, min_component_triangles=0, keep_largest=0):
     """A triangle mesh of the field's density, extracted on the device: what the original NeRF code's extract_mesh notebook
     makes on the host with marching cubes.  field_density_grid samples ``network`` on ``resolution`` points per axis over
     [-bound, bound]^3; ops.mesh_extract turns the lattice into the triangles of the surface density == ``threshold`` by
     marching tetrahedra (closed and facing outwards wherever it stays off the lattice boundary); ops.mesh_weld joins them on
     their lattice-edge keys.  ``threshold``: 50 is a starting value, not a property of a scene -- lower it where the surface
-    has holes, raise it where it carries floaters.  ``colours``: the field is queried once more at the welded vertices, looking
+    has holes; the floaters a low threshold brings, small closed blobs of stray density around the object, are what
+    ``min_component_triangles`` and ``keep_largest`` drop (mesh_filter: the connected components of the welded faces; only
+    those of at least that many triangles stay, and of those only the ``keep_largest`` largest; 0 and 0, the default, launch
+    and return what scene_mesh always did).  The filter runs before the colour query, so a dropped vertex is never evaluated; the
+    dict then also has n_components, n_kept_components, n_dropped_triangles and component_triangles (mesh_filter), while
+    n_triangles stays what ops.mesh_extract counted.  ``colours``: the field is queried once more at the welded vertices, looking
     along the unit vector from the vertex towards the box centre: rgb = sigmoid(raw[:, :3]).  ``capacity``: triangles to make
     room for; None counts first (ops.mesh_extract); fewer than the surface has: RuntimeError naming the count.
     Returns dict(vertices [V,3], faces [F,3] int64, rgb [V,3] or None, n_triangles, n_skipped, lo, h[, grid]) with device
     tensors; lo and h are the lattice's (mesh_lattice).  ``savedir`` gets scene_mesh.ply (write_mesh_ply).  Not part of this:
-    simplification, normals, and lattices of 2^31 points or more."""
+    simplification, normals, per-component area or volume, and lattices of 2^31 points or more."""
     lo3, h3, _G = mesh_lattice(-float(bound), float(bound), resolution)
+    if int(min_component_triangles) < 0 or int(keep_largest) < 0:
+        raise ValueError("min_component_triangles and keep_largest must be >= 0")
     with torch.no_grad():
         grid = field_density_grid(network, -float(bound), float(bound), resolution)
         got = ops.mesh_extract(grid, float(threshold), lo3, h3, capacity=capacity)
@@ -1304,6 +1357,10 @@ def scene_mesh(network, bound=1.5, resolution=256, threshold=50.0, colours=True,
             raise RuntimeError(f"scene_mesh: the surface has {got['n_triangles']} triangles but there is room for "
                                f"{got['triangles'].shape[0]}: pass capacity={got['n_triangles']}")
         vertices, faces = ops.mesh_weld(got["triangles"], got["keys"])
+        kept = None
+        if int(min_component_triangles) != 0 or int(keep_largest) != 0:
+            kept = mesh_filter(vertices, faces, None, min_component_triangles, keep_largest)
+            vertices, faces = kept["vertices"], kept["faces"]
         rgb = None
         if colours:
             rgb = torch.empty((vertices.shape[0], 3), dtype=torch.float32, device=vertices.device)
@@ -1312,6 +1369,8 @@ def scene_mesh(network, bound=1.5, resolution=256, threshold=50.0, colours=True,
                 towards = towards / towards.norm(dim=-1, keepdim=True).clamp_min(1e-12)
                 rgb = torch.sigmoid(ops.nerf_forward(network.packed(), vertices[:, None, :], towards)[:, 0, :3])
     out = dict(vertices=vertices, faces=faces, rgb=rgb, n_triangles=got["n_triangles"], n_skipped=got["n_skipped"], lo=lo3, h=h3)
+    if kept is not None:
+        out.update({k: kept[k] for k in ("n_components", "n_kept_components", "n_dropped_triangles", "component_triangles")})
     if return_grid:
         out["grid"] = grid
     if savedir is not None:

@@ -453,6 +453,64 @@ def mesh_weld(triangles, keys):
     return vertices, inverse.reshape(-1, 3)
 
 
+def mesh_components_workspace_bytes(n_vertices: int, n_faces: int) -> int:
+    """ns_mesh_components_workspace_bytes: the counters ``mesh_components`` needs (0: a shape it refuses)"""
+    return int(_lib.load().ns_mesh_components_workspace_bytes(int(n_vertices), int(n_faces)))
+
+
+def mesh_components(faces, n_vertices: int, workspace=None):
+    """ns_mesh_components: the connected components of a mesh's faces, on the device.  ``faces``: int64 contiguous [F,3] on the
+    device, as ``mesh_weld`` returns them; two vertices are connected iff a chain of faces joins them (a shared vertex is
+    enough).  A face with an index outside [0, n_vertices) joins nothing and is counted.  ``workspace``: a contiguous
+    8-byte-aligned device tensor of at least ``mesh_components_workspace_bytes(n_vertices, F)`` bytes (None: allocated); what it
+    holds does not matter.  Returns dict(labels int32 [V]: the smallest vertex index of the vertex's component; triangles int32
+    [V] and vertices int32 [V]: at a root ``r == labels[r]`` the faces and the vertices of its component, 0 elsewhere;
+    n_components; n_ignored) after ONE readback of the two counters.  What is wrong with the arguments raises ValueError before
+    any launch.  Not part of this: per-component area or volume, and meshes of 2^31 vertices or faces or more."""
+    if not (isinstance(faces, Tensor) and faces.is_cuda and faces.dtype == torch.int64 and faces.dim() == 2
+            and faces.shape[1] == 3 and faces.is_contiguous()):
+        raise ValueError("faces: a contiguous int64 device tensor [F,3]")
+    V, F = int(n_vertices), int(faces.shape[0])
+    if V < 0 or V >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"n_vertices = {V} and F = {F} must lie in [0, 2^31)")
+    dev = faces.device
+    need = mesh_components_workspace_bytes(V, F)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
+              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
+        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on faces' device")
+    labels, triangles, vertices = (torch.empty((V,), dtype=torch.int32, device=dev) for _ in range(3))
+    counters = torch.empty((2,), dtype=torch.int64, device=dev)
+    check(_lib.load().ns_mesh_components(_ptr(faces), F, V, _ptr(labels), _ptr(triangles), _ptr(vertices), _ptr(counters),
+                                         _ptr(workspace), _stream(dev)), "ns_mesh_components")
+    n_components, n_ignored = (int(v) for v in counters.cpu())                 # the one readback
+    return {"labels": labels, "triangles": triangles, "vertices": vertices, "n_components": n_components,
+            "n_ignored": n_ignored}
+
+
+def mesh_select(vertices, faces, labels, keep, extras=()):
+    """The part of a mesh whose components are kept -- plain torch on whatever device the tensors live on, no kernel of this
+    library.  ``vertices`` [V,...], ``faces`` int64 [F,3], ``labels`` [V] as ``mesh_components`` returns them, ``keep`` bool [V],
+    read at the component roots only: vertex v stays iff ``keep[labels[v]]``, a face iff its first vertex does (a face with an
+    index outside [0, V) never does).  Returns dict(vertices: the kept ones in ascending index order -- ascending key order for
+    ``mesh_weld``'s --; faces: the kept ones in their original order, renumbered; extras: every tensor of ``extras`` (one row per
+    vertex, such as colours; a None stays None) cut as the vertices are; index int64 [V]: the new index of an old vertex, -1 for
+    a dropped one)."""
+    V = int(labels.shape[0])
+    if not (vertices.shape[0] == V and keep.shape == labels.shape and keep.dtype == torch.bool and faces.dim() == 2
+            and faces.shape[1] == 3 and all(e is None or e.shape[0] == V for e in extras)):
+        raise ValueError("vertices [V,...], faces [F,3], labels [V], keep bool [V], extras of V rows each")
+    faces = faces.long()
+    kept_vertex = keep[labels.long()]
+    index = torch.where(kept_vertex, torch.cumsum(kept_vertex, 0) - 1, torch.full_like(labels, -1, dtype=torch.int64))
+    in_range = ((faces >= 0) & (faces < V)).all(dim=1)
+    first = faces[:, 0].clamp(0, max(V - 1, 0))
+    kept_face = in_range & kept_vertex[first] if V > 0 else in_range            # V == 0: no face is in range
+    return {"vertices": vertices[kept_vertex], "faces": index[faces[kept_face]],
+            "extras": tuple(None if e is None else e[kept_vertex] for e in extras), "index": index}
+
+
 # ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b, quantised on the device) -----------------------------
 def frame_to8b(rgb, alpha=None, out=None, channels: int = 3):
     """ns_frame_to8b: ``run_nerf_helpers.to8b`` of a rendered frame on the device -- (uint8) trunc(255 * clip(x, 0, 1)), one fp32

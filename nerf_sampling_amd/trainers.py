@@ -47,7 +47,8 @@ class Trainer:
                  device_ssim: bool = False, device_depth: bool = False, device_cloud: bool = False,
                  cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False,
                  device_video: bool = False, device_mesh: bool = False, mesh_resolution: int = 256,
-                 mesh_threshold: float = 50.0, mesh_bound: float = 1.5):
+                 mesh_threshold: float = 50.0, mesh_bound: float = 1.5, mesh_min_triangles: int = 0,
+                 mesh_keep_largest: int = 0):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -109,12 +110,19 @@ class Trainer:
         # device_mesh (not in the reference; default off): render() also extracts the isosurface of the field's density on the
         # device (nerf_utils.scene_mesh, ns_mesh_extract) -- scene_mesh.ply beside the frames: the density of the fine network
         # (the coarse one where there is none) on a mesh_resolution^3 lattice over [-mesh_bound, mesh_bound]^3, cut at
-        # mesh_threshold (50 is a starting value, not a property of a scene: lower or raise it per scene).  The frames and
-        # psnr.txt are those of the run without the switch.
+        # mesh_threshold (50 is a starting value, not a property of a scene: lower it where the surface has holes).  The
+        # floaters that brings are dropped by the component filter (nerf_utils.mesh_filter, ns_mesh_components; default off):
+        # only the connected components of at least mesh_min_triangles triangles stay, and of those only the
+        # mesh_keep_largest largest.  The frames and psnr.txt are those of the run without the switch.
         self.device_mesh = bool(device_mesh)
         self.mesh_resolution, self.mesh_threshold, self.mesh_bound = int(mesh_resolution), float(mesh_threshold), float(mesh_bound)
         if self.mesh_resolution < 2 or not self.mesh_bound > 0.0:
             raise ValueError("mesh_resolution must be at least 2 and mesh_bound positive")
+        for name in ("mesh_min_triangles", "mesh_keep_largest"):
+            value = getattr(self, name)
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
+            setattr(self, name, int(value))
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -215,7 +223,8 @@ class Trainer:
         """renderonly_{test|path}_{step:06d}/ with NNN.png, psnr.txt[, scene_data.pt] -- Trainer.py:181-230
         (no mp4; under device_video without render_test: rgb/NNN.png and disp/NNN.png through nerf_utils.write_video).  Under
         device_cloud also scene_cloud.pt and scene_cloud.ply of the same poses (nerf_utils.scene_cloud); under device_mesh also
-        scene_mesh.ply, the isosurface of the field's density (nerf_utils.scene_mesh)."""
+        scene_mesh.ply, the isosurface of the field's density (nerf_utils.scene_mesh_filtered), without its small components where
+        mesh_min_triangles or mesh_keep_largest is set."""
         with torch.no_grad():
             images = images[i_test] if render_test else None
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
@@ -232,11 +241,17 @@ class Trainer:
                       f", {cloud['pts'].shape[0]} written to {testsavedir}")
             if self.device_mesh:
                 fine = render_kwargs_test.get("network_fine")
-                mesh = nerf_utils.scene_mesh(fine if fine is not None else render_kwargs_test["network_fn"],
-                                             bound=self.mesh_bound, resolution=self.mesh_resolution,
-                                             threshold=self.mesh_threshold, savedir=testsavedir)
+                mesh = nerf_utils.scene_mesh_filtered(fine if fine is not None else render_kwargs_test["network_fn"],
+                                                      bound=self.mesh_bound, resolution=self.mesh_resolution,
+                                                      threshold=self.mesh_threshold, savedir=testsavedir,
+                                                      min_component_triangles=self.mesh_min_triangles,
+                                                      keep_largest=self.mesh_keep_largest)
+                filtered = ""
+                if "n_components" in mesh:
+                    filtered = (f"; {mesh['n_kept_components']} of {mesh['n_components']} components kept, "
+                                f"{mesh['n_dropped_triangles']} triangles dropped")
                 print(f"scene mesh: {mesh['faces'].shape[0]} triangles on {mesh['vertices'].shape[0]} vertices at density "
-                      f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped), written to {testsavedir}")
+                      f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped{filtered}), written to {testsavedir}")
             if self.device_eval and render_test and self.render_factor == 0:
                 ds, ids = self._ray_dataset, i_test
                 if ds is None:          # called on its own: the test views alone go to the device
