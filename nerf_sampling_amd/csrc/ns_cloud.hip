@@ -12,15 +12,15 @@
 //            earlier (j, wave) cells of its share (through LDS) + the kept lanes below it (__ballot, a 64-bit mask, and a popcount).
 // No atomics and nothing that waits on another workgroup's memory: a launch boundary is the only ordering between workgroups, so
 // the record order depends on the weights alone.
+#include "ns_block.h"
 #include "ns_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+using ns::kBlock;
+using ns::kWaves;
 constexpr int kShare = NS_CLOUD_SHARE;
-constexpr int kSteps = kShare / kBlock;
-static_assert(kShare % kBlock == 0, "a whole number of elements per thread");
+constexpr int kSteps = ns::ShareOf<kShare>::steps;
 
 // the predicate: utils.py:36-43 get_min_indices, weights >= min_weight
 __device__ __forceinline__ bool cloud_keeps(float w, float min_weight) { return w >= min_weight; }
@@ -48,65 +48,16 @@ cloud_count_kernel(const float* __restrict__ w, int64_t stride, uint32_t total, 
                    int64_t* __restrict__ counts) {
   __shared__ int wave_counts[kWaves];
   float wv[kSteps];
-  int n = __popc(cloud_load(w, stride, total, N, min_weight, wv));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_counts[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) s += wave_counts[v];
-    counts[blockIdx.x] = s;
-  }
+  const int n = ns::block_sum<int>(__popc(cloud_load(w, stride, total, N, min_weight, wv)), wave_counts);
+  if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
-// counts[g] <- *count + counts[0] + ... + counts[g - 1]; *count += the sum of all.  One workgroup walks tiles of kScanTile
-// entries: thread t owns kScanPer consecutive ones, the lanes of a wave are scanned with shuffles, the waves through LDS (two
-// buffers in turn, so one barrier per tile), the tiles by a running carry every thread keeps.
-constexpr int kScanPer = 8;
-constexpr int kScanTile = kBlock * kScanPer;
-
+// counts[g] <- *count + counts[0] + ... + counts[g - 1]; *count += the sum of all (ns::share_scan, one workgroup)
 __global__ void __launch_bounds__(kBlock)
 cloud_scan_kernel(int64_t* __restrict__ counts, int groups, int64_t* __restrict__ count) {
-  __shared__ int64_t wave_totals[2][kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t carry = *count;                                  // read by every thread before thread 0 writes it, below the last barrier
-  int buf = 0;
-  for (int tile0 = 0; tile0 < groups; tile0 += kScanTile, buf ^= 1) {
-    const int first = tile0 + static_cast<int>(threadIdx.x) * kScanPer;
-    int64_t v[kScanPer];
-    int64_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < kScanPer; ++i) {
-      v[i] = first + i < groups ? counts[first + i] : 0;
-      mine += v[i];
-    }
-    int64_t incl = mine;                                   // inclusive scan over the lanes of the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_totals[buf][wave] = incl;
-    __syncthreads();
-    int64_t before = carry, tile_total = 0;
-#pragma unroll
-    for (int v_ = 0; v_ < kWaves; ++v_) {
-      const int64_t t = wave_totals[buf][v_];
-      if (v_ < wave) before += t;
-      tile_total += t;
-    }
-    int64_t run = before + (incl - mine);
-#pragma unroll
-    for (int i = 0; i < kScanPer; ++i) {
-      if (first + i < groups) counts[first + i] = run;
-      run += v[i];
-    }
-    carry += tile_total;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) *count = carry;
+  const int64_t total = ns::share_scan(counts, groups, *count);
+  __syncthreads();                                         // every thread has read *count
+  if (threadIdx.x == 0) *count = total;
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -115,32 +66,15 @@ cloud_scatter_kernel(const float* __restrict__ o, const float* __restrict__ d, c
                      uint32_t total, uint32_t N, float min_weight, const int64_t* __restrict__ bases,
                      float* __restrict__ pts_out, float* __restrict__ w_out, float* __restrict__ rgb_out, int64_t capacity) {
   __shared__ int cell_counts[kSteps][kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float wv[kSteps];
-  const uint32_t kept = cloud_load(w, w_stride, total, N, min_weight, wv);
-  int below[kSteps];                                       // kept lanes of this wave below this one, per step
-#pragma unroll
-  for (int j = 0; j < kSteps; ++j) {
-    const unsigned long long mask = __ballot((kept >> j) & 1u);
-    below[j] = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) cell_counts[j][wave] = __popcll(mask);
-  }
-  __syncthreads();
   const int64_t base = bases[blockIdx.x];
   if (base >= capacity) return;                            // every record of this share lies at or beyond the capacity
+  float wv[kSteps];
+  const uint32_t kept = cloud_load(w, w_stride, total, N, min_weight, wv);
   const uint32_t e0 = blockIdx.x * static_cast<uint32_t>(kShare) + threadIdx.x;
-  int cells_before = 0;                                    // kept elements of the earlier (j, wave) cells
-#pragma unroll
-  for (int j = 0; j < kSteps; ++j) {
-    int mine = cells_before;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) {
-      const int c = cell_counts[j][v];
-      if (v < wave) mine += c;
-      cells_before += c;
-    }
-    if ((kept >> j) & 1u) {
-      const int64_t i = base + mine + below[j];
+  const auto keeps = [kept](int j) { return ((kept >> j) & 1u) != 0u; };
+  ns::share_place<kSteps>(keeps, cell_counts, [&](int j, int at) {    // at: kept elements of the share before this one
+    if (keeps(j)) {
+      const int64_t i = base + at;
       if (i >= 0 && i < capacity) {                        // a counter that was negative places nothing below record 0
         const uint32_t e = e0 + j * kBlock;
         const uint32_t r = e / N, k = e - r * N;
@@ -157,21 +91,18 @@ cloud_scatter_kernel(const float* __restrict__ o, const float* __restrict__ d, c
         }
       }
     }
-  }
+  });
 }
 
-// R * N in [1, 2^31): the flat element index and its division by N are 32-bit in the kernels
-bool cloud_shape_ok(int64_t R, int N) { return R >= 1 && N >= 1 && R <= ((int64_t(1) << 31) - 1) / N; }
-
-int64_t cloud_groups(int64_t R, int N) { return (R * N + kShare - 1) / kShare; }
+int64_t cloud_groups(int64_t R, int N) { return ns::cdiv(R * N, kShare); }
 
 }  // namespace
 
 extern "C" {
 
 int64_t ns_cloud_workspace_bytes(int64_t R, int N) {
-  if (!cloud_shape_ok(R, N)) return 0;
-  return (cloud_groups(R, N) * static_cast<int64_t>(sizeof(int64_t)) + 255) / 256 * 256;
+  if (!ns::flat_shape_ok(R, N)) return 0;
+  return ns::round_256(cloud_groups(R, N) * static_cast<int64_t>(sizeof(int64_t)));
 }
 
 int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, int64_t z_row_stride, const float* w_dev,
@@ -179,7 +110,7 @@ int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, 
                     float* pts_out, float* w_out, float* rgb_out, int64_t capacity, int64_t* count_dev, void* workspace_dev,
                     void* stream) {
   NS_REQUIRE(R >= 0 && N >= 1, "R must be at least 0 and N at least 1");
-  NS_REQUIRE(R == 0 || cloud_shape_ok(R, N), "R * N must be below 2^31");
+  NS_REQUIRE(R == 0 || ns::flat_shape_ok(R, N), "R * N must be below 2^31");
   NS_REQUIRE(z_row_stride == 0 || z_row_stride >= N, "z_row_stride is 0 (packed) or at least N floats");
   NS_REQUIRE(w_row_stride == 0 || w_row_stride >= N, "w_row_stride is 0 (packed) or at least N floats");
   NS_REQUIRE(rgb_stride == 0 || rgb_stride >= 3, "rgb_stride is 0 (packed) or at least 3 floats");
@@ -187,8 +118,7 @@ int ns_cloud_append(const float* o_dev, const float* d_dev, const float* z_dev, 
   NS_REQUIRE(capacity == 0 || (pts_out && w_out), "pts_out and w_out are required when capacity > 0");
   NS_REQUIRE(!rgb_out || rgb_dev || R == 0, "rgb_out without rgb_dev");
   NS_REQUIRE(count_dev, "null counter");
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(count_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace_dev) & 7) == 0,
-             "count_dev and workspace_dev are 8-byte aligned");
+  NS_REQUIRE(ns::aligned(count_dev, 8) && ns::aligned(workspace_dev, 8), "count_dev and workspace_dev are 8-byte aligned");
   if (R == 0) return NS_OK;
   NS_REQUIRE(o_dev && d_dev && z_dev && w_dev && workspace_dev, "null pointer");
   const int64_t total = R * N;

@@ -17,6 +17,14 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // ceil-div on 64-bit sizes
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// what the evaluation entries ask of their sizes and pointers: a count a 32-bit index can hold, R * N in [1, 2^31) (the flat
+// element index and its division by N are 32-bit in the kernels), a pointer on a multiple of `a` bytes (a power of two; NULL
+// is), and a workspace size rounded up to whole 256-byte lines
+inline bool below_2_31(int64_t n) { return n < (int64_t(1) << 31); }
+inline bool flat_shape_ok(int64_t R, int N) { return R >= 1 && N >= 1 && R <= ((int64_t(1) << 31) - 1) / N; }
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline int64_t round_256(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+
 // grid for grid-stride elementwise kernels: enough blocks to fill 256 CUs x 8, capped
 inline int ew_grid(int64_t n, int block) {
   int64_t g = cdiv(n, block);

@@ -15,11 +15,13 @@
 // maximum of the frames' maps on the device, ns_map_to8b divides by it where it lies and quantises with the same to8b.
 #include <cmath>
 
+#include "ns_block.h"
 #include "ns_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using ns::kBlock;
+using ns::kWaves;
 constexpr int kGroup = 4;
 
 // run_nerf_helpers.py:11.  The comparisons (not fmaxf / fminf) state what happens to the values numpy leaves to the platform:
@@ -131,6 +133,7 @@ map_to8b_kernel(const float* __restrict__ map, int stride, int64_t n, const floa
 // seen).  Shaped as ns_image_sqerr: workgroup g owns the kMaxShare values from g * kMaxShare on and leaves (max, flag) in
 // partial[g]; a second launch of ONE workgroup folds the partials, and under `accumulate` the state already there, into the
 // state.  A maximum does not depend on the order of its comparisons: no atomics.  (-0.0 against +0.0 is whichever came first.)
+// block_fold is ns::block_sum with fold for +; it stays here: a combine parameter on block_sum would cost more lines than this.
 constexpr int kMaxPerThread = 8;
 constexpr int kMaxShare = kBlock * kMaxPerThread;
 
@@ -160,13 +163,13 @@ __device__ __forceinline__ MaxState block_fold(MaxState s, MaxState* wave_states
   __syncthreads();
   MaxState r = wave_states[0];
 #pragma unroll
-  for (int w = 1; w < kBlock / 64; ++w) fold(r, wave_states[w]);
+  for (int w = 1; w < kWaves; ++w) fold(r, wave_states[w]);
   return r;
 }
 
 __global__ void __launch_bounds__(kBlock)
 map_max_kernel(const float* __restrict__ map, int stride, int64_t n, MaxState* __restrict__ partial, int wide_loads) {
-  __shared__ MaxState wave_states[kBlock / 64];
+  __shared__ MaxState wave_states[kWaves];
   const int64_t base = static_cast<int64_t>(blockIdx.x) * kMaxShare;
   MaxState s = {-INFINITY, 0.0f};
   if (wide_loads) {                                          // packed, 16-byte aligned base: kMaxShare / 4 float4s per share
@@ -193,7 +196,7 @@ map_max_kernel(const float* __restrict__ map, int stride, int64_t n, MaxState* _
 
 __global__ void __launch_bounds__(kBlock)
 map_max_combine_kernel(const MaxState* __restrict__ partial, int n_partial, int accumulate, MaxState* state) {
-  __shared__ MaxState wave_states[kBlock / 64];
+  __shared__ MaxState wave_states[kWaves];
   MaxState s = {-INFINITY, 0.0f};
   for (int i = threadIdx.x; i < n_partial; i += kBlock) fold(s, partial[i]);
   MaxState r = block_fold(s, wave_states);
@@ -207,7 +210,7 @@ map_max_combine_kernel(const MaxState* __restrict__ partial, int n_partial, int 
   }
 }
 
-int64_t map_max_groups(int64_t n) { return (n + kMaxShare - 1) / kMaxShare; }
+int64_t map_max_groups(int64_t n) { return ns::cdiv(n, kMaxShare); }
 
 // what both map entries ask of (stride, n); `who` is the entry's name
 int check_map(const char* who, int64_t stride, int64_t n) {
@@ -215,7 +218,7 @@ int check_map(const char* who, int64_t stride, int64_t n) {
     ns::set_error("%s: negative n", who);
     return NS_E_INVALID;
   }
-  if (n >= (int64_t(1) << 31)) {
+  if (!ns::below_2_31(n)) {
     ns::set_error("%s: n must be below 2^31", who);
     return NS_E_INVALID;
   }
@@ -242,8 +245,8 @@ int ns_frame_to8b(const float* rgb_dev, int64_t rgb_stride, const float* alpha_d
   const int stride = rgb_stride == 0 ? 3 : static_cast<int>(rgb_stride);
   const int groups = (n + kGroup - 1) / kGroup;
   const int grid = (groups + kBlock - 1) / kBlock;                  // at most 2^19 workgroups
-  const int wide_loads = (reinterpret_cast<uintptr_t>(rgb_dev) & 15) == 0;
-  const int dword_stores = (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+  const int wide_loads = ns::aligned(rgb_dev, 16);
+  const int dword_stores = ns::aligned(out_dev, 4);
   hipStream_t s = ns::as_stream(stream);
   if (out_channels == 3)
     frame_to8b_kernel<3><<<grid, kBlock, 0, s>>>(rgb_dev, stride, alpha_dev, n, out_dev, wide_loads, dword_stores);
@@ -254,8 +257,8 @@ int ns_frame_to8b(const float* rgb_dev, int64_t rgb_stride, const float* alpha_d
 }
 
 int64_t ns_map_max_workspace_bytes(int64_t n) {
-  if (n <= 0 || n >= (int64_t(1) << 31)) return 0;
-  return (map_max_groups(n) * static_cast<int64_t>(sizeof(MaxState)) + 255) / 256 * 256;
+  if (n <= 0 || !ns::below_2_31(n)) return 0;
+  return ns::round_256(map_max_groups(n) * static_cast<int64_t>(sizeof(MaxState)));
 }
 
 int ns_map_max(const float* map_dev, int64_t stride, int64_t n, int accumulate, float* state_dev, void* workspace_dev,
@@ -263,15 +266,15 @@ int ns_map_max(const float* map_dev, int64_t stride, int64_t n, int accumulate, 
   const int rc = check_map(__func__, stride, n);
   if (rc != NS_OK) return rc;
   NS_REQUIRE(state_dev, "null pointer");
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 3) == 0, "state_dev must be 4-byte aligned");
+  NS_REQUIRE(ns::aligned(state_dev, 4), "state_dev must be 4-byte aligned");
   NS_REQUIRE(n == 0 || (map_dev && workspace_dev), "null pointer");
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(workspace_dev) & 7) == 0, "workspace_dev must be 8-byte aligned");
+  NS_REQUIRE(ns::aligned(workspace_dev, 8), "workspace_dev must be 8-byte aligned");
   if (n == 0 && accumulate) return NS_OK;                    // nothing to fold: the state stays
   const int groups = static_cast<int>(map_max_groups(n));    // at most 2^20
   MaxState* partial = static_cast<MaxState*>(workspace_dev);
   hipStream_t s = ns::as_stream(stream);
   if (n > 0) {
-    const int wide_loads = stride == 1 && (reinterpret_cast<uintptr_t>(map_dev) & 15) == 0;
+    const int wide_loads = stride == 1 && ns::aligned(map_dev, 16);
     map_max_kernel<<<groups, kBlock, 0, s>>>(map_dev, static_cast<int>(stride), n, partial, wide_loads);
     NS_LAUNCH_CHECK();
   }
@@ -283,13 +286,13 @@ int ns_map_max(const float* map_dev, int64_t stride, int64_t n, int accumulate, 
 int ns_map_to8b(const float* map_dev, int64_t stride, int64_t n, const float* denom_dev, uint8_t* out_dev, void* stream) {
   const int rc = check_map(__func__, stride, n);
   if (rc != NS_OK) return rc;
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(denom_dev) & 3) == 0, "denom_dev must be 4-byte aligned");
+  NS_REQUIRE(ns::aligned(denom_dev, 4), "denom_dev must be 4-byte aligned");
   if (n == 0) return NS_OK;
   NS_REQUIRE(map_dev && out_dev, "null pointer");
   const int64_t groups = (n + kGroup - 1) / kGroup;
   const int grid = static_cast<int>((groups + kBlock - 1) / kBlock);          // at most 2^21 workgroups
-  const int wide_loads = stride == 1 && (reinterpret_cast<uintptr_t>(map_dev) & 15) == 0;
-  const int dword_stores = (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+  const int wide_loads = stride == 1 && ns::aligned(map_dev, 16);
+  const int dword_stores = ns::aligned(out_dev, 4);
   map_to8b_kernel<<<grid, kBlock, 0, ns::as_stream(stream)>>>(map_dev, static_cast<int>(stride), n, denom_dev, out_dev,
                                                               wide_loads, dword_stores);
   NS_LAUNCH_CHECK();

@@ -17,16 +17,16 @@
 // No atomics and nothing that waits on another workgroup's memory: the triangle order depends on the lattice alone.
 #include <cmath>
 
+#include "ns_block.h"
 #include "ns_common.h"
 #include "ns_mesh_table.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+using ns::kBlock;
+using ns::kWaves;
 constexpr int kShare = NS_MESH_SHARE;
-constexpr int kSteps = kShare / kBlock;
-static_assert(kShare % kBlock == 0, "a whole number of cells per thread");
+constexpr int kSteps = ns::ShareOf<kShare>::steps;
 
 __constant__ ns_mesh::CaseTable kCases = ns_mesh::make_case_table();
 
@@ -139,91 +139,36 @@ mesh_count_kernel(Lattice L, int64_t* __restrict__ counts, int groups) {
       skipped += c.skipped ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n += __shfl_xor(n, off, 64);
-    skipped += __shfl_xor(skipped, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    wave_counts[0][threadIdx.x >> 6] = n;
-    wave_counts[1][threadIdx.x >> 6] = skipped;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    int s = 0;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) s += wave_counts[threadIdx.x][v];
-    counts[static_cast<int64_t>(threadIdx.x) * groups + blockIdx.x] = s;
-  }
+  ns::wave_sum_to(n, wave_counts[0], skipped, wave_counts[1]);
+  __syncthreads();                                         // one barrier for both sums
+  if (threadIdx.x < 2) counts[static_cast<int64_t>(threadIdx.x) * groups + blockIdx.x] = ns::slots_sum(wave_counts[threadIdx.x]);
 }
 
-// counts[g] <- counts[0] + ... + counts[g - 1]; totals[0] = the sum of all, totals[1] = the sum of counts[groups ..].  One
-// workgroup, shaped as ns_cloud.hip's scan: thread t owns kScanPer consecutive entries of a tile, the lanes of a wave are scanned
-// with shuffles, the waves through LDS (two buffers in turn, one barrier per tile), the tiles by a carry every thread keeps.
-constexpr int kScanPer = 8;
-constexpr int kScanTile = kBlock * kScanPer;
-
+// counts[g] <- counts[0] + ... + counts[g - 1] (ns::share_scan, one workgroup); totals[0] = the sum of all, totals[1] = the sum
+// of counts[groups ..], which every thread adds up for its own entries beside the scan's loads
 __global__ void __launch_bounds__(kBlock)
 mesh_scan_kernel(int64_t* __restrict__ counts, int groups, int64_t* __restrict__ totals) {
-  __shared__ int64_t wave_totals[2][kWaves];
   __shared__ int64_t wave_skipped[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t* skipped_counts = counts + groups;
-  int64_t carry = 0, skipped = 0;
-  int buf = 0;
-  for (int tile0 = 0; tile0 < groups; tile0 += kScanTile, buf ^= 1) {
-    const int first = tile0 + static_cast<int>(threadIdx.x) * kScanPer;
-    int64_t v[kScanPer];
-    int64_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < kScanPer; ++i) {
-      v[i] = first + i < groups ? counts[first + i] : 0;
-      mine += v[i];
-      skipped += first + i < groups ? skipped_counts[first + i] : 0;
-    }
-    int64_t incl = mine;                                   // inclusive scan over the lanes of the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_totals[buf][wave] = incl;
-    __syncthreads();
-    int64_t before = carry, tile_total = 0;
-#pragma unroll
-    for (int v_ = 0; v_ < kWaves; ++v_) {
-      const int64_t t = wave_totals[buf][v_];
-      if (v_ < wave) before += t;
-      tile_total += t;
-    }
-    int64_t run = before + (incl - mine);
-#pragma unroll
-    for (int i = 0; i < kScanPer; ++i) {
-      if (first + i < groups) counts[first + i] = run;
-      run += v[i];
-    }
-    carry += tile_total;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) skipped += __shfl_xor(skipped, off, 64);
-  if (lane == 0) wave_skipped[wave] = skipped;
-  __syncthreads();
+  int64_t skipped = 0;
+  const int64_t triangles = ns::share_scan(counts, groups, 0, [&](int g, bool in_range) {
+    skipped += in_range ? skipped_counts[g] : 0;
+  });
+  skipped = ns::block_sum(skipped, wave_skipped);
   if (threadIdx.x == 0) {
-    int64_t s = 0;
-#pragma unroll
-    for (int v_ = 0; v_ < kWaves; ++v_) s += wave_skipped[v_];
-    totals[0] = carry;
-    totals[1] = s;
+    totals[0] = triangles;
+    totals[1] = skipped;
   }
 }
 
+// ns::share_place's placement, written out: a step's scan follows its eight loads, and the 7 300-instruction schedule hangs on it
 __global__ void __launch_bounds__(kBlock)
 mesh_emit_kernel(Lattice L, Frame F, const int64_t* __restrict__ bases, float* __restrict__ tri_out,
                  int64_t* __restrict__ key_out, int64_t capacity) {
   __shared__ int group_counts[kSteps][kWaves];
   const int64_t base = bases[blockIdx.x];
   if (base >= capacity) return;                            // every triangle of this share lies at or beyond the capacity
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave = threadIdx.x >> 6;
   const uint32_t e0 = blockIdx.x * static_cast<uint32_t>(kShare) + threadIdx.x;
   Cell c[kSteps];
   int below[kSteps];                                       // triangles of the lanes of this wave below this one, per step
@@ -232,14 +177,7 @@ mesh_emit_kernel(Lattice L, Frame F, const int64_t* __restrict__ bases, float* _
     const uint32_t e = e0 + s * kBlock;
     c[s].inside = 0u;
     const int n = e < L.cells ? cell_load(L, e, c[s]) : 0;
-    int incl = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    below[s] = incl - n;
-    if (lane == 63) group_counts[s][wave] = incl;
+    below[s] = ns::wave_place(n, &group_counts[s][wave]);
   }
   __syncthreads();
   int groups_before = 0;                                   // triangles of the earlier (s, wave) groups
@@ -266,13 +204,13 @@ mesh_emit_kernel(Lattice L, Frame F, const int64_t* __restrict__ bases, float* _
 // every dimension at least 2 and Gx * Gy * Gz in [8, 2^31): lattice and cell indices are 32-bit in the kernels
 bool mesh_shape_ok(int Gx, int Gy, int Gz) {
   if (Gx < 2 || Gy < 2 || Gz < 2) return false;
-  const int64_t limit = int64_t(1) << 31, xy = static_cast<int64_t>(Gx) * Gy;
-  return xy < limit && xy * Gz < limit;
+  const int64_t xy = static_cast<int64_t>(Gx) * Gy;
+  return ns::below_2_31(xy) && ns::below_2_31(xy * Gz);
 }
 
 int64_t mesh_cells(int Gx, int Gy, int Gz) { return static_cast<int64_t>(Gx - 1) * (Gy - 1) * (Gz - 1); }
 
-int64_t mesh_groups(int Gx, int Gy, int Gz) { return (mesh_cells(Gx, Gy, Gz) + kShare - 1) / kShare; }
+int64_t mesh_groups(int Gx, int Gy, int Gz) { return ns::cdiv(mesh_cells(Gx, Gy, Gz), kShare); }
 
 }  // namespace
 
@@ -280,7 +218,7 @@ extern "C" {
 
 int64_t ns_mesh_workspace_bytes(int Gx, int Gy, int Gz) {
   if (!mesh_shape_ok(Gx, Gy, Gz)) return 0;
-  return (mesh_groups(Gx, Gy, Gz) * 2 * static_cast<int64_t>(sizeof(int64_t)) + 255) / 256 * 256;
+  return ns::round_256(mesh_groups(Gx, Gy, Gz) * 2 * static_cast<int64_t>(sizeof(int64_t)));
 }
 
 int ns_mesh_extract(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy, int Gz, float iso, float lo_x, float lo_y,
@@ -292,8 +230,7 @@ int ns_mesh_extract(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy
   NS_REQUIRE(capacity >= 0, "negative capacity");
   NS_REQUIRE(capacity == 0 || (tri_out && key_out), "tri_out and key_out are required when capacity > 0");
   NS_REQUIRE(count_dev && sigma_dev && workspace_dev, "null pointer");
-  NS_REQUIRE((reinterpret_cast<uintptr_t>(count_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(key_out) & 7) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace_dev) & 7) == 0,
+  NS_REQUIRE(ns::aligned(count_dev, 8) && ns::aligned(key_out, 8) && ns::aligned(workspace_dev, 8),
              "count_dev, key_out and workspace_dev are 8-byte aligned");
   NS_REQUIRE(std::isfinite(iso) && std::isfinite(lo_x) && std::isfinite(lo_y) && std::isfinite(lo_z), "iso and lo must be finite");
   NS_REQUIRE(std::isfinite(h_x) && std::isfinite(h_y) && std::isfinite(h_z) && h_x > 0.0f && h_y > 0.0f && h_z > 0.0f,

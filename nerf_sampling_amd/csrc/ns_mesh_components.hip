@@ -19,15 +19,15 @@
 // of the same tree at or below x, from which the walk still ends at a root of x's tree -- a stale read costs steps, or one more
 // turn of unite's loop, never a wrong hook or a wrong "they meet": whether r is still a root is decided by the atomicCAS on r's
 // own word alone, and two positions that were ever in one tree still are.
+#include "ns_block.h"
 #include "ns_common.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+using ns::kBlock;
+using ns::kWaves;
 constexpr int kShare = NS_MESH_COMPONENTS_SHARE;
-constexpr int kSteps = kShare / kBlock;
-static_assert(kShare % kBlock == 0, "a whole number of faces per thread");
+constexpr int kSteps = ns::ShareOf<kShare>::steps;
 
 __device__ __forceinline__ int32_t load_word(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -82,18 +82,6 @@ __device__ __forceinline__ void wave_add_by_key(int32_t* counts, int32_t key, bo
   }
 }
 
-// the sum of n over the workgroup, in thread 0
-__device__ __forceinline__ int block_sum(int n, int* wave_sums) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = n;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) s += wave_sums[w];
-  return s;
-}
-
 // counts[key[s]] += 1 for every active item of the workgroup.  A surface is mostly one component: the items that carry the key of
 // the workgroup's first item are summed over the workgroup and added once -- per wave they would queue 16 atomics per workgroup
 // on ONE word --, the others per wave.  Every thread of the workgroup calls.
@@ -109,7 +97,7 @@ __device__ __forceinline__ void block_add_by_key(int32_t* counts, const int32_t 
     mine += first ? 1 : 0;
     wave_add_by_key(counts, key[s], active[s] && !first);
   }
-  const int total = block_sum(mine, wave_sums);
+  const int total = ns::block_sum(mine, wave_sums);
   if (threadIdx.x == 0 && total != 0) atomicAdd(counts + k0, total);
 }
 
@@ -147,7 +135,7 @@ cc_hook_kernel(const int64_t* __restrict__ faces, int64_t F, int64_t V, int32_t*
     if (v[0] != v[1]) unite(parent, v[0], v[1]);
     if (v[0] != v[2] && v[1] != v[2]) unite(parent, v[0], v[2]);
   }
-  const int total = block_sum(ignored, wave_sums);
+  const int total = ns::block_sum(ignored, wave_sums);
   if (threadIdx.x == 0 && total != 0) atomicAdd(counters, total);
 }
 
@@ -176,7 +164,7 @@ cc_flatten_kernel(int32_t* label, int32_t* vert_count, int64_t V, int32_t* count
     root[s] = r;
   }
   block_add_by_key(vert_count, root, active, wave_sums[0], &first_key);
-  const int total = block_sum(roots, wave_sums[1]);
+  const int total = ns::block_sum(roots, wave_sums[1]);
   if (threadIdx.x == 0 && total != 0) atomicAdd(counters + 1, total);
 }
 
@@ -208,12 +196,7 @@ __global__ void cc_empty_kernel(int64_t* __restrict__ count_out, int64_t F) {
   count_out[1] = F;
 }
 
-bool cc_shape_ok(int64_t V, int64_t F) {
-  const int64_t limit = int64_t(1) << 31;
-  return V >= 0 && F >= 0 && V < limit && F < limit;
-}
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+bool cc_shape_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && ns::below_2_31(V) && ns::below_2_31(F); }
 
 }  // namespace
 
@@ -229,9 +212,9 @@ int ns_mesh_components(const int64_t* faces_dev, int64_t F, int64_t V, int32_t* 
   NS_REQUIRE(F == 0 || faces_dev, "faces_dev is required when F > 0");
   NS_REQUIRE(V == 0 || (label_dev && tri_count_dev && vert_count_dev && workspace_dev),
              "label_dev, tri_count_dev, vert_count_dev and workspace_dev are required when V > 0");
-  NS_REQUIRE(aligned(count_dev, 8) && aligned(workspace_dev, 8) && aligned(faces_dev, 8),
+  NS_REQUIRE(ns::aligned(count_dev, 8) && ns::aligned(workspace_dev, 8) && ns::aligned(faces_dev, 8),
              "count_dev, workspace_dev and faces_dev are 8-byte aligned");
-  NS_REQUIRE(aligned(label_dev, 4) && aligned(tri_count_dev, 4) && aligned(vert_count_dev, 4),
+  NS_REQUIRE(ns::aligned(label_dev, 4) && ns::aligned(tri_count_dev, 4) && ns::aligned(vert_count_dev, 4),
              "label_dev, tri_count_dev and vert_count_dev are 4-byte aligned");
   hipStream_t s = ns::as_stream(stream);
   if (V == 0) {

@@ -2,12 +2,14 @@
 // sample placement, coarse depths.  All HBM-bound, fp32, one thread per output element or per
 // ray, grid-stride.  Built with -ffp-contract=off so that mul/add stay separate roundings like
 // the reference's eager PyTorch arithmetic.
+#include "ns_block.h"
 #include "ns_common.h"
 #include "ns_place.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using ns::kBlock;
+using ns::kWaves;
 
 using nsplace::linspace_at;
 
@@ -202,28 +204,16 @@ ray_batch_draw_kernel(ns_ray_dataset ds, const int* __restrict__ train_idx, int 
 // ---- frame PSNR on the device (ns_image_sqerr) ----------------------------------------------------------------------
 // sum over the pixels of a row band and the three channels of (double)(fl32(rgb - target))^2.  Workgroup g owns pixels
 // [g * kSqerrShare, (g + 1) * kSqerrShare); thread t adds its pixels g * kSqerrShare + k * kBlock + t in the order of k, the
-// lanes of a wave are combined by a fixed xor tree, the waves in index order by thread 0 -> partial[g].  A second launch of
-// ONE workgroup adds the partials the same way (thread t: partials t, t + kBlock, ... in order).  Every addition is fixed
-// by the pixel count alone -- no atomics, nothing that depends on the CU count; a NaN term makes the sum NaN.
+// workgroup's sum in the fixed order of ns::block_sum -> partial[g].  A second launch of ONE workgroup adds the partials the
+// same way (thread t: partials t, t + kBlock, ... in order).  Every addition is fixed by the pixel count alone -- no atomics,
+// nothing that depends on the CU count; a NaN term makes the sum NaN.
 constexpr int kSqerrPerThread = 8;
 constexpr int kSqerrShare = kBlock * kSqerrPerThread;
-
-__device__ __forceinline__ double block_sum_ordered(double v, double* wave_sums) {   // valid in thread 0
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) wave_sums[wave] = v;
-  __syncthreads();
-  double s = wave_sums[0];
-#pragma unroll
-  for (int w = 1; w < kBlock / 64; ++w) s += wave_sums[w];
-  return s;
-}
 
 __global__ void __launch_bounds__(kBlock)
 image_sqerr_kernel(ns_ray_dataset ds, int img, int pix0, int n, const float* __restrict__ rgb, int stride,
                    double* __restrict__ partial) {
-  __shared__ double wave_sums[kBlock / 64];
+  __shared__ double wave_sums[kWaves];
   const int64_t base = static_cast<int64_t>(blockIdx.x) * kSqerrShare + threadIdx.x;
   double acc = 0.0;
 #pragma unroll
@@ -240,16 +230,16 @@ image_sqerr_kernel(ns_ray_dataset ds, int img, int pix0, int n, const float* __r
       }
     }
   }
-  const double s = block_sum_ordered(acc, wave_sums);
+  const double s = ns::block_sum(acc, wave_sums);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(kBlock)
 image_sqerr_combine_kernel(const double* __restrict__ partial, int n_partial, double* __restrict__ sum) {
-  __shared__ double wave_sums[kBlock / 64];
+  __shared__ double wave_sums[kWaves];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n_partial; i += kBlock) acc += partial[i];
-  const double s = block_sum_ordered(acc, wave_sums);
+  const double s = ns::block_sum(acc, wave_sums);
   if (threadIdx.x == 0) *sum = s;
 }
 
@@ -257,18 +247,18 @@ image_sqerr_combine_kernel(const double* __restrict__ partial, int n_partial, do
 // sum over rays r and samples k of (double)(fl32(z[r, k] - ref[r]))^2, the flat element e = r * N + k.  Workgroup g owns
 // elements [g * kDepthShare, (g + 1) * kDepthShare); thread t adds its elements g * kDepthShare + j * kBlock + t in the order of
 // j (consecutive lanes read consecutive floats of a packed z); lanes, waves and workgroups are combined as ns_image_sqerr's are
-// (block_sum_ordered, partial[g], the same second launch), so every addition is fixed by (R, N) alone.
+// (ns::block_sum, partial[g], the same second launch), so every addition is fixed by (R, N) alone.
 constexpr int kDepthShare = NS_DEPTH_SQERR_SHARE;
-static_assert(kDepthShare % kBlock == 0, "a whole number of elements per thread");
+constexpr int kDepthSteps = ns::ShareOf<kDepthShare>::steps;
 
 __global__ void __launch_bounds__(kBlock)
 depth_sqerr_kernel(const float* __restrict__ z, int64_t stride, const float* __restrict__ ref, uint32_t total, uint32_t N,
                    double* __restrict__ partial) {
-  __shared__ double wave_sums[kBlock / 64];
+  __shared__ double wave_sums[kWaves];
   const uint32_t base = blockIdx.x * static_cast<uint32_t>(kDepthShare) + threadIdx.x;   // below 2^31 + kDepthShare
   double acc = 0.0;
 #pragma unroll
-  for (int j = 0; j < kDepthShare / kBlock; ++j) {
+  for (int j = 0; j < kDepthSteps; ++j) {
     const uint32_t e = base + j * kBlock;
     if (e < total) {
       const uint32_t r = e / N, k = e - r * N;
@@ -276,7 +266,7 @@ depth_sqerr_kernel(const float* __restrict__ z, int64_t stride, const float* __r
       acc += d * d;                                                                            // exact in double
     }
   }
-  const double s = block_sum_ordered(acc, wave_sums);
+  const double s = ns::block_sum(acc, wave_sums);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -308,7 +298,7 @@ image_ssim_kernel(ns_ray_dataset ds, int img, int tiles_x, const float* __restri
   __shared__ float xs[3][kSsimPatchH][kSsimPatchW];      // the rendered frame's patch
   __shared__ float ys[3][kSsimPatchH][kSsimPatchW];      // the target's
   __shared__ double rows[5][kSsimPatchH][kSsimTileW];    // row sums of x, y, x^2, y^2, xy
-  __shared__ double wave_sums[kBlock / 64];
+  __shared__ double wave_sums[kWaves];
   const int H = ds.H, W = ds.W;
   const int oy = (static_cast<int>(blockIdx.x) / tiles_x) * kSsimTileH;
   const int ox = (static_cast<int>(blockIdx.x) % tiles_x) * kSsimTileW;
@@ -358,7 +348,7 @@ image_ssim_kernel(ns_ray_dataset ds, int img, int tiles_x, const float* __restri
     }
     __syncthreads();                                      // rows is rewritten by the next channel
   }
-  const double s = block_sum_ordered(acc, wave_sums);
+  const double s = ns::block_sum(acc, wave_sums);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -608,11 +598,11 @@ int ns_ray_batch_draw(const ns_ray_dataset* ds, const int* train_idx_dev, int n_
   return NS_OK;
 }
 
-static int64_t image_sqerr_groups(int64_t n_pixels) { return (n_pixels + kSqerrShare - 1) / kSqerrShare; }
+static int64_t image_sqerr_groups(int64_t n_pixels) { return ns::cdiv(n_pixels, kSqerrShare); }
 
 int64_t ns_image_sqerr_workspace_bytes(int64_t n_pixels) {
   if (n_pixels <= 0) return 0;
-  return (image_sqerr_groups(n_pixels) * static_cast<int64_t>(sizeof(double)) + 255) / 256 * 256;
+  return ns::round_256(image_sqerr_groups(n_pixels) * static_cast<int64_t>(sizeof(double)));
 }
 
 int ns_image_sqerr(const ns_ray_dataset* ds, int image_idx, int row0, int row1, const float* rgb_dev, int64_t rgb_stride,
@@ -636,25 +626,19 @@ int ns_image_sqerr(const ns_ray_dataset* ds, int image_idx, int row0, int row1, 
   return NS_OK;
 }
 
-// R * N in [1, 2^31): the flat element index and its division by N are 32-bit in the kernel
-static bool depth_sqerr_shape_ok(int64_t R, int N) {
-  return R >= 1 && N >= 1 && R <= ((int64_t(1) << 31) - 1) / N;
-}
-
 int64_t ns_depth_sqerr_workspace_bytes(int64_t R, int N) {
-  if (!depth_sqerr_shape_ok(R, N)) return 0;
-  const int64_t groups = (R * N + kDepthShare - 1) / kDepthShare;
-  return (groups * static_cast<int64_t>(sizeof(double)) + 255) / 256 * 256;
+  if (!ns::flat_shape_ok(R, N)) return 0;
+  return ns::round_256(ns::cdiv(R * N, kDepthShare) * static_cast<int64_t>(sizeof(double)));
 }
 
 int ns_depth_sqerr(const float* z_dev, int64_t z_row_stride, const float* ref_dev, int64_t R, int N, double* sum_dev,
                    void* workspace_dev, void* stream) {
   NS_REQUIRE(z_dev && ref_dev && sum_dev && workspace_dev, "null pointer");
   NS_REQUIRE(R >= 1 && N >= 1, "R and N must be at least 1");
-  NS_REQUIRE(depth_sqerr_shape_ok(R, N), "R * N must be below 2^31");
+  NS_REQUIRE(ns::flat_shape_ok(R, N), "R * N must be below 2^31");
   NS_REQUIRE(z_row_stride == 0 || z_row_stride >= N, "z_row_stride is 0 (packed) or at least N floats");
   const int64_t total = R * N;
-  const int groups = static_cast<int>((total + kDepthShare - 1) / kDepthShare);
+  const int groups = static_cast<int>(ns::cdiv(total, kDepthShare));
   double* partial = static_cast<double*>(workspace_dev);
   hipStream_t s = ns::as_stream(stream);
   depth_sqerr_kernel<<<groups, kBlock, 0, s>>>(z_dev, z_row_stride == 0 ? N : z_row_stride, ref_dev,
@@ -676,7 +660,7 @@ void ns_image_ssim_tile(int* tile_h, int* tile_w) {
 
 int64_t ns_image_ssim_workspace_bytes(int H, int W) {
   if (H < kSsimWin || W < kSsimWin) return 0;
-  return (image_ssim_tiles_y(H) * image_ssim_tiles_x(W) * static_cast<int64_t>(sizeof(double)) + 255) / 256 * 256;
+  return ns::round_256(image_ssim_tiles_y(H) * image_ssim_tiles_x(W) * static_cast<int64_t>(sizeof(double)));
 }
 
 int ns_image_ssim(const ns_ray_dataset* ds, int image_idx, const float* rgb_dev, int64_t rgb_stride, double* sum_dev,

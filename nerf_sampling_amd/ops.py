@@ -152,6 +152,49 @@ def _stream(dev) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _scratch(workspace, need: int, dev, what: str):
+    """the caller's ``workspace`` -- a contiguous 8-byte-aligned tensor of at least ``need`` bytes on ``dev``, the device of
+    ``what`` -- or, for None, ``need`` fresh bytes there"""
+    if workspace is None:
+        return torch.empty((need,), dtype=torch.uint8, device=dev)
+    if not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
+            and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
+        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on {what}'s device")
+    return workspace
+
+
+def _rows(t, name: str, dev):
+    """(R, N, row stride in floats) of ``t``: float32 [R,N] or [R] on ``dev``, contiguous or a column slice (unit inner stride)"""
+    if not (isinstance(t, Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() in (1, 2)):
+        raise ValueError(f"{name}: a float32 tensor [R,N] or [R] on the device of the call's other tensors")
+    R, N = int(t.shape[0]), (int(t.shape[1]) if t.dim() == 2 else 1)
+    if N < 1:
+        raise ValueError(f"{name}: at least one sample per ray, got {tuple(t.shape)}")
+    if t.dim() == 1:
+        stride = 1 if R <= 1 else int(t.stride(0))              # one column of a wider buffer: its row stride
+        if stride < 1:
+            raise ValueError(f"{name}: a vector [R] with a positive stride")
+    else:
+        stride = N if R <= 1 else int(t.stride(0))
+        if (N > 1 and t.stride(1) != 1) or stride < N:
+            raise ValueError(f"{name}: contiguous [R,N], or a column slice of a wider contiguous buffer (unit inner stride)")
+    return R, N, stride
+
+
+def _sum_slot(out, slot, dev):
+    """(out, slot) of a double sum: ``out`` a contiguous 1-d float64 device tensor and ``slot`` an index into it; for None a
+    fresh one-element tensor on ``dev`` and slot 0.  ``dev`` only places that tensor: a caller's ``out`` is taken on whatever
+    device it lives, as it always was"""
+    if out is None:
+        return torch.empty((1,), dtype=torch.float64, device=dev), 0
+    if not (isinstance(out, Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError("out: a contiguous 1-d float64 device tensor")
+    slot = int(slot)
+    if not 0 <= slot < out.numel():
+        raise ValueError(f"slot {slot} out of range [0, {out.numel()})")
+    return out, slot
+
+
 def _c2w_host(c2w) -> np.ndarray:
     """camera-to-world matrix (tensor or array) -> contiguous host float32 [3,4]"""
     c2w = c2w.detach().cpu().numpy() if isinstance(c2w, Tensor) else np.asarray(c2w)
@@ -212,35 +255,16 @@ def depth_sqerr(z, ref, out=None, slot: int = 0, workspace=None):
     is wrong with the arguments raises ValueError before any launch."""
     if not (isinstance(z, Tensor) and z.is_cuda and z.dtype == torch.float32 and z.dim() in (1, 2)):
         raise ValueError("z: a float32 device tensor [R,N] or [R]")
-    R, N = int(z.shape[0]), (int(z.shape[1]) if z.dim() == 2 else 1)
-    if R < 1 or N < 1:
+    R, N, stride = _rows(z, "z", z.device)
+    if R < 1:
         raise ValueError(f"z: at least one ray and one sample, got {tuple(z.shape)}")
     if R * N >= 2 ** 31:
         raise ValueError(f"z: R * N = {R * N} is not below 2^31")
-    if z.dim() == 1:
-        stride = 1 if R == 1 else int(z.stride(0))              # one column of a wider buffer: its row stride
-        if stride < 1:
-            raise ValueError("z: a vector [R] with a positive stride")
-    else:
-        stride = N if R == 1 else int(z.stride(0))
-        if (N > 1 and z.stride(1) != 1) or stride < N:
-            raise ValueError("z: contiguous [R,N], or a column slice of a wider contiguous buffer (unit inner stride)")
     if not (isinstance(ref, Tensor) and ref.is_cuda and ref.device == z.device and ref.dtype == torch.float32
             and tuple(ref.shape) in ((R,), (R, 1)) and ref.is_contiguous()):
         raise ValueError(f"ref: a contiguous float32 tensor of shape ({R},) or ({R}, 1) on z's device")
-    if out is None:
-        out, slot = torch.empty((1,), dtype=torch.float64, device=z.device), 0
-    elif not (isinstance(out, Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1 and out.is_contiguous()):
-        raise ValueError("out: a contiguous 1-d float64 device tensor")
-    slot = int(slot)
-    if not 0 <= slot < out.numel():
-        raise ValueError(f"slot {slot} out of range [0, {out.numel()})")
-    need = depth_sqerr_workspace_bytes(R, N)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=z.device)
-    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.is_contiguous()
-              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"workspace: a contiguous 8-byte-aligned device tensor of at least {need} bytes")
+    out, slot = _sum_slot(out, slot, z.device)
+    workspace = _scratch(workspace, depth_sqerr_workspace_bytes(R, N), z.device, "z")
     check(_lib.load().ns_depth_sqerr(_ptr(z), stride, _ptr(ref), R, N, C.c_void_p(out.data_ptr() + 8 * slot), _ptr(workspace),
                                      _stream(z.device)), "ns_depth_sqerr")
     return out
@@ -259,24 +283,6 @@ def cloud_workspace_bytes(R: int, N: int) -> int:
     """ns_cloud_workspace_bytes: the per-share counts ``cloud_append`` needs for R rays of N samples (0: a shape it refuses, or
     no rays)"""
     return int(_lib.load().ns_cloud_workspace_bytes(int(R), int(N)))
-
-
-def _cloud_rows(t, name: str, dev):
-    """(R, N, row stride in floats) of ``t``: float32 [R,N] or [R] on ``dev``, contiguous or a column slice (unit inner stride)"""
-    if not (isinstance(t, Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() in (1, 2)):
-        raise ValueError(f"{name}: a float32 tensor [R,N] or [R] on the rays' device")
-    R, N = int(t.shape[0]), (int(t.shape[1]) if t.dim() == 2 else 1)
-    if N < 1:
-        raise ValueError(f"{name}: at least one sample per ray, got {tuple(t.shape)}")
-    if t.dim() == 1:
-        stride = 1 if R <= 1 else int(t.stride(0))              # one column of a wider buffer: its row stride
-        if stride < 1:
-            raise ValueError(f"{name}: a vector [R] with a positive stride")
-    else:
-        stride = N if R <= 1 else int(t.stride(0))
-        if (N > 1 and t.stride(1) != 1) or stride < N:
-            raise ValueError(f"{name}: contiguous [R,N], or a column slice of a wider contiguous buffer (unit inner stride)")
-    return R, N, stride
 
 
 def cloud_append(cloud, o, d, z, w, rgb=None, min_weight: float = 0.0):
@@ -298,8 +304,8 @@ def cloud_append(cloud, o, d, z, w, rgb=None, min_weight: float = 0.0):
     R = int(o.shape[0])
     if int(d.shape[0]) != R:
         raise ValueError("o and d: the same number of rays")
-    Rz, N, z_stride = _cloud_rows(z, "z", dev)
-    Rw, Nw, w_stride = _cloud_rows(w, "w", dev)
+    Rz, N, z_stride = _rows(z, "z", dev)
+    Rw, Nw, w_stride = _rows(w, "w", dev)
     if (Rz, Rw, Nw) != (R, R, N):
         raise ValueError(f"z and w: both [{R}, N], got {tuple(z.shape)} and {tuple(w.shape)}")
     if R * N >= 2 ** 31:
@@ -407,12 +413,7 @@ def mesh_extract(sigma, iso, lo, h, capacity: Optional[int] = None, workspace=No
         raise ValueError("lo and h: three numbers each")
     if capacity is not None and int(capacity) < 0:
         raise ValueError("capacity must be >= 0")
-    need = mesh_workspace_bytes(Gx, Gy, Gz)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
-              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on sigma's device")
+    workspace = _scratch(workspace, mesh_workspace_bytes(Gx, Gy, Gz), dev, "sigma")
     lib = _lib.load()
     counters = torch.empty((2,), dtype=torch.int64, device=dev)
 
@@ -474,12 +475,7 @@ def mesh_components(faces, n_vertices: int, workspace=None):
     if V < 0 or V >= 2 ** 31 or F >= 2 ** 31:
         raise ValueError(f"n_vertices = {V} and F = {F} must lie in [0, 2^31)")
     dev = faces.device
-    need = mesh_components_workspace_bytes(V, F)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
-              and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on faces' device")
+    workspace = _scratch(workspace, mesh_components_workspace_bytes(V, F), dev, "faces")
     labels, triangles, vertices = (torch.empty((V,), dtype=torch.int32, device=dev) for _ in range(3))
     counters = torch.empty((2,), dtype=torch.int64, device=dev)
     check(_lib.load().ns_mesh_components(_ptr(faces), F, V, _ptr(labels), _ptr(triangles), _ptr(vertices), _ptr(counters),
@@ -597,13 +593,7 @@ def map_max(map, state=None, accumulate: bool = False, workspace=None):
     elif not (isinstance(state, Tensor) and state.is_cuda and state.device == map.device and state.dtype == torch.float32
               and tuple(state.shape) == (2,) and state.is_contiguous()):
         raise ValueError("state: a contiguous float32 tensor of shape (2,) on map's device")
-    need = map_max_workspace_bytes(R)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=map.device) if need else None
-    elif not (isinstance(workspace, Tensor) and workspace.is_cuda and workspace.device == map.device
-              and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need
-              and workspace.data_ptr() % 8 == 0):
-        raise ValueError(f"workspace: a contiguous 8-byte-aligned tensor of at least {need} bytes on map's device")
+    workspace = _scratch(workspace, map_max_workspace_bytes(R), map.device, "map")
     check(_lib.load().ns_map_max(_ptr(map) if R else None, stride, R, int(accumulate), _ptr(state),
                                  _ptr(workspace) if R else None, _stream(map.device)), "ns_map_max")
     return state

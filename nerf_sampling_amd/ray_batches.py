@@ -273,6 +273,8 @@ class DeviceRayDataset:
         -> (rgb stride in floats, out, slot, workspace), ``out`` and ``workspace`` allocated where None"""
         import torch
 
+        from . import ops
+
         if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.float32 and tuple(rgb.shape) == (R, 3)):
             raise ValueError(f"rgb: a float32 device tensor of shape ({R}, 3)")
         if rgb.is_contiguous():
@@ -281,20 +283,8 @@ class DeviceRayDataset:
             stride = 4
         else:
             raise ValueError("rgb: contiguous [R,3], or the [:, :3] view of a contiguous [R,4] shard")
-        if out is None:
-            out, slot = torch.empty((1,), dtype=torch.float64, device=self.device), 0
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 1
-                  and out.is_contiguous()):
-            raise ValueError("out: a contiguous 1-d float64 device tensor")
-        slot = int(slot)
-        if not 0 <= slot < out.numel():
-            raise ValueError(f"slot {slot} out of range [0, {out.numel()})")
-        if workspace is None:
-            workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous()
-                  and workspace.numel() * workspace.element_size() >= need and workspace.data_ptr() % 8 == 0):
-            raise ValueError(f"workspace: a contiguous 8-byte-aligned device tensor of at least {need} bytes")
-        return stride, out, slot, workspace
+        dev = self.images.device                                # the dataset's device, with its index
+        return (stride, *ops._sum_slot(out, slot, dev), ops._scratch(workspace, need, dev, "the dataset"))
 
     @staticmethod
     def sqerr_workspace_bytes(n_pixels: int) -> int:

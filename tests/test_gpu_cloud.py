@@ -274,6 +274,33 @@ def test_capacity_is_never_exceeded(R, N):
     assert (twice[1][kept:] == _bits(want[1])[:2]).all() and (twice[2][kept:] == _bits(want[2])[:2]).all()
 
 
+@pytest.mark.parametrize("shares", [2047, 2048, 2049, 4097])
+def test_the_scan_across_its_tiles(shares):
+    """The scan of the per-share counts walks tiles of 2048 entries with a carry and two LDS buffers in turn: one tile short of
+    full, full, one entry into the second, one entry into the third.  About 1 % of the weights pass, and so do the first and the
+    last flat element and the two elements on either side of the first tile boundary (the last of share 2047, the first of
+    share 2048); two appends into one cloud, so that the second scan starts from a counter that is not 0."""
+    N = 64
+    assert S % N == 0
+    R = shares * S // N - (shares != 2048)                                 # the last share is 64 elements short; at 2048, full
+    n = R * N
+    assert (n + S - 1) // S == shares
+    o, d, z, rgb = _rays(R, N, seed=shares)
+    pts = _points(o, d, z)
+    rng = np.random.default_rng(shares + 1)
+    mask = rng.random(n) < 0.01
+    edges = [e for e in (0, 2048 * S - 1, 2048 * S, n - 1) if e < n]
+    mask[edges] = True
+    w = _weights_of(mask.reshape(R, N), rng)
+    w_again = np.ascontiguousarray(w[::-1, ::-1])                          # another pattern, its first and last element kept too
+    want = CR.select_batches([(pts, w, rgb), (pts, w_again, rgb)], 0.5)
+    kept = len(want[1])
+    assert kept == 2 * int(mask.sum()) and 2 * len(edges) < kept < n // 25
+    got = Call(kept + 5).append(o, d, z, w, rgb, 0.5).append(o, d, z, w_again, rgb, 0.5).result()
+    assert got[3] == kept
+    _assert_records(got, want)
+
+
 def test_point_cloud_object():
     """ops.PointCloud / ops.cloud_append: the same records through the tensor interface, the overflow error and truncate"""
     import torch

@@ -188,6 +188,52 @@ def test_capacity_zero_counts_and_a_small_capacity_keeps_the_fence():
         assert (got_keys == keys[:m]).all() and (got_tri == tri[:m].view(np.int32)).all()
 
 
+TILE_LATTICES = {2047: (2048, 33, 33), 2048: (129, 129, 129), 2049: (2050, 33, 33), 4097: (4098, 33, 33)}
+
+
+def _two_balls(dims):
+    """a ball of radius 3.7 cells around lattice point (2, 2, 2) and one around (Gx - 3, Gy - 3, Gz - 3), both cut by the faces
+    of the lattice, so that the first and the last cells hold triangles, and nothing between them; the lattice's last point is
+    NaN: the last cell, and only it, is skipped"""
+    def make():
+        Gx, Gy, Gz = dims
+        z, y, x = np.meshgrid(np.arange(Gz, dtype=np.float32), np.arange(Gy, dtype=np.float32), np.arange(Gx, dtype=np.float32),
+                              indexing="ij", sparse=True)
+        near = np.sqrt((x - 2) ** 2 + (y - 2) ** 2 + (z - 2) ** 2)
+        far = np.sqrt((x - (Gx - 3)) ** 2 + (y - (Gy - 3)) ** 2 + (z - (Gz - 3)) ** 2)
+        sigma = (np.float32(3.7) - np.minimum(near, far)).astype(np.float32)
+        sigma[-1, -1, -1] = np.nan
+        return sigma, 0.0, (-1.0, 0.5, 3.0), (0.25, 0.125, 0.75)
+    return make
+
+
+def _cell_of(keys, dims):
+    """the cell index e of the lattice point a key's edge starts from (that point is a corner of the triangle's cell)"""
+    Gx, Gy, Gz = dims
+    lin = keys // 8
+    i, j, k = lin % Gx, lin // Gx % Gy, lin // (Gx * Gy)
+    return (np.minimum(k, Gz - 2) * (Gy - 1) + np.minimum(j, Gy - 2)) * (Gx - 1) + np.minimum(i, Gx - 2)
+
+
+@pytest.mark.parametrize("shares", sorted(TILE_LATTICES))
+def test_the_scan_across_its_tiles(shares):
+    """The scan of the per-share counts walks tiles of 2048 entries with a carry and two LDS buffers in turn: lattices of exactly
+    2047, 2048, 2049 and 4097 shares, triangles in the first and in the last shares only, and the one skipped cell in the last
+    share, so both totals and every index of the second ball cross every tile boundary there is."""
+    dims = TILE_LATTICES[shares]
+    assert S == 1024 and (dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1) == shares * S
+    sigma, iso, lo, h, tri, keys, skipped = check(f"tiles{dims}", _two_balls(dims))
+    cells = _cell_of(keys, dims)
+    first_ball = int((cells.max(axis=1) < shares * S // 2).sum())
+    assert skipped == 1 and 0 < first_ball < tri.shape[0]
+    assert cells.min() < S and cells.max() >= (shares - 1) * S             # triangles in share 0 and in the last share
+    if shares == 2049:
+        # fewer records than the first ball has triangles: they are right, the rest is counted, nothing is written behind them
+        got_tri, got_keys, n_triangles, n_skipped = run(sigma, iso, lo, h, first_ball - 3)
+        assert (n_triangles, n_skipped) == (tri.shape[0], 1) and got_tri.shape[0] == first_ball - 3
+        assert (got_keys == keys[:first_ball - 3]).all() and (got_tri == tri[:first_ball - 3].view(np.int32)).all()
+
+
 def test_two_runs_are_bit_identical():
     sigma, iso, lo, h, tri, keys, _ = reference("non finite", _non_finite)
     a = run(sigma, iso, lo, h, tri.shape[0])
