@@ -287,6 +287,46 @@ int64_t ns_mesh_components_workspace_bytes(int64_t V, int64_t F);
 int ns_mesh_components(const int64_t* faces_dev, int64_t F, int64_t V, int32_t* label_dev, int32_t* tri_count_dev,
                        int32_t* vert_count_dev, int64_t* count_dev, void* workspace_dev, void* stream);
 
+/* ---- per-vertex normals of the device mesh  (what every NeRF mesh export ships so that a viewer shades the surface, not the
+ * triangulation; not in the reference) ----  The finite-difference gradient of the density lattice, interpolated along the
+ * vertex's own lattice edge: a function of the edge alone, as the position is -- no atomics, no adjacency, no dependence on the
+ * triangulation.  Lattice, sigma_stride and lin are exactly ns_mesh_extract's.
+ * KEY: key_dev[v], v in [0, V), is lin(a) * 8 + code as ns_mesh_extract's key_out holds it: the offset is
+ * d = (code & 1, (code >> 1) & 1, code >> 2) and b = a + d.  Keys need not be sorted or distinct.
+ * NODAL GRADIENT at lattice point q, per axis with index x in [0, G) and spacing h, s[.] the values along that axis through q:
+ *   xm = max(x - 1, 0),  xp = min(x + 1, G - 1),
+ *   g  = (s[xp] - s[xm]) / ((float)(xp - xm) * h)     one fp32 subtraction, one fp32 multiplication (exact: the factor is 1 or
+ *                                                     2) and one correctly rounded fp32 division:
+ * the central difference where both neighbours exist, the one-sided one on the lattice boundary.
+ * GRADIENT AT THE VERTEX on the edge between a and b with values s_a and s_b:
+ *   tt = (iso - s_a) / (s_b - s_a)       the same expression as the vertex's,
+ *   g  = g_a + tt * (g_b - g_a)          per axis, every operation rounded separately.
+ * NORMAL: G = (double) g, len = sqrt(Gx * Gx + Gy * Gy + Gz * Gz) added left to right in fp64, n = (float)(-G / len) per axis,
+ * normal_out[v * 3 ..] -- fp64 so that no density scale overflows the sum of squares and numpy float64 restates the bits (a
+ * correctly rounded fp64 square root and division).  It points outward: inside is sigma >= iso and the density falls towards the
+ * outside, the side ns_mesh_extract's winding faces.
+ * DEGENERATE vertex: s_a, s_b, tt or any component of g is not finite, or len == 0: the normal is (0, 0, 0) and the vertex is
+ * counted in count_dev[0].  A key whose edge does not cross iso is legal: tt lies outside [0, 1] and the formula extrapolates.
+ * INVALID key: negative, lin(a) >= Gx * Gy * Gz, code == 0, or b outside the lattice on any axis: the normal is (0, 0, 0) and
+ * the key is counted in count_dev[1] only, not also as degenerate; no address is ever formed from an invalid key.
+ * Both counters are overwritten, not accumulated.  Nothing is written outside normal_out[0 .. 3 V).
+ * Two launches on `stream`, no atomics of any kind: (1) workgroup g takes the NS_MESH_NORMALS_SHARE keys from
+ * g * NS_MESH_NORMALS_SHARE on (thread t takes g * NS_MESH_NORMALS_SHARE + s * 256 + t), writes their normals and its two int64
+ * partial counts into workspace_dev (ns_mesh_normals_workspace_bytes(V) bytes; what it holds before the call does not matter);
+ * (2) ONE workgroup adds the partials in the order of g and writes count_dev.  V == 0 writes the two zeros and launches nothing
+ * else.  A gather: per vertex s_a, s_b and up to twelve stencil neighbours as 4-byte loads; ascending keys (ops.mesh_weld's
+ * order) make neighbouring threads read neighbouring lattice rows.  Not part of this: normals of meshes that did not come from
+ * a lattice (no keys), the field's analytic gradient, normal maps of rendered frames.
+ * Checked before any launch (NS_E_INVALID): a dimension below 2, Gx * Gy * Gz >= 2^31, a negative stride, a non-finite iso or
+ * h, h <= 0, V < 0 or V >= 2^31, count_dev NULL, with V > 0 any of sigma_dev / key_dev / normal_out / workspace_dev NULL,
+ * key_dev / count_dev / workspace_dev not 8-byte aligned, normal_out not 4-byte aligned.  ns_mesh_normals_workspace_bytes is 0
+ * for a shape that would be refused (and for V == 0, which needs none).                                                       */
+#define NS_MESH_NORMALS_SHARE 1024
+int64_t ns_mesh_normals_workspace_bytes(int64_t V);
+int ns_mesh_normals(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy, int Gz, float iso, float h_x, float h_y,
+                    float h_z, const int64_t* key_dev, int64_t V, float* normal_out, int64_t* count_dev, void* workspace_dev,
+                    void* stream);
+
 /* ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
  * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a
  * quarter of the frame's bytes cross to the host:

@@ -1,4 +1,4 @@
-// Workgroup primitives of the device evaluation kernels (ns_cloud, ns_mesh, ns_mesh_components, the scoring kernels of ns_rays,
+// Workgroup primitives of the device evaluation kernels (ns_cloud, ns_mesh, ns_mesh_components, ns_mesh_normals, the scoring kernels of ns_rays,
 // ns_map_max): device-side helpers only -- no kernel, no host state.  Each is called by ALL kBlock threads of a workgroup of kWaves
 // 64-lane waves and fixes the order of everything it adds: a result is a function of the inputs alone, never of CU count or timing.
 #pragma once

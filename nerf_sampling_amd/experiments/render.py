@@ -94,6 +94,14 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @click.option("--mesh-keep-largest", "mesh_keep_largest", default=0, type=click.IntRange(min=0), show_default=True,
               help="(not in the reference) --device-mesh keeps only this many of its surface's connected components, those with "
                    "the most triangles (among those --mesh-min-triangles leaves).  0: no filter.")
+@click.option("--mesh-normals", "mesh_normals", is_flag=True, default=False,
+              help="(not in the reference) --device-mesh also writes per-vertex normals nx ny nz into scene_mesh.ply "
+                   "(ns_mesh_normals, nerf_utils.scene_mesh_shaded): the density lattice's gradient at each vertex, so that a "
+                   "viewer shades the surface and not its triangles.")
+@click.option("--mesh-colour-view", "mesh_colour_view", default="centre", type=click.Choice(["centre", "normal"]),
+              show_default=True,
+              help="(not in the reference) --device-mesh queries a vertex's colour looking towards the box centre, or with "
+                   "'normal' (it needs --mesh-normals) looking at the surface along its inward normal.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -119,7 +127,8 @@ def main(**kw):
     if kw["device_mesh"]:
         k.update(device_mesh=True, mesh_resolution=kw["mesh_resolution"], mesh_threshold=kw["mesh_threshold"],
                  mesh_bound=kw["mesh_bound"], mesh_min_triangles=kw["mesh_min_triangles"],
-                 mesh_keep_largest=kw["mesh_keep_largest"])
+                 mesh_keep_largest=kw["mesh_keep_largest"], mesh_normals=kw["mesh_normals"],
+                 mesh_colour_view=kw["mesh_colour_view"])
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -1251,7 +1251,14 @@ def field_density_grid(network, lo, hi, resolution, chunk=1 << 20):
 
 def write_mesh_ply(path, vertices, faces, rgb=None) -> None:
     """A binary little-endian PLY triangle mesh from host arrays: per vertex float x y z and, with ``rgb`` (in [0, 1], through
-    to8b), uchar red green blue; per face ``property list uchar int vertex_indices`` -- a count of 3 and three int32."""
+    to8b), uchar red green blue; per face ``property list uchar int vertex_indices`` -- a count of 3 and three int32.
+    write_mesh_ply_normals without normals."""
+    write_mesh_ply_normals(path, vertices, faces, rgb=rgb, normals=None)
+
+
+def write_mesh_ply_normals(path, vertices, faces, rgb=None, normals=None) -> None:
+    """The one PLY writer: write_mesh_ply's file and, with ``normals`` [V,3], ``property float nx / ny / nz`` directly after z,
+    before the colours -- the order MeshLab, Blender and Open3D read."""
     import numpy as np
 
     vertices = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
@@ -1260,6 +1267,11 @@ def write_mesh_ply(path, vertices, faces, rgb=None) -> None:
     if V >= 2 ** 31 or (F and (faces.min() < 0 or faces.max() >= V)):
         raise ValueError(f"faces index {V} vertices with int32")
     fields = [("xyz", "<f4", (3,))]
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        if normals.shape[0] != V:
+            raise ValueError(f"{V} vertices, {normals.shape[0]} normals")
+        fields.append(("n", "<f4", (3,)))
     if rgb is not None:
         colours = run_nerf_helpers.to8b(np.asarray(rgb, dtype=np.float32).reshape(-1, 3))
         if colours.shape[0] != V:
@@ -1267,6 +1279,8 @@ def write_mesh_ply(path, vertices, faces, rgb=None) -> None:
         fields.append(("rgb", "u1", (3,)))
     vertex = np.empty((V,), dtype=fields)
     vertex["xyz"] = vertices
+    if normals is not None:
+        vertex["n"] = normals
     if rgb is not None:
         vertex["rgb"] = colours
     face = np.empty((F,), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
@@ -1274,6 +1288,7 @@ def write_mesh_ply(path, vertices, faces, rgb=None) -> None:
     header = ("ply\nformat binary_little_endian 1.0\n"
               f"element vertex {V}\n"
               "property float x\nproperty float y\nproperty float z\n"
+              + ("property float nx\nproperty float ny\nproperty float nz\n" if normals is not None else "")
               + ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if rgb is not None else "")
               + f"element face {F}\n"
               "property list uchar int vertex_indices\nend_header\n")
@@ -1308,13 +1323,21 @@ def mesh_filter(vertices, faces, rgb=None, min_component_triangles=0, keep_large
     The kept vertices and faces stay in their order, the faces renumbered (ops.mesh_select).  Returns dict(vertices, faces, rgb,
     index int64 [V]: old -> new vertex, -1 where dropped; n_components; n_kept_components; n_dropped_triangles: the faces that
     left, those with an index out of range among them; component_triangles: the face counts of all components in label order,
-    an int32 device tensor).  Not part of this: per-component area or volume, normals, simplification."""
+    an int32 device tensor).  Not part of this: per-component area or volume, normals (they need the lattice: scene_mesh_shaded),
+    simplification."""
+    kept = _mesh_filter(vertices, faces, (rgb,), min_component_triangles, keep_largest)
+    return {("rgb" if k == "extras" else k): (v[0] if k == "extras" else v) for k, v in kept.items()}
+
+
+def _mesh_filter(vertices, faces, extras, min_component_triangles, keep_largest):
+    """mesh_filter with any number of per-vertex tensors (colours, normals; a None stays None) cut as the vertices are: its dict
+    with ``extras`` a tuple in place of rgb"""
     faces = faces.contiguous()
     comp = ops.mesh_components(faces, int(vertices.shape[0]))
     keep = mesh_component_keep(comp["labels"], comp["triangles"], min_component_triangles, keep_largest)
-    got = ops.mesh_select(vertices, faces, comp["labels"], keep, extras=(rgb,))
+    got = ops.mesh_select(vertices, faces, comp["labels"], keep, extras=tuple(extras))
     roots = comp["labels"].long() == torch.arange(vertices.shape[0], device=vertices.device)
-    return dict(vertices=got["vertices"], faces=got["faces"], rgb=got["extras"][0], index=got["index"],
+    return dict(vertices=got["vertices"], faces=got["faces"], extras=got["extras"], index=got["index"],
                 n_components=comp["n_components"], n_kept_components=int(keep.sum()),
                 n_dropped_triangles=int(faces.shape[0] - got["faces"].shape[0]), component_triangles=comp["triangles"][roots])
 
@@ -1345,11 +1368,34 @@ def scene_mesh_filtered(network, bound=1.5, resolution=256, threshold=50.0, colo
     along the unit vector from the vertex towards the box centre: rgb = sigmoid(raw[:, :3]).  ``capacity``: triangles to make
     room for; None counts first (ops.mesh_extract); fewer than the surface has: RuntimeError naming the count.
     Returns dict(vertices [V,3], faces [F,3] int64, rgb [V,3] or None, n_triangles, n_skipped, lo, h[, grid]) with device
-    tensors; lo and h are the lattice's (mesh_lattice).  ``savedir`` gets scene_mesh.ply (write_mesh_ply).  Not part of this:
-    simplification, normals, per-component area or volume, and lattices of 2^31 points or more."""
+    tensors; lo and h are the lattice's (mesh_lattice).  ``savedir`` gets scene_mesh.ply (write_mesh_ply).  Per-vertex normals
+    are scene_mesh_shaded's, of which this is the call without them: the same launches, the same dict, the same file.  Not part
+    of this: simplification, per-component area or volume, and lattices of 2^31 points or more."""
+    return scene_mesh_shaded(network, bound=bound, resolution=resolution, threshold=threshold, colours=colours, savedir=savedir,
+                             capacity=capacity, return_grid=return_grid, min_component_triangles=min_component_triangles,
+                             keep_largest=keep_largest, normals=False, colour_view="centre")
+
+
+def scene_mesh_shaded(network, bound=1.5, resolution=256, threshold=50.0, colours=True, savedir=None, capacity=None,
+                      return_grid=False, min_component_triangles=0, keep_largest=0, normals=True, colour_view="centre"):
+    """scene_mesh_filtered with per-vertex normals, so that a viewer shades the surface and not the Kuhn split's slivers.
+    ``normals``: ops.mesh_normals on the density lattice the mesh was cut from -- the lattice's finite-difference gradient at
+    each vertex's own lattice edge, pointing outward; a function of the edge alone, not of the triangles around the vertex.  It
+    runs before the filter and the normals are cut as the vertices are.  The dict gains normals [V,3] and n_degenerate_normals
+    (vertices of the unfiltered surface whose gradient is zero or not finite: their normal is (0, 0, 0)), and scene_mesh.ply
+    carries nx ny nz (write_mesh_ply_normals).  ``colour_view``: "centre" is scene_mesh_filtered's colour query, unchanged;
+    "normal" (it needs ``normals``) looks at the surface along its inward normal -n -- on a concave part of an object the
+    direction to the box centre is arbitrary --, and along the centre direction exactly where the normal is (0, 0, 0).  With
+    ``normals=False`` and "centre" this is scene_mesh_filtered to the launch and to the byte.  Not part of this: normals of
+    meshes that did not come from a lattice (no keys), the field's analytic gradient, normal maps of rendered frames,
+    simplification."""
     lo3, h3, _G = mesh_lattice(-float(bound), float(bound), resolution)
     if int(min_component_triangles) < 0 or int(keep_largest) < 0:
         raise ValueError("min_component_triangles and keep_largest must be >= 0")
+    if colour_view not in ("centre", "normal"):
+        raise ValueError(f"colour_view: 'centre' or 'normal', got {colour_view!r}")
+    if colour_view == "normal" and not normals:
+        raise ValueError("colour_view='normal' needs normals=True")
     with torch.no_grad():
         grid = field_density_grid(network, -float(bound), float(bound), resolution)
         got = ops.mesh_extract(grid, float(threshold), lo3, h3, capacity=capacity)
@@ -1357,26 +1403,37 @@ def scene_mesh_filtered(network, bound=1.5, resolution=256, threshold=50.0, colo
             raise RuntimeError(f"scene_mesh: the surface has {got['n_triangles']} triangles but there is room for "
                                f"{got['triangles'].shape[0]}: pass capacity={got['n_triangles']}")
         vertices, faces = ops.mesh_weld(got["triangles"], got["keys"])
+        vertex_normals = n_degenerate = None
+        if normals:
+            # torch.unique(keys) is the keys in ascending order: ops.mesh_weld's vertex order, so row v is vertex v's normal
+            shaded = ops.mesh_normals(grid, float(threshold), h3, torch.unique(got["keys"]))
+            vertex_normals, n_degenerate = shaded["normals"], shaded["n_degenerate"]
         kept = None
         if int(min_component_triangles) != 0 or int(keep_largest) != 0:
-            kept = mesh_filter(vertices, faces, None, min_component_triangles, keep_largest)
-            vertices, faces = kept["vertices"], kept["faces"]
+            kept = _mesh_filter(vertices, faces, (vertex_normals,), min_component_triangles, keep_largest)
+            vertices, faces, vertex_normals = kept["vertices"], kept["faces"], kept["extras"][0]
         rgb = None
         if colours:
             rgb = torch.empty((vertices.shape[0], 3), dtype=torch.float32, device=vertices.device)
             if vertices.shape[0] > 0:
                 towards = -vertices                                            # the box centre is the origin
                 towards = towards / towards.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+                if colour_view == "normal":                                    # along -n; the centre direction where n is zero
+                    flat = (vertex_normals == 0).all(dim=-1, keepdim=True)
+                    towards = torch.where(flat, towards, -vertex_normals)
                 rgb = torch.sigmoid(ops.nerf_forward(network.packed(), vertices[:, None, :], towards)[:, 0, :3])
     out = dict(vertices=vertices, faces=faces, rgb=rgb, n_triangles=got["n_triangles"], n_skipped=got["n_skipped"], lo=lo3, h=h3)
+    if normals:
+        out.update(normals=vertex_normals, n_degenerate_normals=n_degenerate)
     if kept is not None:
         out.update({k: kept[k] for k in ("n_components", "n_kept_components", "n_dropped_triangles", "component_triangles")})
     if return_grid:
         out["grid"] = grid
     if savedir is not None:
         os.makedirs(savedir, exist_ok=True)
-        write_mesh_ply(os.path.join(savedir, "scene_mesh.ply"), vertices.cpu().numpy(), faces.cpu().numpy(),
-                       None if rgb is None else rgb.cpu().numpy())
+        write_mesh_ply_normals(os.path.join(savedir, "scene_mesh.ply"), vertices.cpu().numpy(), faces.cpu().numpy(),
+                               None if rgb is None else rgb.cpu().numpy(),
+                               None if vertex_normals is None else vertex_normals.cpu().numpy())
     return out
 
 

@@ -485,6 +485,46 @@ def mesh_components(faces, n_vertices: int, workspace=None):
             "n_ignored": n_ignored}
 
 
+def mesh_normals_workspace_bytes(n_vertices: int) -> int:
+    """ns_mesh_normals_workspace_bytes: the per-share counts ``mesh_normals`` needs for that many keys (0: a count it refuses, or
+    none)"""
+    return int(_lib.load().ns_mesh_normals_workspace_bytes(int(n_vertices)))
+
+
+def mesh_normals(sigma, iso, h, keys, workspace=None):
+    """ns_mesh_normals: unit normals of mesh vertices from the density lattice they were cut from, on the device -- the
+    finite-difference gradient of ``sigma`` (central, one-sided on the lattice boundary) interpolated along each vertex's own
+    lattice edge, negated (it points outward, from sigma >= iso to below) and normalised in fp64; a function of the edge alone.
+    ``sigma``: what ``mesh_extract`` takes, and ``h`` its three spacings.  ``keys``: int64 on sigma's device, any shape -- [V],
+    such as ``torch.unique`` of ``mesh_extract``'s keys (``mesh_weld``'s vertex order), or its [n,3] as they are; they need not
+    be sorted or distinct.  ``workspace``: a contiguous 8-byte-aligned device tensor of at least
+    ``mesh_normals_workspace_bytes(keys.numel())`` bytes (None: allocated).  Returns dict(normals fp32 keys.shape + (3,),
+    n_degenerate: vertices whose gradient is zero or not finite, normal (0, 0, 0); n_invalid: keys that name no lattice edge,
+    normal (0, 0, 0)) after ONE readback of the two counters.  What is wrong with the arguments raises ValueError before any
+    launch."""
+    Gx, Gy, Gz, stride = _mesh_lattice(sigma)
+    dev = sigma.device
+    if not (isinstance(keys, Tensor) and keys.dtype == torch.int64 and keys.device == dev):
+        raise ValueError("keys: an int64 tensor on sigma's device")
+    h3 = [float(np.float32(v)) for v in h]
+    if len(h3) != 3 or not all(np.isfinite(v) and v > 0.0 for v in h3):
+        raise ValueError("h: three finite positive numbers")
+    iso = float(np.float32(iso))
+    if not np.isfinite(iso):
+        raise ValueError("iso must be finite")
+    flat = keys.reshape(-1).contiguous()
+    V = int(flat.shape[0])
+    if V >= 2 ** 31:
+        raise ValueError(f"{V} keys are not below 2^31")
+    workspace = _scratch(workspace, mesh_normals_workspace_bytes(V), dev, "sigma")
+    normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    counters = torch.empty((2,), dtype=torch.int64, device=dev)
+    check(_lib.load().ns_mesh_normals(_ptr(sigma), stride, Gx, Gy, Gz, iso, *h3, _ptr(flat), V, _ptr(normals), _ptr(counters),
+                                      _ptr(workspace), _stream(dev)), "ns_mesh_normals")
+    n_degenerate, n_invalid = (int(v) for v in counters.cpu())                 # the one readback
+    return {"normals": normals.reshape(tuple(keys.shape) + (3,)), "n_degenerate": n_degenerate, "n_invalid": n_invalid}
+
+
 def mesh_select(vertices, faces, labels, keep, extras=()):
     """The part of a mesh whose components are kept -- plain torch on whatever device the tensors live on, no kernel of this
     library.  ``vertices`` [V,...], ``faces`` int64 [F,3], ``labels`` [V] as ``mesh_components`` returns them, ``keep`` bool [V],

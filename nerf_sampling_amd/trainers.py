@@ -48,7 +48,7 @@ class Trainer:
                  cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False,
                  device_video: bool = False, device_mesh: bool = False, mesh_resolution: int = 256,
                  mesh_threshold: float = 50.0, mesh_bound: float = 1.5, mesh_min_triangles: int = 0,
-                 mesh_keep_largest: int = 0):
+                 mesh_keep_largest: int = 0, mesh_normals: bool = False, mesh_colour_view: str = "centre"):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -123,6 +123,17 @@ class Trainer:
             if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
                 raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
             setattr(self, name, int(value))
+        # mesh_normals (default off): scene_mesh.ply also carries per-vertex normals (nerf_utils.scene_mesh_shaded,
+        # ns_mesh_normals: the density lattice's gradient at each vertex's lattice edge), so that a viewer shades the surface and
+        # not its slivers.  mesh_colour_view: "centre" queries a vertex's colour looking towards the box centre, as ever;
+        # "normal" (it needs mesh_normals) looking at the surface along its inward normal.
+        if not isinstance(mesh_normals, (bool, np.bool_)):
+            raise ValueError(f"mesh_normals must be a bool, got {mesh_normals!r}")
+        self.mesh_normals = bool(mesh_normals)
+        if mesh_colour_view not in ("centre", "normal"):
+            raise ValueError(f"mesh_colour_view: 'centre' or 'normal', got {mesh_colour_view!r}")
+        if mesh_colour_view == "normal" and not self.mesh_normals:
+            raise ValueError("mesh_colour_view='normal' looks along the vertex normals: it needs mesh_normals=True")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -223,8 +234,8 @@ class Trainer:
         """renderonly_{test|path}_{step:06d}/ with NNN.png, psnr.txt[, scene_data.pt] -- Trainer.py:181-230
         (no mp4; under device_video without render_test: rgb/NNN.png and disp/NNN.png through nerf_utils.write_video).  Under
         device_cloud also scene_cloud.pt and scene_cloud.ply of the same poses (nerf_utils.scene_cloud); under device_mesh also
-        scene_mesh.ply, the isosurface of the field's density (nerf_utils.scene_mesh_filtered), without its small components where
-        mesh_min_triangles or mesh_keep_largest is set."""
+        scene_mesh.ply, the isosurface of the field's density (nerf_utils.scene_mesh_shaded), without its small components where
+        mesh_min_triangles or mesh_keep_largest is set and with per-vertex normals under mesh_normals."""
         with torch.no_grad():
             images = images[i_test] if render_test else None
             testsavedir = os.path.join(self.basedir, self.expname, "renderonly_{}_{:06d}".format(
@@ -241,15 +252,18 @@ class Trainer:
                       f", {cloud['pts'].shape[0]} written to {testsavedir}")
             if self.device_mesh:
                 fine = render_kwargs_test.get("network_fine")
-                mesh = nerf_utils.scene_mesh_filtered(fine if fine is not None else render_kwargs_test["network_fn"],
-                                                      bound=self.mesh_bound, resolution=self.mesh_resolution,
-                                                      threshold=self.mesh_threshold, savedir=testsavedir,
-                                                      min_component_triangles=self.mesh_min_triangles,
-                                                      keep_largest=self.mesh_keep_largest)
+                mesh = nerf_utils.scene_mesh_shaded(fine if fine is not None else render_kwargs_test["network_fn"],
+                                                    bound=self.mesh_bound, resolution=self.mesh_resolution,
+                                                    threshold=self.mesh_threshold, savedir=testsavedir,
+                                                    min_component_triangles=self.mesh_min_triangles,
+                                                    keep_largest=self.mesh_keep_largest, normals=self.mesh_normals,
+                                                    colour_view=self.mesh_colour_view)
                 filtered = ""
                 if "n_components" in mesh:
                     filtered = (f"; {mesh['n_kept_components']} of {mesh['n_components']} components kept, "
                                 f"{mesh['n_dropped_triangles']} triangles dropped")
+                if "normals" in mesh:
+                    filtered += f"; normals, {mesh['n_degenerate_normals']} degenerate"
                 print(f"scene mesh: {mesh['faces'].shape[0]} triangles on {mesh['vertices'].shape[0]} vertices at density "
                       f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped{filtered}), written to {testsavedir}")
             if self.device_eval and render_test and self.render_factor == 0:
