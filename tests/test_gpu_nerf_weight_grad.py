@@ -3,7 +3,11 @@ against torch-CPU autograd of the oracle.
 
 Gate of every gradient tensor: relative L2 < 2e-3, the figure test_depthnet_training_gradients_match_oracle_autograd uses for
 the same comparison (fp32 GEMMs in another summation order; a ReLU whose pre-activation is within rounding of zero may flip).
-Each test prints its worst tensor's figure before it asserts."""
+Each test prints its worst tensor's figure before it asserts.
+
+The chain itself -- which columns, which mask, which operands each GEMM receives -- is pinned bit for bit by
+tests/test_gpu_exact_field_backward.py on exactly representable networks; the gate here stays for real scenes, whose ReLUs sit
+near zero."""
 
 import os
 
