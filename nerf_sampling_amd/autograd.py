@@ -811,6 +811,18 @@ class HipAdam(torch.optim.Adam):
 
 
 # ---- the one-kernel renderer, differentiable in the DepthNet's depth (ns_render_rays_fused_tangent) ------------------------
+def tangent_d_mean(J: dict, g_rgb, g_disp, g_depth, g_acc) -> Tensor:
+    """d mean [R] = sum_k g_k J_k per ray, from the tangent kernel's Jacobian J = dict(rgb [R,3], disp, depth, acc [R]) and the
+    upstream gradients of those maps (None: no gradient): the backward of DepthNetTangentRender down to the DepthNet's depth."""
+    d_mean = torch.zeros_like(J["disp"])
+    if g_rgb is not None:
+        d_mean += (g_rgb * J["rgb"]).sum(-1)
+    for g, k in ((g_disp, "disp"), (g_depth, "depth"), (g_acc, "acc")):
+        if g is not None:
+            d_mean += g.reshape(-1) * J[k]
+    return d_mean
+
+
 class DepthNetTangentRender(torch.autograd.Function):
     """rgb, disp, depth, acc of rays through DepthNet -> uniform placement -> a frozen f16x3 (or f16) field -> compositing, rendered in
     chunks by the tangent kernel; differentiable in the DepthNet's parameters.  The kernel returns each ray's Jacobian
@@ -840,13 +852,7 @@ class DepthNetTangentRender(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_depth, g_acc):
         o, d, *params = ctx.saved_tensors
-        J = ctx.jac
-        d_mean = torch.zeros((o.shape[0],), dtype=torch.float32, device=o.device)
-        if g_rgb is not None:
-            d_mean += (g_rgb * J["rgb"]).sum(-1)
-        for g, k in ((g_disp, "disp"), (g_depth, "depth"), (g_acc, "acc")):
-            if g is not None:
-                d_mean += g.reshape(-1) * J[k]
+        d_mean = tangent_d_mean(ctx.jac, g_rgb, g_disp, g_depth, g_acc)
         net, chunk = ctx.cfg["depth_net"], ctx.cfg["chunk"]
         grads = [torch.zeros_like(p) for p in params]
         for s in range(0, o.shape[0], chunk):

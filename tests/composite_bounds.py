@@ -154,35 +154,28 @@ def _model(raw, z, d, noise, white, ref):
     return dict(rgb=e_rgb, acc=e_acc, depth=e_depth, alphas=e_alpha, weights=e_w)
 
 
-def check(got, raw, z, d, noise, white, ref=None):
-    """got: the six outputs (float32, any device).  Raises AssertionError naming the first output out of its bound; returns
-    {output: (max |err| / bound, max |err|)} over the finite entries."""
-    if ref is None:
-        ref = reference(raw, z, d, noise, white)
-    b = _model(raw, z, d, noise, white, ref)
-    got = dict(zip(OUTPUTS, (x.detach().cpu().double() if x is not None else None for x in got)))
-    R, N = z.shape
-    stats = {}
-    for name in ("alphas", "weights", "acc", "depth", "rgb"):
-        g, x = got[name], ref[name]
-        assert g.shape == x.shape, (name, tuple(g.shape), tuple(x.shape))
-        assert torch.equal(torch.isnan(g), torch.isnan(x)), (name, "NaN pattern", int((torch.isnan(g) ^ torch.isnan(x)).sum()))
-        fin = torch.isfinite(x)
-        assert torch.equal(torch.isinf(g), torch.isinf(x)) and bool((g[torch.isinf(x)] == x[torch.isinf(x)]).all()), (name, "inf")
-        err = (g[fin] - x[fin]).abs()
-        ratio = err / (b[name][fin] + TINY) if err.numel() else err
-        worst = float(ratio.max()) if ratio.numel() else 0.0
-        stats[name] = (worst, float(err.max()) if err.numel() else 0.0)
-        if worst > 1.0:
-            j = int(ratio.argmax())
-            raise AssertionError(f"{name}: |err| {float(err[j]):.3e} > bound {float(b[name][fin][j]):.3e} "
-                                 f"(got {float(g[fin][j])!r}, ref {float(x[fin][j])!r}; N={N}, white={white}, "
-                                 f"noise={noise is not None}; worst ratio {worst:.2f})")
-    # disp: 1 / disp against max(1e-10, depth / (acc + 1e-10)); transparent rays exactly the clamp
-    g, x = got["disp"], ref["disp"]
+def _check_one(name, g, x, bound, tag):
+    """One output against its reference and per-element bound: (max |err| / bound, max |err|) over the finite entries"""
+    assert g.shape == x.shape, (name, tuple(g.shape), tuple(x.shape))
+    assert torch.equal(torch.isnan(g), torch.isnan(x)), (name, "NaN pattern", int((torch.isnan(g) ^ torch.isnan(x)).sum()))
+    fin = torch.isfinite(x)
+    assert torch.equal(torch.isinf(g), torch.isinf(x)) and bool((g[torch.isinf(x)] == x[torch.isinf(x)]).all()), (name, "inf")
+    err = (g[fin] - x[fin]).abs()
+    ratio = err / (bound[fin] + TINY) if err.numel() else err
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if worst > 1.0:
+        j = int(ratio.argmax())
+        raise AssertionError(f"{name}: |err| {float(err[j]):.3e} > bound {float(bound[fin][j]):.3e} "
+                             f"(got {float(g[fin][j])!r}, ref {float(x[fin][j])!r}; {tag}; worst ratio {worst:.2f})")
+    return worst, float(err.max()) if err.numel() else 0.0
+
+
+def _check_disp(g, ref, b, N, white):
+    """disp: 1 / disp against max(1e-10, depth / (acc + 1e-10)); transparent rays exactly the clamp"""
+    x = ref["disp"]
     assert torch.equal(torch.isnan(g), torch.isnan(x)), ("disp", "NaN pattern")
     fin = torch.isfinite(x)
-    acc, depth = ref["acc"], ref["depth"]
+    acc = ref["acc"]
     q = 1.0 / x
     if N == 1:
         e_q = torch.zeros_like(q)
@@ -196,8 +189,31 @@ def check(got, raw, z, d, noise, white, ref=None):
     err = (1.0 / g[sel] - q[sel]).abs()
     ratio = err / (e_q[sel] + 4 * U * q[sel])  # (+ the fp32 rounding of disp itself, 2u relative through the reciprocal)
     worst = float(ratio.max()) if ratio.numel() else 0.0
-    stats["disp"] = (worst, float(err.max()) if err.numel() else 0.0)
     if worst > 1.0:
         j = int(ratio.argmax())
         raise AssertionError(f"disp: |1/disp err| {float(err[j]):.3e} over its bound (N={N}, white={white}; ratio {worst:.2f})")
+    return worst, float(err.max()) if err.numel() else 0.0
+
+
+def _check(names, got, raw, z, d, noise, white, ref):
+    if ref is None:
+        ref = reference(raw, z, d, noise, white)
+    b = _model(raw, z, d, noise, white, ref)
+    N = z.shape[1]
+    tag = f"N={N}, white={white}, noise={noise is not None}"
+    stats = {name: _check_one(name, got[name], ref[name], b[name], tag) for name in names}
+    stats["disp"] = _check_disp(got["disp"], ref, b, N, white)
     return stats
+
+
+def check(got, raw, z, d, noise, white, ref=None):
+    """got: the six outputs (float32, any device).  Raises AssertionError naming the first output out of its bound; returns
+    {output: (max |err| / bound, max |err|)} over the finite entries."""
+    got = dict(zip(OUTPUTS, (x.detach().cpu().double() if x is not None else None for x in got)))
+    return _check(("alphas", "weights", "acc", "depth", "rgb"), got, raw, z, d, noise, white, ref)
+
+
+def check_maps(got, raw, z, d, noise, white, ref=None):
+    """The same for a renderer that returns the per-ray maps only: got = dict(rgb [R, 3], disp, acc, depth [R])."""
+    got = {k: got[k].detach().cpu().double() for k in ("rgb", "disp", "acc", "depth")}
+    return _check(("acc", "depth", "rgb"), got, raw, z, d, noise, white, ref)
