@@ -61,13 +61,20 @@ int ns_device_cu_count(void);
  *                            of in the MLP kernels' epilogues;
  *   "no_colour_skip" 0/1  -- 1: launches the render kernel would take (a 16-bit production field composited in the kernel,
  *                            N a power of two <= 64, no raw / max-weight / guard outputs; five tiles) run the production kernel;
- *   "count_colour_skips" 0/1 -- 1: every render-kernel launch counts the waves that skipped their colour statements.
- * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES), read once at first use.              */
+ *   "count_colour_skips" 0/1 -- 1: every render-kernel launch counts the waves that skipped their colour statements and the
+ *                            chunk steps whose MFMAs the K-block-skipping kernel jumped over;
+ *   "kblock_skip" 0/1     -- 1: launches the render kernel takes run its K-block-skipping twin instead (same results bit for
+ *                            bit; off by default: it measured no faster than the render kernel).
+ * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES, NS_KBLOCK_SKIP), read once at first use. */
 int ns_debug_set(const char* name, int value);
 /* Waves that skipped the colour layers in the LAST bf16 / f16 radiance-field launch on the current device that ran with
  * "count_colour_skips" set: 0 when that launch ran another kernel than the render kernel, and before any such launch.
  * Waits for the device.                                                                                            */
 int ns_colour_skip_count(int64_t* waves_out);
+/* Chunk steps (five MFMAs each) whose input K-block was all zero bits and whose MFMAs were jumped over, summed over the waves of
+ * the LAST such launch with "count_colour_skips" set: 0 when it did not run the K-block-skipping render kernel.  Waits for the
+ * device.                                                                                                          */
+int ns_kblock_skip_count(int64_t* steps_out);
 
 /* ---- a1  get_rays + prepare_rays  (run_nerf_helpers.py:187-202, nerf_utils.py:156-188) ----
  * Pixel rows [row0,row1) of an HxW pinhole camera, row-major.  c2w is 12 HOST floats (3x4,

@@ -112,6 +112,7 @@ SIGNATURES = {
     "ns_device_cu_count": (_i, []),
     "ns_debug_set": (_i, [C.c_char_p, _i]),
     "ns_colour_skip_count": (_i, [C.POINTER(_i64)]),
+    "ns_kblock_skip_count": (_i, [C.POINTER(_i64)]),
     "ns_get_rays": (_i, [_i, _i, _f, _f, _f, _f, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "ns_ray_batch_gather": (_i, [C.POINTER(RayDataset), _p, _i, _p, _i64, _p, _p, _p, _p, _p]),
     "ns_ray_batch_draw": (_i, [C.POINTER(RayDataset), _p, _i, _i, _p, C.POINTER(RayDrawParams), C.c_uint64, _i64, _p, _p,

@@ -39,11 +39,13 @@ struct DebugFlags {
   int prod_tiles;        // 4 / 5: tiles per wave of the 16-bit production kernel; 0 = chosen per launch
   int hier_chain;        // 1: ns_render_rays_hierarchical keeps raw [R,N,4] in HBM and composites with the stand-alone kernel
   int no_colour_skip;    // 1: launches the render kernel would take (ns_nerf_mlp_ob16.hip) run the production kernel instead
-  int count_colour_skips;   // 1: the render kernel counts the waves that skipped their colour statements (ns_colour_skip_count)
+  int count_colour_skips;   // 1: the render kernels count the waves that skipped their colour statements (ns_colour_skip_count)
+                            // and the chunk steps the K-block-skipping kernel jumped over (ns_kblock_skip_count)
+  int kblock_skip;       // 1: launches of the render kernel run its K-block-skipping twin (off by default: measured no faster)
 };
 DebugFlags& debug_flags();
-// The render kernel's skip counter for a 16-bit field launch on `stream`: *counter = NULL unless count_colour_skips is set; then
-// the current device's counter, zeroed on `stream` ahead of the launch (ns_colour_skip_count reads the last launch's value).
+// The render kernels' skip counters for a 16-bit field launch on `stream`: *counter = NULL unless count_colour_skips is set; then
+// the current device's two counters (colour-skipping waves, skipped K-block steps), zeroed on `stream` ahead of the launch (ns_colour_skip_count reads the last launch's value).
 int colour_skip_counter(uint32_t** counter, hipStream_t stream);
 // Per-thread launch hint of the one-call renderers (ns_render.cpp): 4 = this call's per-sample outputs are about to be
 // copied to the host while the NEXT call's MLP kernel runs -- the four-tile production kernel leaves 64+ registers of every

@@ -74,12 +74,15 @@ DebugFlags& debug_flags() {
     d.generic_kernels = (v && v[0] == '1') ? 1 : 0;
     v = std::getenv("NS_OB16_TILES");
     d.prod_tiles = (v && (v[0] == '4' || v[0] == '5')) ? v[0] - '0' : 0;
+    v = std::getenv("NS_KBLOCK_SKIP");
+    d.kblock_skip = (v && v[0] == '1') ? 1 : 0;
     return d;
   }();
   return f;
 }
 
-// The render kernel's skip counter: a diagnostic (ns_debug_set("count_colour_skips", 1)), one uint32 per device.  Allocated with
+// The render kernels' skip counters: a diagnostic (ns_debug_set("count_colour_skips", 1)), two uint32 per device -- [0] the waves that
+// skipped their colour statements, [1] the chunk steps whose MFMAs the K-block-skipping kernel jumped over, summed over waves.  Allocated with
 // hipMalloc by the first counted launch on a device and kept for the life of the process (four bytes, never freed); neither
 // the allocation nor the host read-back in ns_colour_skip_count belongs in a stream capture -- do not set the switch while capturing.
 static std::map<int, uint32_t*> g_skip_counters;
@@ -91,7 +94,7 @@ static uint32_t* skip_counter_of_device(bool create) {
   if (it != g_skip_counters.end()) return it->second;
   if (!create) return nullptr;
   uint32_t* p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), sizeof(uint32_t)) != hipSuccess) return nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&p), 2 * sizeof(uint32_t)) != hipSuccess) return nullptr;
   g_skip_counters[dev] = p;
   return p;
 }
@@ -100,7 +103,7 @@ int colour_skip_counter(uint32_t** counter, hipStream_t stream) {
   if (!debug_flags().count_colour_skips) return NS_OK;
   uint32_t* p = skip_counter_of_device(true);
   if (!p) { set_error("colour_skip_counter: no device memory for the counter"); return NS_E_HIP; }
-  NS_HIP(hipMemsetAsync(p, 0, sizeof(uint32_t), stream));
+  NS_HIP(hipMemsetAsync(p, 0, 2 * sizeof(uint32_t), stream));
   *counter = p;
   return NS_OK;
 }
@@ -120,22 +123,25 @@ int ns_debug_set(const char* name, int value) {
   if (!std::strcmp(name, "generic_kernels")) { f.generic_kernels = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "hier_chain")) { f.hier_chain = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "no_colour_skip")) { f.no_colour_skip = value ? 1 : 0; return NS_OK; }
+  if (!std::strcmp(name, "kblock_skip")) { f.kblock_skip = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "count_colour_skips")) { f.count_colour_skips = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "prod_tiles") && (value == 0 || value == 4 || value == 5)) { f.prod_tiles = value; return NS_OK; }
   ns::set_error("ns_debug_set: unknown switch or value (%s = %d)", name, value);
   return NS_E_INVALID;
 }
-int ns_colour_skip_count(int64_t* waves_out) {
-  NS_REQUIRE(waves_out, "null pointer");
-  *waves_out = 0;
+static int read_skip_counter(int which, int64_t* out) {
+  NS_REQUIRE(out, "null pointer");
+  *out = 0;
   uint32_t* p = ns::skip_counter_of_device(false);
   if (!p) return NS_OK;   // no counted launch on this device yet
   uint32_t v = 0;
   NS_HIP(hipDeviceSynchronize());
-  NS_HIP(hipMemcpy(&v, p, sizeof(v), hipMemcpyDeviceToHost));
-  *waves_out = v;
+  NS_HIP(hipMemcpy(&v, p + which, sizeof(v), hipMemcpyDeviceToHost));
+  *out = v;
   return NS_OK;
 }
+int ns_colour_skip_count(int64_t* waves_out) { return read_skip_counter(0, waves_out); }
+int ns_kblock_skip_count(int64_t* steps_out) { return read_skip_counter(1, steps_out); }
 int ns_version(void) { return 1; }
 int ns_device_cu_count(void) { return ns::cu_count(); }
 }

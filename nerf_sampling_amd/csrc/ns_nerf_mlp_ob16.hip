@@ -10,9 +10,10 @@
 #include "ns_mlp_engine.h"
 #include "ns_weights.h"
 
-// This file is compiled three times: as itself; with -DNS_OB16_TU_T5 as a second translation unit that holds only the
-// five-tile production kernels; and with -DNS_OB16_TU_RENDER as a third that holds only the five-tile RENDER kernels,
-// nerf_render_ob16_kernel (the units build in parallel; each is minutes of register allocation).
+// This file is compiled four times: as itself; with -DNS_OB16_TU_T5 as a second translation unit that holds only the
+// five-tile production kernels; with -DNS_OB16_TU_RENDER as a third that holds only the five-tile RENDER kernels,
+// nerf_render_ob16_kernel; and with -DNS_OB16_TU_RENDER -DNS_OB16_TU_KBSKIP as a fourth that holds only the K-BLOCK-SKIPPING
+// render kernels, nerf_kbskip_ob16_kernel (the units build in parallel; each is minutes of register allocation).
 //
 // The render kernel is the five-tile production kernel on the sigma-first weight stream (ns_weights::stream2_dev: same chunks,
 // the tail re-ordered to sigma sub-block | eight colour sub-blocks | rgb head), for launches that composite in the kernel and
@@ -31,18 +32,45 @@
 // activations alone overflow to inf gives NaN rgb on the production kernel (inf * 0 in the rgb head) and 0 here, for samples of
 // zero weight.  It cannot be seen without computing the colour layers; ns_debug_set("no_colour_skip", 1) is the way out.  Outputs that read raw rgb without the weight (raw itself, the
 // max-weight sample, the guards' records) keep a launch on the production kernel.
+//
+// The K-block-skipping render kernel (NS_OB16_TU_KBSKIP) is the render kernel with trunk layers 3..7, sigma and colour from
+// ns_ob16_kbskip_asm.inc (tools/gen_ob16_asm.py --kbskip).  Layers 3..7 also return a live mask of their tested output K-blocks
+// (32 hidden units x the wave's 80 samples; a bit is 0 iff every packed 16-bit activation of the block is the bit pattern 0x0000),
+// and the statement that consumes the block branches around the five MFMAs of each chunk step that would multiply it.
+// Why the results are bit-identical to the render kernel's on the same handle.  (1) Samples are the columns of every MFMA: a dead
+// K-block is dead for all 80 columns of the wave, so no sample's sum loses a term that another wave's decision made.  (2) The
+// products of a skipped step are w * (+0) with w finite (ns_pack.hip refuses the kernel to a handle with an inf / NaN weight:
+// ns_weights::kbskip_ok), so every one of them is +0 or -0 and so is their sum; acc + (+-0) == acc bit for bit unless acc is
+// a zero of the other sign.  (3) That last case cannot reach an output: every skipped sum feeds either a hidden layer's packed
+// ReLU -- v_cvt_pk turns +-0 into 0x0000 / 0x8000 and v_pk_max_i16(x, 0) turns both into 0x0000 -- or sigma, which this kernel's
+// launches only use as `sigma <= 0` (the colour skip; true for both zeros) and as relu(sigma) * dist -> exp(-(+-0)) = 1,
+// alpha = +0: no eligible launch hands raw out (render_eligible).  (4) A sub-block's first step is never skipped, so the bias
+// always enters; a NaN or an inf ACTIVATION has non-zero bits and keeps its K-block live, and so would a -0 (0x8000) had the
+// ReLU let one through.  (5) The test is on the bits the MFMAs would read, after the ReLU, not on values recomputed elsewhere.
+// The matrix cores are taken to add a sum of zeros to a subnormal accumulator without flushing it, as they do on gfx942 / gfx950.
+// OFF by default: ns_debug_set("kblock_skip", 1) (or NS_KBLOCK_SKIP=1) sends the render kernel's launches here.  On the bench frame
+// the kernel skips 12.8 % of its chunk steps and is no faster than the render kernel on the same handle: a skipped step still
+// issues its seven gap instructions, and the mask ORs, tests and branches cost what the skipped MFMAs save.
 namespace nsob16 {
 // the field inputs, and what in-kernel placement and compositing takes (ns_comp_epilogue.h)
 struct Nerf16Args : nsmlp::FieldArgs, nsepi::CompFields {
-  uint32_t* skip_count;   // render kernel only: NULL, or a device counter bumped once per wave that skipped its colour statements
+  uint32_t* skip_count;   // render kernels only: NULL, or two device counters: [0] bumped once per wave that skipped its colour
+                          // statements, [1] (K-block-skipping kernel) by the chunk steps whose MFMAs a wave jumped over
 };
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
 // the five-tile render kernel on the sigma-first stream (a.stream / a.bias name it): defined in the NS_OB16_TU_RENDER unit
 int launch_render_t5(int dtype, Nerf16Args& a, hipStream_t stream);
+// the K-block-skipping render kernel (same stream, same launches): defined in the NS_OB16_TU_KBSKIP unit
+int launch_kbskip_t5(int dtype, Nerf16Args& a, hipStream_t stream);
 }  // namespace nsob16
 
-#ifdef NS_OB16_TU_RENDER
+#if defined(NS_OB16_TU_KBSKIP) && !defined(NS_OB16_TU_RENDER)
+#error "the K-block-skipping unit is a render unit: -DNS_OB16_TU_RENDER -DNS_OB16_TU_KBSKIP"
+#endif
+#ifdef NS_OB16_TU_KBSKIP
+#define NS_OB16_KERNEL nerf_kbskip_ob16_kernel
+#elif defined(NS_OB16_TU_RENDER)
 #define NS_OB16_KERNEL nerf_render_ob16_kernel
 #else
 #define NS_OB16_KERNEL nerf_mlp_ob16_kernel
@@ -80,6 +108,9 @@ using Ob16Lds = FieldLds<kWaves, T * 3 * 1024, 11 * (T * 64)>;
 #include NS_OB16_ASM_INC
 #ifdef NS_OB16_TU_RENDER
 #include "ns_ob16_render_asm.inc"
+#endif
+#ifdef NS_OB16_TU_KBSKIP
+#include "ns_ob16_kbskip_asm.inc"
 #endif
 namespace {
 #ifdef NS_OB16_TU_RENDER
@@ -193,6 +224,63 @@ __device__ __forceinline__ void render_rgb_asm(PipeT& ring, const float* bias_ld
   });
   render_rgb_asm_run<M, T>(ring, bias_lds, g, A, ACCO);
   static_for<T>([&](auto t_) { last[decltype(t_)::value] = __builtin_bit_cast(f32x4a, ACCO[decltype(t_)::value]); });
+}
+#endif
+
+#ifdef NS_OB16_TU_KBSKIP
+// the statements of ns_ob16_kbskip_asm.inc (five tiles): a trunk layer that returns the live mask of its output K-blocks and
+// (KIND > 0) skips the steps of its input's dead ones; sigma and colour as consumers of the trunk's mask
+template <class M, int KIND, bool IN_A, class PipeT>
+__device__ __forceinline__ uint32_t kbs_hidden_layer_asm(PipeT& ring, const float* bias_lds, int g, typename M::Block (&hA)[5][8],
+                                                         typename M::Block (&hB)[5][8], const typename M::Block (&xs)[5][2], uint32_t kmask) {
+  constexpr int T = 5;
+  u32x4 A[8 * T], V[8 * T], X[2 * T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) {
+      constexpr int kb = decltype(kb_)::value;
+      if constexpr (IN_A) A[8 * t + kb] = __builtin_bit_cast(u32x4, hA[t][kb].v);
+      else V[8 * t + kb] = __builtin_bit_cast(u32x4, hB[t][kb].v);
+    });
+    static_for<2>([&](auto kb_) { X[2 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, xs[t][decltype(kb_)::value].v); });
+  });
+  const uint32_t omask = kbs_hidden_asm_run<M, KIND>(ring, bias_lds, g, A, V, X, kmask);
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) {
+      constexpr int kb = decltype(kb_)::value;
+      if constexpr (IN_A) hB[t][kb].v = __builtin_bit_cast(typename M::AFrag, V[8 * t + kb]);
+      else hA[t][kb].v = __builtin_bit_cast(typename M::AFrag, A[8 * t + kb]);
+    });
+  });
+  return omask;
+}
+template <class M, class PipeT>
+__device__ __forceinline__ void kbs_sigma_asm(PipeT& ring, const float* bias_lds, int g, const typename M::Block (&hB)[5][8], u32x4 (&D)[5],
+                                              float (&sigma)[5], uint32_t kmask) {
+  constexpr int T = 5;
+  u32x4 V[8 * T], ACCO[T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) { V[8 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, hB[t][decltype(kb_)::value].v); });
+  });
+  kbs_sigma_asm_run<M>(ring, bias_lds, g, V, D, ACCO, kmask);
+  static_for<T>([&](auto t_) { sigma[decltype(t_)::value] = __builtin_bit_cast(f32x4a, ACCO[decltype(t_)::value])[0]; });
+}
+template <class M, class PipeT>
+__device__ __forceinline__ void kbs_colour_asm(PipeT& ring, const float* bias_lds, int g, const typename M::Block (&hB)[5][8], const u32x4 (&D)[5],
+                                               typename M::Block (&hA)[5][8], uint32_t kmask) {
+  constexpr int T = 5;
+  u32x4 V[8 * T], A[4 * T];
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<8>([&](auto kb_) { V[8 * t + decltype(kb_)::value] = __builtin_bit_cast(u32x4, hB[t][decltype(kb_)::value].v); });
+  });
+  kbs_colour_asm_run<M>(ring, bias_lds, g, V, D, A, kmask);
+  static_for<T>([&](auto t_) {
+    constexpr int t = decltype(t_)::value;
+    static_for<4>([&](auto kb_) { hA[t][decltype(kb_)::value].v = __builtin_bit_cast(typename M::AFrag, A[4 * t + decltype(kb_)::value]); });
+  });
 }
 #endif
 
@@ -422,16 +510,35 @@ NS_OB16_KERNEL(Nerf16Args a) {
     // have been consumed (they fed the embeddings above)
     if constexpr (!PROD) prefetch(nxt_grp);   // (PROD asked before layer 0: compiled code between two statements costs register copies)
     int l = 1;
+    [[maybe_unused]] uint32_t kb_dead = 0, kb_mask7 = 0;   // K-block-skipping kernel: steps jumped over; the trunk output's live mask
     if constexpr (PROD) {
       static_assert(NKB == 8 && (T == 4 || T == 5) && NWAVES == 4, "the generated streams are W = 256, four or five tiles, four waves");
       hidden_layer_asm<M, T, true, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;    // 1
       hidden_layer_asm<M, T, false, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;   // 2
+#ifdef NS_OB16_TU_KBSKIP
+      // live masks of the tested K-blocks travel from each layer to the next in an SGPR; `dead` counts the steps jumped over
+      static_assert(T == 5, "the K-block-skipping statements are five-tile");
+      constexpr uint32_t kAll = (1u << kKbsMaskBits) - 1u;
+      auto dead_of = [&](uint32_t m) { return static_cast<uint32_t>(__builtin_popcount(~m & kAll)); };
+      uint32_t km = kbs_hidden_layer_asm<M, 0, true>(ring, bias, g, hA, hB, xs, kAll); bias += NSB * 16;    // 3
+      kb_dead += NSB * dead_of(km);
+      km = kbs_hidden_layer_asm<M, 1, false>(ring, bias, g, hA, hB, xs, km); bias += NSB * 16;             // 4
+      kb_dead += NSB * dead_of(km);
+      load_xs();
+      km = kbs_hidden_layer_asm<M, 2, true>(ring, bias, g, hA, hB, xs, km); bias += NSB * 16;              // 5: cat[x, h]
+      kb_dead += NSB * dead_of(km);
+      km = kbs_hidden_layer_asm<M, 1, false>(ring, bias, g, hA, hB, xs, km); bias += NSB * 16;             // 6
+      kb_dead += NSB * dead_of(km);
+      km = kbs_hidden_layer_asm<M, 3, true>(ring, bias, g, hA, hB, xs, km); bias += NSB * 16;              // 7: the trunk's output is in hB
+      kb_mask7 = km;
+#else
       hidden_layer_asm<M, T, true, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;    // 3
       hidden_layer_asm<M, T, false, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;   // 4
       load_xs();
       hidden_layer_asm<M, T, true, true>(ring, bias, g, hA, hB, xs); bias += NSB * 16;     // 5: cat[x, h]
       hidden_layer_asm<M, T, false, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;   // 6
       hidden_layer_asm<M, T, true, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;    // 7: the trunk's output is in hB
+#endif
       l = 8;
     }
     // layers 1 .. D-1, two per trip (hA -> hB -> hA); the layer after `skip` sees cat[x, h]
@@ -488,7 +595,12 @@ NS_OB16_KERNEL(Nerf16Args a) {
       // the sigma-first stream: sigma, then EITHER colour and rgb OR their drain twins (see the file's header comment)
       u32x4 D[T];
       static_for<T>([&](auto t_) { D[decltype(t_)::value] = __builtin_bit_cast(u32x4, vs[decltype(t_)::value].v); });
+#ifdef NS_OB16_TU_KBSKIP
+      kbs_sigma_asm<M>(ring, bias, g, hB, D, sigma, kb_mask7); bias += 16;
+      kb_dead += static_cast<uint32_t>(__builtin_popcount(~kb_mask7 & ((1u << kKbsMaskBits) - 1u)));
+#else
       render_sigma_asm<M, T>(ring, bias, g, hB, D, sigma); bias += 16;
+#endif
       // (bitwise, not ||: straight-line code) this lane knows of a sample that may contribute, or that must come out NaN
       uint32_t live = static_cast<uint32_t>(bad != 0) | static_cast<uint32_t>(!rec_finite);
       static_for<T>([&](auto t_) {
@@ -502,7 +614,12 @@ NS_OB16_KERNEL(Nerf16Args a) {
         render_drain_asm_run<M, T, 4>(ring, bias, g);
         static_for<T>([&](auto t_) { last[decltype(t_)::value] = f32x4a{0.0f, 0.0f, 0.0f, 0.0f}; });
       } else {
+#ifdef NS_OB16_TU_KBSKIP
+        kbs_colour_asm<M>(ring, bias, g, hB, D, hA, kb_mask7); bias += (NSB / 2) * 16;
+        kb_dead += (NSB / 2) * static_cast<uint32_t>(__builtin_popcount(~kb_mask7 & ((1u << kKbsMaskBits) - 1u)));
+#else
         render_colour_asm<M, T>(ring, bias, g, hB, D, hA); bias += (NSB / 2) * 16;
+#endif
         render_rgb_asm<M, T>(ring, bias, g, hA, last);
       }
 #else
@@ -533,6 +650,9 @@ NS_OB16_KERNEL(Nerf16Args a) {
     }
     if constexpr (kRenderTU) {
       if (skipped && a.skip_count && le == 0) atomicAdd(a.skip_count, 1u);
+#ifdef NS_OB16_TU_KBSKIP
+      if (kb_dead && a.skip_count && le == 0) atomicAdd(a.skip_count + 1, kb_dead);
+#endif
     }
     if constexpr (!EMBEDDED) nsepi::composite_group(a, rec, comp, grp, gi, par, wave, le);
   }
@@ -577,6 +697,8 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
       if (!EMB && render_eligible(net, a)) {
         Nerf16Args r = a;
         r.stream = static_cast<const char*>(net->stream2_dev); r.bias = net->bias2_dev;
+        // the K-block-skipping twin (opt-in): same launches, same stream; a handle with a non-finite weight stays on the render kernel
+        if (net->kbskip_ok && ns::debug_flags().kblock_skip) return nsob16::launch_kbskip_t5(M::kDtype, r, stream);
         return nsob16::launch_render_t5(M::kDtype, r, stream);
       }
       return nsob16::launch_prod_t5(M::kDtype, EMB, a, stream);
@@ -590,7 +712,12 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
 
 }  // namespace
 
-#if defined(NS_OB16_TU_RENDER)
+#if defined(NS_OB16_TU_KBSKIP)
+int nsob16::launch_kbskip_t5(int dtype, Nerf16Args& a, hipStream_t stream) {
+  if (dtype == Mma16BF16::kDtype) return launch<Mma16BF16, 8, false, true, 5>(a, stream);
+  return launch<Mma16F16, 8, false, true, 5>(a, stream);
+}
+#elif defined(NS_OB16_TU_RENDER)
 int nsob16::launch_render_t5(int dtype, Nerf16Args& a, hipStream_t stream) {
   if (dtype == Mma16BF16::kDtype) return launch<Mma16BF16, 8, false, true, 5>(a, stream);
   return launch<Mma16F16, 8, false, true, 5>(a, stream);

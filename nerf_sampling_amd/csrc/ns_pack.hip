@@ -308,6 +308,13 @@ void finish_sigma_first(const Builder& b2, ns_weights* w) {
       hipMemcpy(s2, b2.bytes.data(), b2.bytes.size(), hipMemcpyHostToDevice) == hipSuccess &&
       hipMemcpy(bias2, b2.bias.data(), b2.bias.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) {
     w->stream2_dev = s2; w->bias2_dev = bias2;
+    // the K-block-skipping render kernel leaves out products with all-zero activations: exact only while no packed weight is
+    // inf or NaN (inf * 0 = NaN); the biases enter as C operands either way
+    const uint16_t expo = w->dtype == NS_DTYPE_BF16 ? 0x7f80u : 0x7c00u;
+    const uint16_t* h = reinterpret_cast<const uint16_t*>(b2.bytes.data());
+    bool finite = true;
+    for (size_t i = 0, n = b2.bytes.size() / 2; i < n && finite; ++i) finite = (h[i] & expo) != expo;
+    w->kbskip_ok = finite ? 1 : 0;
     return;
   }
   (void)hipGetLastError();

@@ -25,6 +25,7 @@ struct ns_weights {
   // bias image in that order (bias_floats as well)
   void* stream2_dev;
   float* bias2_dev;
+  int kbskip_ok;         // 1: every 16-bit weight of the sigma-first stream is finite (the K-block-skipping render kernel may run)
 };
 
 enum { NS_KIND_NERF = 0, NS_KIND_DEPTHNET = 1 };

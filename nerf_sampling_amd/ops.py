@@ -1306,6 +1306,15 @@ def colour_skip_count() -> int:
     return int(n.value)
 
 
+def kblock_skip_count() -> int:
+    """Chunk steps whose MFMAs the K-block-skipping render kernel jumped over (their input K-block was all zero bits for the
+    wave), summed over the waves of the last 16-bit radiance-field launch made under ``debug_switch(count_colour_skips=1)``
+    (0 when that launch ran another kernel); waits for the device."""
+    n = C.c_int64(0)
+    check(_lib.load().ns_kblock_skip_count(C.byref(n)), "ns_kblock_skip_count")
+    return int(n.value)
+
+
 class Event:
     """hipEvent wrapper for timing a kernel on the stream it is launched on."""
 

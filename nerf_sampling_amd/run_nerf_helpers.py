@@ -54,6 +54,61 @@ def get_embedder(multires, i=0, input_dims=4):
     return embedder, embedder.out_dim
 
 
+# ---- the pack-time unit order of a production 16-bit field ---------------------------------------------------------
+# The K-block-skipping render kernel (csrc/ns_nerf_mlp_ob16.hip) jumps over the MFMAs of a chunk step whose input K-block
+# -- 32 hidden units x the wave's 80 samples -- is all zero bits after the ReLU.  With the units in the order they were
+# trained in that never happens; with every trunk layer's units sorted by how often they fire, the rarely firing ones share
+# K-blocks and those are dead for whole waves of empty space.  The order is a permutation of a layer's output units and of the
+# matching input columns of its consumers: the function is unchanged (16-bit results move by the summation order inside the
+# matrix cores only), and no kernel's correctness depends on it.  DESCENDING frequency: the kernel tests the LAST K-blocks of a
+# layer's input and never the first, whose MFMAs carry the bias in.
+UNIT_ORDER_POINTS = 32768
+UNIT_ORDER_RADIUS = 2.0
+UNIT_ORDER_SEED = 20240
+
+
+def firing_counts(net, radius: float = UNIT_ORDER_RADIUS, points: int = UNIT_ORDER_POINTS, seed: int = UNIT_ORDER_SEED):
+    """How many of `points` seeded points, uniform in the ball of `radius`, make each unit of each trunk layer positive, from the
+    module's own fp32 forward (the trunk never sees directions): a list of D int64 tensors [W]."""
+    gen = torch.Generator(device="cpu").manual_seed(seed)      # (explicit: a caller may have set a default device)
+    v = torch.randn(points, 3, generator=gen, dtype=torch.float64, device="cpu")
+    r = torch.rand(points, 1, generator=gen, dtype=torch.float64, device="cpu") ** (1.0 / 3.0) * radius
+    x = (v / v.norm(dim=1, keepdim=True) * r).float()
+    w0 = net.pts_linears[0].weight
+    with torch.no_grad():
+        x = x.to(w0.device)
+        n_freqs = (net.input_ch // 3 - 1) // 2
+        emb = torch.cat([x] + [f(x * 2.0 ** k) for k in range(n_freqs) for f in (torch.sin, torch.cos)], dim=1)
+        h, counts = emb, []
+        for i, lin in enumerate(net.pts_linears):
+            h = torch.relu(torch.nn.functional.linear(h, lin.weight.float(), lin.bias.float()))
+            counts.append((h > 0).sum(dim=0).to(torch.int64).cpu())
+            if i in net.skips:
+                h = torch.cat([emb, h], dim=1)
+    return counts
+
+
+def unit_orders(counts):
+    """per layer: the units by descending firing count, ties by index (a permutation of range(W))"""
+    return [torch.argsort(-c, stable=True) for c in counts]
+
+
+def permute_units(weights, biases, orders, skips, input_ch=63):
+    """The tensors ops.pack_nerf takes (pts_linears.0..D-1, feature, alpha, views, rgb), with unit orders[i][j] of trunk layer i
+    moved to position j: rows and bias of layer i, and the matching input columns of pts_linears[i + 1] (behind the embedded
+    point when i is a skip) or, for the last layer, of feature_linear and alpha_linear.  New tensors; the function is the same."""
+    D = len(orders)
+    ws, bs = [w.clone() for w in weights], [b.clone() for b in biases]
+    for i, perm in enumerate(orders):
+        perm = perm.to(ws[i].device)
+        ws[i], bs[i] = ws[i][perm], bs[i][perm]
+        for c in ([i + 1] if i + 1 < D else [D, D + 1]):
+            off = input_ch if (i in skips and i + 1 < D) else 0
+            cols = torch.cat([torch.arange(off, device=perm.device), off + perm])
+            ws[c] = ws[c][:, cols]
+    return ws, bs
+
+
 class NeRF(nn.Module):
     """Weight container with the reference's state-dict keys (run_nerf_helpers.py:67-105).
 
@@ -102,10 +157,28 @@ class NeRF(nn.Module):
             mods = list(self.pts_linears) + ([self.feature_linear, self.alpha_linear, self.views_linears[0], self.rgb_linear]
                                              if self.use_viewdirs else [self.output_linear])
             dev = self.pts_linears[0].weight.device
-            self._packed[name] = ops.pack_nerf([m.weight for m in mods], [m.bias for m in mods], self.D, self.W, skips, name,
+            ws, bs = [m.weight for m in mods], [m.bias for m in mods]
+            self.unit_orders = None      # the order of the most recent pack (None: that pack kept the trained order)
+            if self._orders_units(name, skips):
+                # once per pack (repack() drops it with the handle): calibrated on seeded points, not on any frame
+                self.unit_orders = unit_orders(firing_counts(self, self.unit_order_radius))
+                with torch.no_grad():
+                    ws, bs = permute_units(ws, bs, self.unit_orders, skips, self.input_ch)
+            self._packed[name] = ops.pack_nerf(ws, bs, self.D, self.W, skips, name,
                                                dev if dev.type == "cuda" else "cuda", use_viewdirs=self.use_viewdirs,
                                                output_ch=self.output_channels)
         return self._packed[name]
+
+    unit_order = True                  # False (or NS_NO_UNIT_ORDER=1 in the environment): pack the units in their own order
+    unit_order_radius = UNIT_ORDER_RADIUS
+    unit_orders = None
+
+    def _orders_units(self, name, skips) -> bool:
+        """production-shaped 16-bit handles only (the ones that get the sigma-first second stream): 8 x 256, skips = [4], view
+        directions, bf16 or f16; f16x3, f32 and generic shapes keep their order"""
+        import os
+        return (self.unit_order and os.environ.get("NS_NO_UNIT_ORDER", "0") != "1" and name in ("bf16", "f16") and self.D == 8
+                and self.W == 256 and list(skips) == [4] and bool(self.use_viewdirs))
 
     def repack(self):
         self._packed = {}

@@ -31,7 +31,8 @@ rule needs it and an independent checker pass re-verifies the final text (tests/
 
 gen_layer() is the layout in use (one dword converted per chunk step, a three-stage pipeline); gen_layer_q() issues the
 same micro-ops from a queue, one per MFMA gap -- measured 2-4 % slower and kept for that A/B
-(--queue4 / --queue5).  --exp-* flags build timing-only ablations (results wrong on purpose).
+(--queue4 / --queue5).  --exp-* flags build timing-only ablations (results wrong on purpose).  --render writes the sigma-first
+tail of the render kernel, --kbskip the statements of its K-block-skipping twin (their sections below).
 """
 import argparse
 import os
@@ -625,7 +626,7 @@ def special_spec(kind, m):
     raise ValueError(kind)
 
 
-def gen_layer_special(dt, kind, m, drain=False):
+def gen_layer_special(dt, kind, m, drain=False, kbs_tags=None, kbs_tested=()):
     """Layer 0, view layer, rgb head as statements (queue layout of gen_layer_q: together they are 9 of the 67 slabs).
     Their streams are not slab multiples: the chunks are padded to the fragment pipeline depth (pad steps carry no MFMA),
     the last slab may be short (its refill pieces ride on its first four steps).
@@ -633,7 +634,11 @@ def gen_layer_special(dt, kind, m, drain=False):
     drain: the statement's twin for a wave that does not need its result -- every step is a pad step.  The ring protocol is
     the full statement's (same slabs, vmcnt waits, barriers, refill pieces with their islab / dsto / M0 bookkeeping, the same
     read-ahead of the NEXT statement's first fragments at the end), so the wave stays in step with the three that compute; no
-    MFMA, no fragment or bias read, no conversion."""
+    MFMA, no fragment or bias read, no conversion.
+
+    kbs_tags (--kbskip): a dict that receives index -> (step, mask bit) of the MFMAs of the steps whose hidden K-block is in
+    kbs_tested (never the bias step, never the view direction's K-block); the ring's s_cmp / s_cselect pair then shares one gap
+    (a step's test would clobber SCC between them)."""
     sp = special_spec(kind, m)
     TT, nsb, nkb = m.T, sp["nsb"], sp["nkb"]
     real = nsb * nkb
@@ -696,6 +701,8 @@ def gen_layer_special(dt, kind, m, drain=False):
                                     "s_and_b32 %[dsto], %[dsto], 0xc000"]
             elif pending_salu:
                 e.salu(pending_salu.pop(0))
+                if kbs_tags is not None and pending_salu and pending_salu[0].startswith("s_cselect"):
+                    e.salu(pending_salu.pop(0))
             if last_of_slab:
                 while pending_salu:
                     e.salu(pending_salu.pop(0))
@@ -720,6 +727,8 @@ def gen_layer_special(dt, kind, m, drain=False):
             share[cands[i % len(cands)]] += 1
         for t in range(TT):
             e.mfma(m.ACC(par, t), frag, sp["operand"](t, kc), m.BIAS if kc == 0 else m.ACC(par, t))
+            if kbs_tags is not None and kc > 0 and kc in kbs_tested:
+                kbs_tags[len(e.ins) - 1] = (p, kbs_bit(kc, kbs_tested))
             if t == 0 and c == 0 and not OPT.no_barrier:
                 e.salu(f"s_waitcnt vmcnt({VM_WAIT})")
                 e.salu("s_barrier")
@@ -1277,13 +1286,545 @@ __device__ __forceinline__ void rgb_asm_run(PipeT& ring, const float* bias_lds, 
 """
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# --kbskip: the five-tile statements of the K-block-skipping render kernel (csrc/ns_ob16_kbskip_asm.inc).
+#
+# A chunk step multiplies one 16 x 32 weight fragment by one K-block (32 features x 16 samples per tile) of the layer's
+# input.  After the packed-int16 ReLU a hidden activation is the bit pattern 0x0000 about half the time; when a K-block is
+# all zero bits for all five tiles of the wave, the step's five MFMAs add only +-0 products.  A PRODUCER (trunk layers 3..7)
+# ORs the packed dwords of its tested output K-blocks into one VGPR (KBS_ACC) as they leave the conversion pipeline and
+# returns a live mask in an SGPR; a CONSUMER (trunk layers 4..7, sigma, colour) takes the mask and branches around the
+# MFMAs of a dead K-block's steps.  Everything else of the step (conversion pieces, fragment read-ahead, LDS-DMA pieces,
+# vmcnt + barrier, bias reads, counted lgkmcnt waits) is in the step's DEAD TWIN too, so the ring protocol and the wait
+# counts are the same on every path:
+#
+#     s_bitcmp1_b32 mask, bit ; s_cbranch_scc1 Llive ; <dead twin: the gaps' instructions> ; s_branch Ljoin
+#     Llive: M0 <G0> M1 <G1> M2 <G2> M3 <G3> M4 ; Ljoin:
+#
+# (both arms within two cache lines of the test: a far dead block would pay an instruction fetch per skipped step).
+# Which K-blocks are tested: KBS_TESTED, the LAST hidden K-blocks -- the pack-time unit order (run_nerf_helpers) puts the
+# units that fire least there.  A test and a branch are two issue slots on a loop that is about issue-bound, so the K-blocks
+# the order makes unlikely to die are not tested.  The sub-block's FIRST step is never tested: its MFMAs carry the bias in
+# as the C operand.  The embedded point (skip layer) and the view direction are never tested.
+#
+# Hazards: the base stream comes from the Emitter on the all-live path; a skipped step shortens distances the position rules
+# rely on (an MFMA result read by the conversion a few steps later).  kbs_repair() walks EVERY mask path with the checker's
+# rules and records the pads a path needs in front of an instruction (common code: on every path; inside an arm: on that arm);
+# kbs_verify() then re-checks every linearised path with check() itself.
+KBS_TESTED = (4, 5, 6, 7)
+KBS_ACC = R('v', 64)                     # the producers' OR accumulator (a clobber of the statement)
+
+
+def kbs_bit(kb, tested=KBS_TESTED):
+    """bit of hidden K-block kb in a live mask: the producers shift the tested K-blocks in, in ascending order"""
+    assert kb in tested
+    return sum(1 for k in tested if k > kb)
+
+
+class KbsProgram:
+    """segments ("c", [Ins]) of common code and ("s", bit, live [Ins], dead [Ins]) of a tested step; pads: id(Ins) -> wait states"""
+
+    def __init__(self, segs, slabs, dt):
+        self.segs, self.slabs, self.dt = segs, slabs, dt
+        self.pads = {}
+        self.bits = sorted({s[1] for s in segs if s[0] == "s"})
+        self.test = Ins("s_bitcmp1_b32 %[kmask], <bit>", "salu")
+        self.cbr = Ins("s_cbranch_scc1 <live>", "salu")
+        self.jmp = Ins("s_branch <join>", "salu")
+
+    def _padded(self, ins):
+        for i in ins:
+            n = self.pads.get(id(i), 0)
+            while n > 0:
+                k = min(n, 8)
+                yield Ins(f"s_nop {k - 1}", "nop", ws=k)
+                n -= k
+            yield i
+
+    def linearise(self, mask):
+        """the instructions a wave with live mask `mask` issues, in order"""
+        out = []
+        for s in self.segs:
+            if s[0] == "c":
+                body = s[1]
+            else:
+                out += [self.test, self.cbr]
+                body = s[2] if (mask >> s[1]) & 1 else s[3] + [self.jmp]
+            out.extend(self._padded(body))
+        return out
+
+    def masks(self):
+        for sub in range(1 << len(self.bits)):
+            yield sum(1 << b for n, b in enumerate(self.bits) if (sub >> n) & 1)
+
+    def text(self):
+        lines, n = [], 0
+        for s in self.segs:
+            if s[0] == "c":
+                lines += [i.text for i in self._padded(s[1])]
+                continue
+            n += 1
+            lines += [f"s_bitcmp1_b32 %[kmask], {s[1]}", f"s_cbranch_scc1 .Lkl%=_{n}"]
+            lines += [i.text for i in self._padded(s[3])] + [f"s_branch .Lkj%=_{n}", f".Lkl%=_{n}:"]
+            lines += [i.text for i in self._padded(s[2])] + [f".Lkj%=_{n}:"]
+        return lines
+
+
+def kbs_split(e, tags, slabs, dt):
+    """the Emitter's all-live stream -> KbsProgram: a tested step is first .. last tagged MFMA; its dead twin is the same
+    instructions without the MFMAs and without the live path's pads"""
+    steps = {}
+    for idx, (p, bit) in tags.items():
+        lo, hi, b = steps.get(p, (idx, idx, bit))
+        steps[p] = (min(lo, idx), max(hi, idx), bit)
+    segs, at = [], 0
+    for p in sorted(steps):
+        lo, hi, bit = steps[p]
+        assert lo >= at and all((k in tags) == (e.ins[k].kind == "mfma") for k in range(lo, hi + 1))
+        if lo > at:
+            segs.append(("c", e.ins[at:lo]))
+        live = e.ins[lo:hi + 1]
+        dead = [Ins(i.text, i.kind) for i in live if i.kind not in ("mfma", "nop")]
+        for d, i in zip(dead, [i for i in live if i.kind not in ("mfma", "nop")]):
+            d.reads, d.writes, d.creads, d.ws = i.reads, i.writes, i.creads, i.ws
+        segs.append(("s", bit, live, dead))
+        at = hi + 1
+    segs.append(("c", e.ins[at:]))
+    return KbsProgram(segs, slabs, dt)
+
+
+def kbs_deficits(seq):
+    """check()'s rules on one linearised path, returning [(instruction, missing wait states)] instead of failing; a missing pad
+    is taken as given from there on.  LDS results must be waited for on every path: that cannot be padded and fails here."""
+    pos, xw, vw, xc, fifo, clk, out = 0, {}, {}, {}, [], Clock(), []
+    for i in seq:
+        need = 0
+        touched = i.reads | i.creads | i.writes
+        if i.kind == "wait" and "lgkmcnt" in i.text:
+            left = int(i.text.split("lgkmcnt(")[1].split(")")[0])
+            del fifo[:max(len(fifo) - left, 0)]
+        for dst in fifo:
+            assert not (dst & touched), f"LDS result not waited for: {i.text}"
+        if i.kind == "mfma":
+            for r in touched:
+                need = max(need, vw.get(r, -99) + VALU_WRITE_TO_XDL - pos)
+            for r in i.reads:
+                need = max(need, xw.get(r, -99) + XDL_WRITE_TO_OTHER - pos)
+            if i.creads != i.writes:
+                for r in i.creads:
+                    need = max(need, xw.get(r, -99) + XDL_WRITE_TO_OTHER - pos)
+                for r in i.writes:
+                    need = max(need, xc.get(r, -99) + XDL_READC_TO_WRITE - pos)
+        elif i.kind in ("valu", "lds", "dma"):
+            for r in touched:
+                need = max(need, xw.get(r, -99) + XDL_WRITE_TO_OTHER - pos)
+            for r in i.writes:
+                need = max(need, xc.get(r, -99) + XDL_READC_TO_WRITE - pos)
+            need = max(need, clk.need(touched))
+        if need > 0:
+            out.append((i, need))
+            pos += need
+            clk.t += need
+        clk.issue(i)
+        pos += i.ws
+        if i.kind == "mfma":
+            for r in i.writes:
+                xw[r] = pos
+            for r in i.creads:
+                xc[r] = pos
+        elif i.kind == "valu":
+            for r in i.writes:
+                vw[r] = pos
+        elif i.kind == "lds":
+            fifo.append(i.writes)
+    assert not fifo, "LDS reads outstanding at the end of the statement"
+    return out
+
+
+def kbs_repair(prog):
+    """pads until no path of the program misses a wait state (a pad only lengthens distances: a few rounds)"""
+    for _ in range(8):
+        grew = False
+        for mask in prog.masks():
+            for i, n in kbs_deficits(prog.linearise(mask)):
+                assert i.kind != "nop" and i not in (prog.test, prog.cbr, prog.jmp)
+                prog.pads[id(i)] = prog.pads.get(id(i), 0) + n
+                grew = True
+        if not grew:
+            return prog
+    raise AssertionError("the pads of the mask paths did not settle")
+
+
+def kbs_verify(prog, masks=None):
+    """every (or the given) mask path through check(), and the path-independent protocol: barriers, vmcnt waits, DMA pieces,
+    LDS reads, lgkmcnt waits and every VALU / SALU instruction are the same sequence on every path"""
+    def protocol(seq):
+        return [i.text for i in seq if i.kind not in ("mfma", "nop") and i not in (prog.test, prog.cbr, prog.jmp)]
+    full = max(prog.masks())
+    want = protocol(prog.linearise(full))
+    for mask in (prog.masks() if masks is None else masks):
+        seq = prog.linearise(mask)
+        check(seq)
+        assert protocol(seq) == want, f"mask {mask:#x}: the path drops or reorders a non-MFMA instruction"
+    return len(want)
+
+
+def gen_layer_kbs(dt, in_a, skip, consume, tested=KBS_TESTED, nsb=16, nkb_h=8):
+    """gen_layer() for the five-tile wave (ReLU), as a producer of the live mask %[omask] of its tested output K-blocks and,
+    when `consume`, a consumer of %[kmask] for the tested K-blocks of its input.  Differences from gen_layer(): the ORs ride in
+    G1 every second step (two freshly clamped dwords per v_or3_b32: the pair is still in its scratch registers / already in set
+    V there) and behind the extra pieces in G3; a finished K-block costs v_cmp_ne_u32 + s_cmp_lg_u64 + s_addc_u32 in the last
+    gap; the ring's s_cmp / s_cselect pair shares one gap (a step's test would clobber SCC between them)."""
+    m = Map5
+    T, ACC, FR, BIAS, TMP, VOFF, XS = m.T, m.ACC, m.FR, m.BIAS, m.TMP, m.VOFF, m.XS
+    nkb = nkb_h + (2 if skip else 0)
+    total = nsb * nkb
+    assert total % SLAB == 0 and total % DEPTH == 0 and 0 not in tested and not any(getattr(OPT, k) for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"))
+    slabs = total // SLAB
+    IN = m.SETA if in_a else m.SETV
+    OUT = m.SETV if in_a else m.SETA
+    cvt = "v_cvt_pk_bf16_f32" if dt == "bf16" else "v_cvt_pk_f16_f32"
+    e = Emitter(dt)
+    tags = {}
+    e.salu("s_mov_b32 %[keep], m0")
+    e.salu("s_mov_b32 %[omask], 0")
+    e.lds_read(BIAS, "%[bias]", 0)
+
+    def dma_setup():
+        e.valu(f"v_lshl_add_u32 {fmt(VOFF)}, %[islab], 14, %[loff]", (), (VOFF,))
+        e.salu("s_add_u32 m0, %[dsto], %[ldsw]")
+
+    dma_setup()
+    e.nop(VALU_WRITE_TO_XDL)
+
+    def piece_regs(s, piece):
+        t, J = piece % T, piece // T
+        a = ACC(s & 1, t)
+        dst = OUT(t, s >> 1)
+        return R('v', a[1] + 2 * J), R('v', a[1] + 2 * J + 1), R(dst[0], dst[1] + 2 * (s & 1) + J)
+
+    clamped = []                         # (output K-block, register holding the clamped dword) not ORed yet
+    extra_clamped = []                   # ... of the extra pieces (ORed one at a time, a stage later)
+    started, n_ored, fin_q = set(), {}, []
+
+    def op_cvt(s, piece, tmp):
+        lo, hi, _ = piece_regs(s, piece)
+        e.valu(f"{cvt} {fmt(tmp)}, {fmt(lo)}, {fmt(hi)}", (lo, hi), (tmp,))
+
+    def op_max(s, piece, tmp):
+        dword = piece_regs(s, piece)[2]
+        dst = dword if in_a else tmp
+        e.valu(f"v_pk_max_i16 {fmt(dst)}, {fmt(tmp)}, 0", (tmp,), (dst,))
+        clamped.append((s >> 1, dst))
+
+    def op_accw(s, piece, tmp):
+        if not in_a:
+            dword = piece_regs(s, piece)[2]
+            e.valu(f"v_accvgpr_write_b32 {fmt(dword)}, {fmt(tmp)}", (tmp,), (dword,))
+
+    def g_or(n):
+        """OR the n oldest clamped dwords (one or two, of one K-block) into the accumulator"""
+        items = [clamped.pop(0) for _ in range(n)]
+        okb = items[0][0]
+        assert all(k == okb for k, _ in items)
+        n_ored[okb] = n_ored.get(okb, 0) + n
+        if n_ored[okb] == 4 * T:
+            fin_q.append(okb)
+        if okb not in tested:
+            return
+        srcs = [r for _, r in items]
+        if okb not in started:
+            assert n == 2
+            started.add(okb)
+            e.valu(f"v_or_b32_e32 {fmt(KBS_ACC)}, {fmt(srcs[0])}, {fmt(srcs[1])}", srcs, (KBS_ACC,))
+        elif n == 2:
+            e.valu(f"v_or3_b32 {fmt(KBS_ACC)}, {fmt(srcs[0])}, {fmt(srcs[1])}, {fmt(KBS_ACC)}", srcs + [KBS_ACC], (KBS_ACC,))
+        else:
+            e.valu(f"v_or_b32_e32 {fmt(KBS_ACC)}, {fmt(srcs[0])}, {fmt(KBS_ACC)}", srcs + [KBS_ACC], (KBS_ACC,))
+
+    def g_finish():
+        while fin_q:
+            okb = fin_q.pop(0)
+            if okb in tested:
+                e.valu(f"v_cmp_ne_u32_e32 vcc, 0, {fmt(KBS_ACC)}", (KBS_ACC,), ())
+                e.salu("s_cmp_lg_u64 vcc, 0")
+                e.salu("s_addc_u32 %[omask], %[omask], %[omask]")
+
+    n_main = min(2 * T, nkb)
+    extras = list(range(n_main, 2 * T))
+    max_q, accw_q = [], []
+    pending_salu = []
+    for p in range(total):
+        sb, kc = divmod(p, nkb)
+        par = sb & 1
+        c = p % SLAB
+        frag = FR(p)
+        hk = kc - (2 if skip else 0)     # the hidden K-block of this step (< 0: the embedded point)
+        bit = kbs_bit(hk, tested) if (consume and kc > 0 and hk in tested) else None
+
+        def operand(t):
+            if skip:
+                return XS(t, kc) if kc < 2 else IN(t, kc - 2)
+            return IN(t, kc)
+
+        def mm(t):
+            e.mfma(ACC(par, t), frag, operand(t), BIAS if kc == 0 else ACC(par, t))
+            if bit is not None:
+                tags[len(e.ins) - 1] = (p, bit)
+
+        mm(0)
+        # ---- G0
+        if c == 0:
+            e.salu(f"s_waitcnt vmcnt({VM_WAIT})")
+            e.salu("s_barrier")
+        if max_q:
+            op_max(*max_q[0])
+            accw_q.append(max_q.pop(0))
+        mm(1)
+        # ---- G1
+        q = p + DEPTH - 1
+        e.lds_read(FR(q), f"%[rb{(q // SLAB) % RING}]", (q % SLAB) * 1024)
+        if len(clamped) >= 2:
+            g_or(2)
+        mm(2)
+        # ---- G2
+        if sb > 0 and kc < n_main:
+            item = (sb - 1, kc, TMP[kc & 1])
+            op_cvt(*item)
+            max_q.append(item)
+        if accw_q:
+            op_accw(*accw_q.pop(0))
+        mm(3)
+        # ---- G3: the two extra pieces of an eight-step sub-block, one after the other through m.TMP3
+        if sb > 0:
+            for n, x in enumerate(extras):
+                stage = kc - (1 + 3 * n)
+                if stage == 0:
+                    op_cvt(sb - 1, x, m.TMP3)
+                elif stage == 1:
+                    dword = piece_regs(sb - 1, x)[2]
+                    dst = dword if in_a else m.TMP3
+                    e.valu(f"v_pk_max_i16 {fmt(dst)}, {fmt(m.TMP3)}, 0", (m.TMP3,), (dst,))
+                    extra_clamped.append(((sb - 1) >> 1, dst))
+                elif stage == 2:
+                    op_accw(sb - 1, x, m.TMP3)
+                    clamped.insert(0, extra_clamped.pop(0))
+                    g_or(1)
+        mm(4)
+        # ---- last gap
+        if c in OPT.dma_steps:
+            e.dma(OPT.dma_steps.index(c) * 1024, VOFF)
+            if c == OPT.dma_steps[-1]:
+                pending_salu = [["s_add_i32 %[islab], %[islab], 1"],
+                                ["s_cmp_lg_u32 %[islab], %[nsl]", "s_cselect_b32 %[islab], %[islab], 0"],
+                                ["s_add_i32 %[dsto], %[dsto], 0x4000"], ["s_and_b32 %[dsto], %[dsto], 0xc000"]]
+        elif pending_salu:
+            for text in pending_salu.pop(0):
+                e.salu(text)
+        elif c == SLAB - 1 and p + 1 < total:
+            dma_setup()
+        if kc == min(3, nkb - 1) and sb + 1 < nsb:
+            e.lds_read(BIAS, "%[bias]", 64 * (sb + 1))
+        g_finish()
+    assert not pending_salu and not extra_clamped
+    # ---- tail: as gen_layer(), with the ORs of what is clamped here and the last K-block's mask bit
+    for it in max_q:
+        op_max(*it)
+    while clamped:
+        g_or(2)
+    for it in accw_q + max_q:
+        op_accw(*it)
+    s = nsb - 1
+    scratch = [R('v', ACC((s & 1) ^ 1, 0)[1] + i) for i in range(2 * T)]
+    for t0 in range(0, T, 2):
+        pcs = [t + T * J for t in (t0, t0 + 1) if t < T for J in (0, 1)]
+        for piece in pcs:
+            op_cvt(s, piece, scratch[piece])
+        for piece in pcs:
+            op_max(s, piece, scratch[piece])
+        while clamped:
+            g_or(2)
+        for piece in pcs:
+            op_accw(s, piece, scratch[piece])
+    g_finish()
+    assert sorted(n_ored) == list(range(nsb // 2)) and all(v == 4 * T for v in n_ored.values()) and started == set(tested)
+    e.drain_lds()
+    e.salu("s_mov_b32 m0, %[keep]")
+    e.nop(VALU_WRITE_TO_XDL)
+    check(e.ins)
+    return kbs_repair(kbs_split(e, tags, slabs, dt))
+
+
+def gen_special_kbs(dt, kind, tested=KBS_TESTED):
+    """the five-tile sigma / colour statement of the sigma-first tail as a consumer of %[kmask] (the trunk's output): the steps
+    and the ring protocol of gen_layer_special()"""
+    assert kind in ("sigma", "colour") and 0 not in tested and not any(getattr(OPT, k) for k in ("no_wait", "no_lds"))
+    tags = {}
+    e, slabs = gen_layer_special(dt, kind, Map5, kbs_tags=tags, kbs_tested=tested)
+    return kbs_repair(kbs_split(e, tags, slabs, dt))
+
+
+# KbsAsm<M, KIND>: the statements in the order the kernel runs them
+KBS_KINDS = (("hidden", dict(in_a=True, skip=False, consume=False)),    # 0: trunk layer 3, producer only (set A -> set V)
+             ("hidden", dict(in_a=False, skip=False, consume=True)),    # 1: trunk layers 4 and 6 (set V -> set A)
+             ("hidden", dict(in_a=True, skip=True, consume=True)),      # 2: trunk layer 5, cat[x, h] (set A -> set V)
+             ("hidden", dict(in_a=True, skip=False, consume=True)),     # 3: trunk layer 7 (set A -> set V)
+             ("sigma", None),                                           # 4: the view layer's sigma sub-block
+             ("colour", None))                                          # 5: its eight colour sub-blocks
+
+
+def gen_kbs(dt, kid, tested=KBS_TESTED):
+    kind, kw = KBS_KINDS[kid]
+    return gen_layer_kbs(dt, tested=tested, **kw) if kind == "hidden" else gen_special_kbs(dt, kind, tested)
+
+
+def cpp_kbs(dt, kid, prog):
+    mp, nt = Map5, 5
+    mname = {"bf16": "Mma16BF16", "f16": "Mma16F16"}[dt]
+    kind, kw = KBS_KINDS[kid]
+    text = "\\n\\t\"\n      \"".join(prog.text())
+    outs, ins, params = [], [], []
+    clobber = list(mp.CLOBBER)
+    if kind == "hidden":
+        clobber.append(KBS_ACC[1])
+        params = [f"u32x4 (&A)[{8 * nt}]", f"u32x4 (&V)[{8 * nt}]", f"const u32x4 (&X)[{2 * nt}]"]
+        for t in range(nt):
+            for kb in range(8):
+                k = 8 * t + kb
+                if kw["in_a"]:
+                    outs.append(f'"=&{{{fmt(mp.SETV(t, kb))}}}"(V[{k}])')
+                    ins.append(f'"{{{fmt(mp.SETA(t, kb))}}}"(A[{k}])')
+                else:
+                    outs.append(f'"=&{{{fmt(mp.SETA(t, kb))}}}"(A[{k}])')
+                    ins.append(f'"{{{fmt(mp.SETV(t, kb))}}}"(V[{k}])')
+        if kw["skip"]:
+            for t in range(nt):
+                for kb in range(2):
+                    ins.append(f'"{{{fmt(mp.XS(t, kb))}}}"(X[{2 * t + kb}])')
+    else:
+        params = [f"const u32x4 (&V)[{8 * nt}]", f"u32x4 (&D)[{nt}]" if kind == "sigma" else f"const u32x4 (&D)[{nt}]"]
+        for t in range(nt):
+            for kb in range(8):
+                ins.append(f'"{{{fmt(mp.SETV(t, kb))}}}"(V[{8 * t + kb}])')
+            if kind == "sigma":
+                outs.append(f'"+{{{fmt(mp.XS(t, 0))}}}"(D[{t}])')
+            else:
+                ins.append(f'"{{{fmt(mp.XS(t, 0))}}}"(D[{t}])')
+        if kind == "colour":
+            params.append(f"u32x4 (&A)[{4 * nt}]")
+            for t in range(nt):
+                for kb in range(4):
+                    outs.append(f'"=&{{{fmt(mp.SETA(t, kb))}}}"(A[{4 * t + kb}])')
+        else:
+            params.append(f"u32x4 (&ACCO)[{nt}]")
+            for t in range(nt):
+                r = mp.ACC(0, t)
+                outs.append(f'"=&{{{fmt(r)}}}"(ACCO[{t}])')
+                for i in range(4):
+                    clobber.remove(r[1] + i)
+    for i in range(DEPTH):
+        outs.append(f'"+{{{fmt(mp.FR(i))}}}"(F[{i}])')
+    outs += ['[islab] "+s"(islab)', '[dsto] "+s"(dsto)', '[keep] "=&s"(keep)']
+    if kind == "hidden":
+        outs.append('[omask] "=&s"(omask)')
+    ins += ['[rb0] "v"(rb0)', '[rb1] "v"(rb1)', '[rb2] "v"(rb2)', '[rb3] "v"(rb3)', '[bias] "v"(bias)', '[loff] "v"(loff)',
+            '[sbase] "s"(sbase)', '[nsl] "s"(nsl)', '[ldsw] "s"(ldsw)', '[kmask] "s"(kmask)']
+    clob = ['"memory"', '"scc"', '"vcc"'] + [f'"v{i}"' for i in clobber]
+    n_steps = sum(s[0] == "s" for s in prog.segs)
+    n_pad = sum(prog.pads.values())
+    tail = ", uint32_t kmask" + (", uint32_t& omask" if kind == "hidden" else "")
+    return f"""
+// {dt} KIND {kid} ({kind}{'' if kw is None else ' ' + ' '.join(k for k, v in kw.items() if v)}): {prog.slabs} slabs, {n_steps} tested steps, {len(prog.bits)} mask bits, {n_pad} pad wait states for the skip paths
+template <> struct KbsAsm<{mname}, {kid}> {{
+  static constexpr int kSlabs = {prog.slabs};
+  static constexpr int kTestedSteps = {n_steps};
+  static __device__ __forceinline__ void run({', '.join(params + ['u32x4 (&F)[4]'])},
+                                             uint32_t rb0, uint32_t rb1, uint32_t rb2, uint32_t rb3, uint32_t bias, uint32_t loff,
+                                             uint64_t sbase, uint32_t nsl, uint32_t ldsw, uint32_t& islab, uint32_t& dsto{tail}) {{
+    uint32_t keep;
+    asm volatile(
+      "{text}"
+      : {', '.join(outs)}
+      : {', '.join(ins)}
+      : {', '.join(clob)});
+  }}
+}};
+"""
+
+
+KBS_HEADER = """// GENERATED by tools/gen_ob16_asm.py --kbskip -- do not edit; regenerate with `python tools/gen_ob16_asm.py --kbskip`.
+// The five-tile statements of the K-block-skipping render kernel (ns_nerf_mlp_ob16.hip, NS_OB16_TU_KBSKIP): trunk layers 3..7,
+// sigma and colour with a live mask of the tested hidden K-blocks (the generator's --kbskip section has the rules).  Included
+// after ns_ob16_asm.inc and ns_ob16_render_asm.inc.
+#pragma once
+namespace nsmlp {
+// KIND: 0 layer 3 (producer only), 1 layers 4 / 6, 2 layer 5 (skip), 3 layer 7, 4 sigma, 5 colour
+template <class M, int KIND> struct KbsAsm;
+constexpr uint32_t kKbsMaskBits = <NBITS>;      // live-mask bits: hidden K-block kb of the tested set <TESTED> is bit <BITS>
+"""
+
+KBS_FOOTER = """
+// one trunk layer: returns the live mask of its output; kmask: the live mask of its input (KIND 0 ignores it)
+template <class M, int KIND, class PipeT>
+__device__ __forceinline__ uint32_t kbs_hidden_asm_run(PipeT& ring, const float* bias_lds, int g, u32x4 (&A)[40], u32x4 (&V)[40], const u32x4 (&X)[10],
+                                                       uint32_t kmask) {
+  using Gen = KbsAsm<M, KIND>;
+  AsmRingArgs r;
+  uint32_t omask;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(A, V, X, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto, kmask, omask);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+  return omask;
+}
+template <class M, class PipeT>
+__device__ __forceinline__ void kbs_sigma_asm_run(PipeT& ring, const float* bias_lds, int g, const u32x4 (&V)[40], u32x4 (&D)[5], u32x4 (&ACCO)[5],
+                                                  uint32_t kmask) {
+  using Gen = KbsAsm<M, 4>;
+  static_assert(Gen::kSlabs == RenderAsm<M, 5, 0>::kSlabs, "the sigma statement's slabs");
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(V, D, ACCO, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto, kmask);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+template <class M, class PipeT>
+__device__ __forceinline__ void kbs_colour_asm_run(PipeT& ring, const float* bias_lds, int g, const u32x4 (&V)[40], const u32x4 (&D)[5], u32x4 (&A)[20],
+                                                   uint32_t kmask) {
+  using Gen = KbsAsm<M, 5>;
+  static_assert(Gen::kSlabs == RenderAsm<M, 5, 1>::kSlabs, "the colour statement's slabs");
+  AsmRingArgs r;
+  asm_ring_begin(ring, bias_lds, g, r);
+  Gen::run(V, D, A, r.F, r.rb0, r.rb1, r.rb2, r.rb3, r.bias, r.loff, r.sbase, r.nsl, r.ldsw, r.islab, r.dsto, kmask);
+  asm_ring_end<typename M::AFrag>(ring, r, Gen::kSlabs);
+}
+}  // namespace nsmlp
+"""
+
+
+def kbs_main(path, tested=KBS_TESTED):
+    """--kbskip: every statement repaired over all its mask paths and verified (kbs_verify) before it is written"""
+    bits = ", ".join(f"{kb} -> {kbs_bit(kb, tested)}" for kb in tested)
+    out = [KBS_HEADER.replace("<NBITS>", str(len(tested))).replace("<TESTED>", "{" + ", ".join(map(str, tested)) + "}").replace("<BITS>", bits)]
+    for dt in ("bf16", "f16"):
+        for kid in range(len(KBS_KINDS)):
+            prog = gen_kbs(dt, kid, tested)
+            kbs_verify(prog)
+            out.append(cpp_kbs(dt, kid, prog))
+            print(f"{dt} KIND {kid}: {sum(s[0] == 's' for s in prog.segs)} tested steps, pads {sum(prog.pads.values())}", file=sys.stderr)
+    out.append(KBS_FOOTER)
+    with open(path, "w") as f:
+        f.write("".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "nerf_sampling_amd", "csrc")
     ap.add_argument("-o", help="output file (default: csrc/ns_ob16_asm.inc, or csrc/ns_ob16_render_asm.inc with --render)")
     ap.add_argument("--render", action="store_true",
                     help="write the sigma-first tail of the renderer (sigma, colour, rgb and the drain twins; five tiles) instead")
-    ap.add_argument("--render-tiles4", action="store_true", help="with --render: the four-tile statements as well")
+    ap.add_argument("--kbskip", action="store_true",
+                    help="write the statements of the K-block-skipping render kernel (csrc/ns_ob16_kbskip_asm.inc) instead")
+    ap.add_argument("--kbs-tested", default=",".join(map(str, KBS_TESTED)), help="with --kbskip: the hidden K-blocks the consumers test")
+    ap.add_argument("--render-tiles4",action="store_true", help="with --render: the four-tile statements as well")
     ap.add_argument("--dump", help="write the plain instruction stream of one variant (e.g. bf16_AV) here")
     for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"):
         ap.add_argument("--exp-" + k.replace("_", "-"), dest=k, action="store_true")
@@ -1296,6 +1837,9 @@ def main():
     assert len(OPT.dma_steps) == 4 and OPT.dma_steps[-1] <= 9
     for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"):
         setattr(OPT, k, getattr(a, k))
+    if a.kbskip:
+        kbs_main(a.o or os.path.join(csrc, "ns_ob16_kbskip_asm.inc"), tuple(int(x) for x in a.kbs_tested.split(",")))
+        return
     if a.render:
         render_main(a.o or os.path.join(csrc, "ns_ob16_render_asm.inc"), (Map4, Map5) if a.render_tiles4 else (Map5,))
         return
