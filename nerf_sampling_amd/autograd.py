@@ -543,6 +543,10 @@ class DepthNetFunction(torch.autograd.Function):
     def forward(ctx, o: Tensor, d: Tensor, near: float, far: float, radius: float, n: int, *params: Tensor):
         W_ = params[0::2]
         B_ = params[1::2]
+        ctx.no_rays = o.shape[0] == 0
+        if ctx.no_rays:        # nothing to launch (the batched GEMM takes no empty problem): z is empty, every gradient zero
+            ctx.param_like = [(p.shape, p.device) for p in params]
+            return torch.empty((0, 1), dtype=torch.float32, device=o.device)
         e_o, e_d = ops.posenc(o, 10), ops.posenc(d, 10)
         _, P = ops.sphere_intersect(o, d, radius)
         e_x = ops.posenc(P.reshape(-1, 6), 10)
@@ -587,6 +591,9 @@ class DepthNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz: Tensor):
+        if ctx.no_rays:
+            zeros = [torch.zeros(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_like]
+            return (None, None, None, None, None, None, *zeros)
         n, W_, width = ctx.n, ctx.weights, ctx.width
         grads: List[Optional[Tensor]] = [None] * (2 * (4 * n + 1))
         dev = ctx.s.device
