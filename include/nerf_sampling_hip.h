@@ -64,7 +64,9 @@ int ns_device_cu_count(void);
  *   "count_colour_skips" 0/1 -- 1: every render-kernel launch counts the waves that skipped their colour statements and the
  *                            chunk steps whose MFMAs the K-block-skipping kernel jumped over;
  *   "kblock_skip" 0/1     -- 1: launches the render kernel takes run its K-block-skipping twin instead (same results bit for
- *                            bit; off by default: it measured no faster than the render kernel).
+ *                            bit; off by default: it measured no faster than the render kernel);
+ *   "mesh_raster_big_box" n >= 0 -- ns_mesh_raster's faces whose clamped bounding box has more than n pixels take its workgroup
+ *                            launch; 0 = NS_MESH_RASTER_BIG_BOX.
  * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES, NS_KBLOCK_SKIP), read once at first use. */
 int ns_debug_set(const char* name, int value);
 /* Waves that skipped the colour layers in the LAST bf16 / f16 radiance-field launch on the current device that ran with
@@ -333,6 +335,67 @@ int64_t ns_mesh_normals_workspace_bytes(int64_t V);
 int ns_mesh_normals(const float* sigma_dev, int64_t sigma_stride, int Gx, int Gy, int Gz, float iso, float h_x, float h_y,
                     float h_z, const int64_t* key_dev, int64_t V, float* normal_out, int64_t* count_dev, void* workspace_dev,
                     void* stream);
+
+/* ---- the device mesh rasterised from a pinhole camera  (the frame a mesh viewer shows; not in the reference) ----  A z-buffer
+ * rasteriser whose frame sits on the field's: depth_out is the ray parameter along the unnormalised direction of ns_get_rays'
+ * pixel (its camera-space z component is -1), the unit of the one-call renderers' depth extra, so ns_depth_sqerr and
+ * ns_image_sqerr score the mesh against the field and the photographs.  A result is a function of the inputs alone.
+ * INPUTS: vertices_dev fp32 [V,3]; faces_dev int64 [F,3] (ops.mesh_weld's); attr_dev fp32 [V,3] vertex colours or NULL; the
+ * camera as ns_get_rays takes it (c2w_host: 12 host floats, row-major [3,4]; fx, fy, cx, cy; H, W); near_ > 0; cull 0 none,
+ * 1 back faces, 2 front faces; background.
+ * PROJECTION of vertex p, every fp32 operation rounded on its own (the inverse of ns_get_rays' pixel ray), r = c2w[:3,:3]
+ * row-major, t = c2w[:3,3]:  e_c = p_c - t_c;  q_k = (e_0 r[k] + e_1 r[3 + k]) + e_2 r[6 + k], k = 0, 1, 2;  z = -q_2;
+ * x = cx + fx (q_0 / z);  y = cy - fy (q_1 / z).  Pixel (column i, row j) is the sample point (x, y) = (i, j), NOT
+ * (i + 1/2, j + 1/2): the project's ray through pixel (i, j) uses (i - cx) / fx.
+ * SNAPPING: X = (int64) rintf(x * 256.0f), Y likewise: eight sub-pixel bits, round half to even.  A vertex is UNUSABLE if x, y
+ * or z is not finite, z < near_, or |x| or |y| exceeds 2^20 pixels -- with that bound |X|, |Y| <= 2^28 and every edge value
+ * below is smaller than 2^59 in magnitude.  A face with an unusable vertex is dropped and counted in count_dev[0] (clipped):
+ * there is no near-plane clipping, and the count says when a camera sits inside the mesh.
+ * COVERAGE, int64 throughout: E_AB(P) = (B_x - A_x)(P_y - A_y) - (B_y - A_y)(P_x - A_x); pixel (i, j) is P = (256 i, 256 j);
+ * area2 = E_01(V_2).  area2 == 0: dropped and counted in count_dev[1] (degenerate).  FACING: x grows to the right and y DOWN the
+ * frame, so a face of ns_mesh_extract's outward winding seen from outside has area2 < 0: that is the FRONT; cull = 1 drops
+ * faces with area2 > 0, cull = 2 those with area2 < 0 (neither is counted).  w_0 = E_12(P), w_1 = E_20(P), w_2 = E_01(P) are
+ * the edge values opposite vertices 0, 1, 2 and sum to area2.  With sg = the sign of area2, the pixel is covered iff for each
+ * k: sg w_k > 0, or sg w_k == 0 and the TIE RULE gives the edge's points to this side -- top-left, a function of the edge's two
+ * snapped end points and the side alone: for d = sg (B - A), the edge walked so that the triangle lies where its edge value is
+ * positive, a centre on the edge is covered iff d_y < 0 (the triangle lies at larger x: a left edge) or d_y == 0 and d_x > 0
+ * (it lies at larger y: a top edge).  The two sides of an edge get opposite d, so a centre on an edge shared by two triangles
+ * that do not overlap is covered by exactly one of them whatever their windings, and a centre on the shared vertex of a closed
+ * fan by exactly one triangle of the fan (the rule is that of sampling at P + (eps, eps^2)).  The bounding box is clamped to
+ * the frame; faces wholly outside it are no error and are not counted.
+ * DEPTH of a covered pixel, fp64: s = ((double) w_0 / (double) z_0 + (double) w_1 / (double) z_1) + (double) w_2 / (double) z_2,
+ * zpix = (float)((double) area2 / s): perspective-correct (1 / z is affine on the screen), never below the smallest z_k.
+ * Z-BUFFER: one uint64 per pixel, all ones when empty; a fragment is ((uint64) bits(zpix) << 32) | (uint32) face index, merged
+ * by a 64-bit unsigned atomic minimum: zpix >= near_ > 0, so the bits order as the values do -- the nearest surface wins, at
+ * equal depth bits the smaller face index.  Integer atomics only (that minimum, and atomicAdd on the counters and on the
+ * length of a list of faces); no floating-point atomic anywhere, so nothing depends on the order of the atomics.
+ * RESOLVE: an empty pixel gets depth_out = 0 (the field's depth of a ray through empty space), tri_out = -1, rgb_out =
+ * background.  A covered one: depth_out and tri_out from the word; rgb_out per channel c from the w_k of that face recomputed
+ * at that pixel, num = ((w_0 / z_0) a_0c + (w_1 / z_1) a_1c) + (w_2 / z_2) a_2c in fp64 with the quotients of DEPTH,
+ * rgb_out = (float)(num / s).  depth_out fp32 [H*W], tri_out int32 [H*W], rgb_out fp32 [H*W,3]: any may be NULL.
+ * INVALID face: an index outside [0, V) -- negative ones and those >= 2^32 included -- is counted in count_dev[2] and only
+ * there; none of its indices is ever used as an address.  count_dev[3] = the number of covered pixels.  All four int64 are
+ * overwritten, not accumulated.  Nothing is written outside the outputs and workspace_dev
+ * (ns_mesh_raster_workspace_bytes(V, F, H, W) bytes; what it holds before the call does not matter).
+ * LAUNCHES, all on `stream`, nothing read back in between, no workgroup waiting for another: (1) z-buffer and counters cleared;
+ * (2) every vertex projected once into the workspace (X, Y, z, usable); (3) workgroup g takes the NS_MESH_RASTER_SHARE faces
+ * from g * NS_MESH_RASTER_SHARE on (thread t takes g * NS_MESH_RASTER_SHARE + s * 256 + t): a face whose clamped bounding box
+ * has at most NS_MESH_RASTER_BIG_BOX pixels is rasterised by its thread, a larger one is appended to a list in the workspace;
+ * (4) a grid of fixed size strides over that list, whose length it reads from device memory, in tiles of 16 x 16 pixels, one
+ * pixel per thread; (5) resolve, one thread per pixel.  The path a face takes is not observable (ns_debug_set
+ * "mesh_raster_big_box" moves the threshold; the bits stay).  F == 0 is one launch: a frame of background, four zeros.
+ * Checked before any launch (NS_E_INVALID): H or W < 1 or > 16384; V or F < 0 or >= 2^31; c2w_host NULL; a non-finite c2w, fx,
+ * fy, cx, cy, near_ or background; fx or fy == 0; near_ <= 0; cull outside 0 .. 2; count_dev NULL; with F > 0 vertices_dev,
+ * faces_dev or workspace_dev NULL; rgb_out without attr_dev; faces_dev, count_dev or workspace_dev not 8-byte aligned.
+ * ns_mesh_raster_workspace_bytes is 0 for a shape that would be refused (and for F == 0, which needs none).  Not part of this:
+ * antialiasing, lighting, textures, near-plane clipping, meshes or frames of 2^31 elements.                                  */
+#define NS_MESH_RASTER_SHARE 1024
+#define NS_MESH_RASTER_BIG_BOX 1024
+int64_t ns_mesh_raster_workspace_bytes(int64_t V, int64_t F, int H, int W);
+int ns_mesh_raster(const float* vertices_dev, int64_t V, const int64_t* faces_dev, int64_t F, const float* attr_dev,
+                   const float* c2w_host, float fx, float fy, float cx, float cy, int H, int W, float near_, int cull,
+                   float background, float* depth_out, int32_t* tri_out, float* rgb_out, int64_t* count_dev,
+                   void* workspace_dev, void* stream);
 
 /* ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
  * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a

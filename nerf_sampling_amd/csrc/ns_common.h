@@ -42,6 +42,8 @@ struct DebugFlags {
   int count_colour_skips;   // 1: the render kernels count the waves that skipped their colour statements (ns_colour_skip_count)
                             // and the chunk steps the K-block-skipping kernel jumped over (ns_kblock_skip_count)
   int kblock_skip;       // 1: launches of the render kernel run its K-block-skipping twin (off by default: measured no faster)
+  int mesh_raster_big_box;  // > 0: ns_mesh_raster hands faces whose clamped bounding box has more pixels than this to its workgroup
+                            // launch; 0 = NS_MESH_RASTER_BIG_BOX (the results are the same bits for every value)
 };
 DebugFlags& debug_flags();
 // The render kernels' skip counters for a 16-bit field launch on `stream`: *counter = NULL unless count_colour_skips is set; then

@@ -124,6 +124,7 @@ int ns_debug_set(const char* name, int value) {
   if (!std::strcmp(name, "hier_chain")) { f.hier_chain = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "no_colour_skip")) { f.no_colour_skip = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "kblock_skip")) { f.kblock_skip = value ? 1 : 0; return NS_OK; }
+  if (!std::strcmp(name, "mesh_raster_big_box") && value >= 0) { f.mesh_raster_big_box = value; return NS_OK; }
   if (!std::strcmp(name, "count_colour_skips")) { f.count_colour_skips = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "prod_tiles") && (value == 0 || value == 4 || value == 5)) { f.prod_tiles = value; return NS_OK; }
   ns::set_error("ns_debug_set: unknown switch or value (%s = %d)", name, value);

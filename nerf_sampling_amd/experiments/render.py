@@ -102,6 +102,11 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               show_default=True,
               help="(not in the reference) --device-mesh queries a vertex's colour looking towards the box centre, or with "
                    "'normal' (it needs --mesh-normals) looking at the surface along its inward normal.")
+@click.option("--device-mesh-eval", "device_mesh_eval", is_flag=True, default=False,
+              help="(not in the reference) --device-mesh also rasterises scene_mesh.ply's mesh from the held-out cameras "
+                   "(ns_mesh_raster) and scores it on the device (nerf_utils.score_mesh_views): mesh_psnr.txt against the "
+                   "photographs, mesh_depth.txt and mesh_iou.txt against the field's depth and opacity, and mesh_rgb/ and "
+                   "mesh_depth/ PNGs -- a number for --mesh-threshold.")
 @click.option("--root", default=os.getcwd(), show_default=True,
               help="Directory holding dataset/ pretrained/ logs/ (the reference uses its package directory).")
 def main(**kw):
@@ -129,6 +134,10 @@ def main(**kw):
                  mesh_bound=kw["mesh_bound"], mesh_min_triangles=kw["mesh_min_triangles"],
                  mesh_keep_largest=kw["mesh_keep_largest"], mesh_normals=kw["mesh_normals"],
                  mesh_colour_view=kw["mesh_colour_view"])
+    if kw["device_mesh_eval"]:
+        if not kw["device_mesh"]:
+            raise click.UsageError("--device-mesh-eval scores the mesh of --device-mesh")
+        k["device_mesh_eval"] = True
     root = kw["root"]
     datadir, ft_path, depth_net_path = kw["dataset_path"], None, None
     dataset_name = kw["dataset"]

@@ -1437,6 +1437,182 @@ def scene_mesh_shaded(network, bound=1.5, resolution=256, threshold=50.0, colour
     return out
 
 
+# ---- the device mesh seen from the held-out cameras and scored where it is made (ns_mesh_raster) ----
+def format_mesh_txt(label, values, avg) -> str:
+    """mesh_psnr.txt / mesh_depth.txt / mesh_iou.txt of a set of views, psnr.txt's layout: one "NNN.png, LABEL: x" line per view,
+    then the average"""
+    lines = [f"{i:03d}.png, {label}: {v}\n" for i, v in enumerate(values)]
+    return "".join(lines) + f"Avg of {len(lines)} images:\n{label}: {avg}\n"
+
+
+def _write_mesh_txt(savedir, name, label, values, avg):
+    os.makedirs(savedir, exist_ok=True)
+    with open(os.path.join(savedir, name), "a") as file:           # appended to, as psnr.txt is
+        file.write(format_mesh_txt(label, values, avg))
+
+
+def _mesh_tensors(mesh):
+    if not (isinstance(mesh, dict) and "vertices" in mesh and "faces" in mesh):
+        raise ValueError("mesh: the dict of scene_mesh_shaded (vertices, faces, rgb)")
+    return mesh["vertices"].contiguous(), mesh["faces"].contiguous(), mesh.get("rgb")
+
+
+def render_mesh_views(mesh, poses, hwf, K, near, savedir=None, background=0.0, cull=0, n_buffers=4, workers=4,
+                      compress_level=None):
+    """The mesh of scene_mesh_shaded seen from every pose: ops.mesh_rasterize per view, nothing but the four counters of each
+    view read back.  ``mesh``: that dict (vertices, faces, rgb; rgb None: no colour frames).  ``near``: as ops.mesh_rasterize's,
+    the near bound of the scene.  With ``savedir`` the colour frames go to ``mesh_rgb/NNN.png`` through a FrameWriter and the
+    depth maps to ``mesh_depth/NNN.png`` as write_video writes its disparity: kept in one [n_views, H*W] stack, divided by
+    the maximum over ALL views, which stays on the device (ops.map_max, accumulated; FrameWriter.put_map) -- a pixel without a
+    face has depth 0 and is black.  -> dict(rgb, depth, tri: one device tensor per view (rgb: None per view without colours);
+    n_clipped, n_degenerate, n_invalid, n_covered: one int per view).  A view whose n_clipped is not 0 has a camera inside or
+    too close to the mesh: faces were dropped, not clipped."""
+    vertices, faces, colours = _mesh_tensors(mesh)
+    n_views = len(poses)
+    if n_views == 0:
+        raise ValueError("render_mesh_views: at least one pose")
+    H, W = int(hwf[0]), int(hwf[1])
+    dev = vertices.device
+    workspace = torch.empty((ops.mesh_raster_workspace_bytes(vertices.shape[0], faces.shape[0], H, W),), dtype=torch.uint8,
+                            device=dev)
+    out = {k: [] for k in ("rgb", "depth", "tri", "n_clipped", "n_degenerate", "n_invalid", "n_covered")}
+    import contextlib
+
+    writer_kw = dict(n_buffers=n_buffers, workers=workers, compress_level=compress_level, device=dev)
+    rgb_writer = (FrameWriter(os.path.join(savedir, "mesh_rgb"), H, W, **writer_kw)
+                  if savedir is not None and colours is not None else contextlib.nullcontext())
+    state = max_ws = None
+    if savedir is not None:
+        state = torch.empty((2,), dtype=torch.float32, device=dev)
+        max_ws = torch.empty((max(ops.map_max_workspace_bytes(H * W), 8),), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        with rgb_writer as writer:
+            for k, c2w in enumerate(poses):
+                got = ops.mesh_rasterize(vertices, faces, c2w[:3, :4], H, W, K, near, rgb=colours, background=background,
+                                         cull=cull, workspace=workspace)
+                for name in out:
+                    out[name].append(got[name])
+                if writer is not None:
+                    writer.put(k, got["rgb"])
+                if state is not None:
+                    ops.map_max(got["depth"], state=state, accumulate=k > 0, workspace=max_ws)
+        if savedir is not None:
+            with FrameWriter(os.path.join(savedir, "mesh_depth"), H, W, channels=1, **writer_kw) as writer:
+                for k in range(n_views):
+                    writer.put_map(k, out["depth"][k], denom=state[:1])        # the divisor stays where it is
+    return out
+
+
+def _field_map_renderer(kw, H, W, K, dev):
+    """``render(c2w)`` -> (depth [H*W], acc [H*W]) of the field seen from a camera: the one-call renderer evaluate_views would
+    take for the configuration ``kw``, asked for its "depth" and "acc" extras -- the expected depth sum w_i z_i in the unit
+    ns_mesh_raster writes, and the opacity before the background.  A configuration that is neither renderer's: ValueError."""
+    render_frame = _one_call_frame_renderer(kw, H, W, K, dev)
+    if render_frame is None:
+        raise ValueError("score_mesh_views: the field's depth and opacity maps come from the one-call renderers, and this "
+                         "configuration is neither's; pass field_depths and field_accs")
+    trainer = kw["trainer"]
+    workspace = ops.RenderWorkspace()
+    gen = None
+
+    def draw(shape, normal=False):
+        nonlocal gen
+        if gen is None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(0)
+        return (torch.randn if normal else torch.rand)(shape, device=dev, generator=gen)
+
+    def render(c2w):
+        if trainer.use_full_nerf:
+            fine, perturb, n_imp = kw.get("network_fine"), float(kw.get("perturb", 0.0)), int(trainer.N_importance)
+            t_rand = draw([H * W, int(kw["N_samples"])]) if perturb > 0.0 else None
+            u = draw([H * W, n_imp]) if perturb != 0.0 and n_imp > 0 else None
+            out = ops.render_rays_hierarchical(kw["network_fn"].packed(), fine.packed() if (fine is not None and n_imp > 0) else None,
+                                               camera=(H, W, K, c2w, 0, H), n_coarse=int(kw["N_samples"]), n_importance=n_imp,
+                                               lindisp=bool(kw.get("lindisp", False)), white_bkgd=bool(kw["white_bkgd"]),
+                                               near=float(kw["near"]), far=float(kw["far"]), t_rand=t_rand, u=u,
+                                               extras=("depth", "acc"), device=dev, workspace=workspace)
+        else:
+            net = kw.get("network_fine") if kw.get("network_fine") is not None else kw.get("network_fn")
+            noise = None
+            if trainer.sampling_mode == "gaussian" and int(trainer.n_depth_samples) > 1:
+                noise = draw([H * W, int(trainer.n_depth_samples) - 1], normal=True)
+            out = _depthnet_one_call(kw["depth_network"], net, trainer, camera=(H, W, K, c2w, 0, H), extras=("depth", "acc"),
+                                     device=dev, noise=noise, workspace=workspace)
+        return out["depth"], out["acc"]
+
+    return render
+
+
+def score_mesh_views(dataset, image_ids, poses, hwf, K, mesh, near, field_depths=None, field_accs=None, render_kwargs=None,
+                     savedir=None, cull=0, background=None, frames=False):
+    """The mesh of scene_mesh_shaded scored against the photographs and against the field it was cut from, per held-out view,
+    nothing per pixel leaving the device.  Every pose is rasterised (render_mesh_views; ``background`` None: white where the
+    dataset is ``white_bkgd``, black otherwise -- a dataset of images that were blended before the upload does not know, and
+    the caller says 1.0 or 0.0) and gets three numbers:
+      mesh_psnr       the mesh's colour frame against image ``image_ids[k]`` of ``dataset`` (DeviceRayDataset.image_sqerr);
+      depth_mse       the mesh's depth against the field's expected depth of the same rays, over all H * W pixels
+                      (ops.depth_sqerr with one sample per ray; an empty pixel is 0 in both);
+      silhouette_iou  |tri >= 0 and acc > 0.5| / |tri >= 0 or acc > 0.5| (1 where both are empty).
+    The field's maps are ``field_depths`` / ``field_accs`` (one [H*W] device tensor per view, both or neither), or are rendered
+    here from ``render_kwargs`` by the one-call renderer of that configuration with extras=("depth", "acc").  One read-back for
+    the whole call, beside render_mesh_views' counters.  ``savedir`` gets mesh_psnr.txt, mesh_depth.txt and mesh_iou.txt in
+    psnr.txt's format, and with ``frames`` also render_mesh_views' mesh_rgb/ and mesh_depth/ PNGs.  -> dict(mesh_psnr, depth_mse, silhouette_iou:
+    float64 [n]; avg_mesh_psnr, avg_depth_mse, avg_silhouette_iou; n_clipped: per view; views: render_mesh_views' dict;
+    field_depths, field_accs: the maps used)."""
+    import numpy as np
+
+    ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
+    if len(ids) == 0 or len(ids) != len(poses):
+        raise ValueError(f"{len(ids)} image ids for {len(poses)} poses (at least one view)")
+    if (field_depths is None) != (field_accs is None):
+        raise ValueError("score_mesh_views: field_depths and field_accs come together")
+    if field_depths is None and render_kwargs is None:
+        raise ValueError("score_mesh_views: the field's maps (field_depths, field_accs) or render_kwargs to render them")
+    if field_depths is not None and not (len(field_depths) == len(ids) == len(field_accs)):
+        raise ValueError(f"{len(field_depths)} field depths and {len(field_accs)} opacities for {len(ids)} views")
+    if mesh.get("rgb") is None:
+        raise ValueError("score_mesh_views: the mesh has no colours (scene_mesh_shaded(colours=True))")
+    H, W = int(hwf[0]), int(hwf[1])
+    if (H, W) != (dataset.H, dataset.W):
+        raise ValueError(f"hwf says {H} x {W}, the dataset's images are {dataset.H} x {dataset.W}")
+    dev = dataset.device
+    n = len(ids)
+    if background is None:
+        background = 1.0 if dataset.white_bkgd else 0.0
+    if frames and savedir is None:
+        raise ValueError("score_mesh_views(frames=True) writes the PNGs under savedir: savedir is required")
+    views = render_mesh_views(mesh, poses, hwf, K, near, savedir=savedir if frames else None, background=float(background),
+                              cull=cull)
+    render = _field_map_renderer(render_kwargs, H, W, K, dev) if field_depths is None else None
+    sums = torch.empty((4, n), dtype=torch.float64, device=dev)       # squared colour error, squared depth error, |and|, |or|
+    depth_ws = torch.empty((ops.depth_sqerr_workspace_bytes(H * W, 1),), dtype=torch.uint8, device=dev)
+    depths, accs = [], []
+    with torch.no_grad():
+        for k, (img, c2w) in enumerate(zip(ids, poses)):
+            depth, acc = (field_depths[k], field_accs[k]) if render is None else render(c2w[:3, :4])
+            depth, acc = depth.reshape(-1).contiguous(), acc.reshape(-1)
+            depths.append(depth)
+            accs.append(acc)
+            dataset.image_sqerr(img, views["rgb"][k], out=sums[0], slot=k)
+            ops.depth_sqerr(views["depth"][k], depth, out=sums[1], slot=k, workspace=depth_ws)
+            solid, seen = acc > 0.5, views["tri"][k] >= 0
+            sums[2, k] = (solid & seen).sum()
+            sums[3, k] = (solid | seen).sum()
+    sums = sums.cpu().numpy()                                                 # the one device-to-host copy
+    psnrs = dataset.psnr_from_sqerr(sums[0], 3 * H * W)
+    mses = ops.mse_from_sqerr(sums[1], H * W)
+    ious = np.where(sums[3] > 0, sums[2] / np.maximum(sums[3], 1.0), 1.0)
+    out = dict(mesh_psnr=psnrs, depth_mse=mses, silhouette_iou=ious, avg_mesh_psnr=float(np.mean(psnrs)),
+               avg_depth_mse=float(np.mean(mses)), avg_silhouette_iou=float(np.mean(ious)), n_clipped=views["n_clipped"],
+               views=views, field_depths=depths, field_accs=accs)
+    if savedir is not None:
+        _write_mesh_txt(savedir, "mesh_psnr.txt", "PSNR", psnrs, out["avg_mesh_psnr"])
+        _write_mesh_txt(savedir, "mesh_depth.txt", "MSE", mses, out["avg_depth_mse"])
+        _write_mesh_txt(savedir, "mesh_iou.txt", "IoU", ious, out["avg_silhouette_iou"])
+    return out
+
+
 def create_nerf(args, model):
     """(render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer) -- nerf_utils.py:393-494."""
     embed_fn, input_ch = run_nerf_helpers.get_embedder(args.multires, args.i_embed, args.input_dims_embed)

@@ -525,6 +525,68 @@ def mesh_normals(sigma, iso, h, keys, workspace=None):
     return {"normals": normals.reshape(tuple(keys.shape) + (3,)), "n_degenerate": n_degenerate, "n_invalid": n_invalid}
 
 
+def mesh_raster_workspace_bytes(n_vertices: int, n_faces: int, H: int, W: int) -> int:
+    """ns_mesh_raster_workspace_bytes: the z-buffer words, projected vertices and face list ``mesh_rasterize`` needs (0: a shape
+    it refuses, or no face)"""
+    return int(_lib.load().ns_mesh_raster_workspace_bytes(int(n_vertices), int(n_faces), int(H), int(W)))
+
+
+def mesh_rasterize(vertices, faces, c2w, H, W, K, near, rgb=None, background=0.0, cull=0, workspace=None):
+    """ns_mesh_raster: a mesh rasterised from the pinhole camera (H, W, K, c2w) of ``get_rays``, on the device -- a z-buffer frame
+    that sits on the field's: pixel (i, j) is the ray through (i - cx) / fx, and ``depth`` is the one-call renderers' ``depth``
+    extra's unit (the ray parameter along the unnormalised direction).  ``vertices``: fp32 contiguous [V,3] on the device;
+    ``faces``: int64 contiguous [F,3] there, as ``mesh_weld`` returns them; ``rgb``: fp32 contiguous [V,3] vertex colours, or
+    None (no colour frame).  ``near`` > 0: a face with a vertex nearer than that (or behind the camera, or farther than 2^20
+    pixels off the axis) is dropped and counted -- there is no near-plane clipping.  ``cull``: 0 none, 1 back faces, 2 front
+    faces (front: ``mesh_extract``'s outward winding seen from outside).  ``workspace``: a contiguous 8-byte-aligned device
+    tensor of at least ``mesh_raster_workspace_bytes(V, F, H, W)`` bytes (None: allocated); what it holds does not matter.
+    Returns dict(depth fp32 [H*W]: 0 where no face is; tri int32 [H*W]: the face seen, -1 where none; rgb fp32 [H*W,3] or None:
+    the colours interpolated perspective-correctly, ``background`` where no face is; n_clipped; n_degenerate: faces of zero
+    area on the screen; n_invalid: faces with an index outside [0, V); n_covered: pixels with a face) after ONE readback of
+    the four counters; the frames stay on the device.  The same bits on every call.  What is wrong with the arguments raises
+    ValueError before any launch."""
+    if not (isinstance(vertices, Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2
+            and vertices.shape[1] == 3 and vertices.is_contiguous()):
+        raise ValueError("vertices: a contiguous float32 device tensor [V,3]")
+    dev = vertices.device
+    if not (isinstance(faces, Tensor) and faces.device == dev and faces.dtype == torch.int64 and faces.dim() == 2
+            and faces.shape[1] == 3 and faces.is_contiguous()):
+        raise ValueError("faces: a contiguous int64 tensor [F,3] on vertices' device")
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if rgb is not None and not (isinstance(rgb, Tensor) and rgb.device == dev and rgb.dtype == torch.float32
+                                and tuple(rgb.shape) == (V, 3) and rgb.is_contiguous()):
+        raise ValueError(f"rgb: a contiguous float32 tensor ({V}, 3) on vertices' device, or None")
+    H, W, cull = int(H), int(W), int(cull)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"H and W must lie in [1, 16384], got {H} x {W}")
+    if V >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"V = {V} and F = {F} must be below 2^31")
+    if cull not in (0, 1, 2):
+        raise ValueError(f"cull: 0 (none), 1 (back faces) or 2 (front faces), got {cull}")
+    near, background = float(np.float32(near)), float(np.float32(background))
+    if not (np.isfinite(near) and near > 0.0):
+        raise ValueError("near must be finite and positive")
+    if not np.isfinite(background):
+        raise ValueError("background must be finite")
+    c2w_h = _c2w_host(c2w)
+    cam = [float(np.float32(v)) for v in (K[0][0], K[1][1], K[0][2], K[1][2])]
+    if not (np.isfinite(c2w_h).all() and np.isfinite(cam).all() and cam[0] != 0.0 and cam[1] != 0.0):
+        raise ValueError("c2w and K must be finite, fx and fy not 0")
+    workspace = _scratch(workspace, mesh_raster_workspace_bytes(V, F, H, W), dev, "vertices")
+    depth = torch.empty((H * W,), dtype=torch.float32, device=dev)
+    tri = torch.empty((H * W,), dtype=torch.int32, device=dev)
+    frame = torch.empty((H * W, 3), dtype=torch.float32, device=dev) if rgb is not None else None
+    counters = torch.empty((4,), dtype=torch.int64, device=dev)
+    # an empty vertex tensor has no address, and the entry asks for one wherever there are faces (all of them invalid, then)
+    vertex_ptr = _ptr(vertices) if V > 0 else _ptr(counters)
+    check(_lib.load().ns_mesh_raster(vertex_ptr, V, _ptr(faces), F, _ptr(rgb), c2w_h.ctypes.data_as(C.c_void_p), *cam, H, W,
+                                     near, cull, background, _ptr(depth), _ptr(tri), _ptr(frame), _ptr(counters),
+                                     _ptr(workspace), _stream(dev)), "ns_mesh_raster")
+    n_clipped, n_degenerate, n_invalid, n_covered = (int(v) for v in counters.cpu())     # the one readback
+    return {"depth": depth, "tri": tri, "rgb": frame, "n_clipped": n_clipped, "n_degenerate": n_degenerate,
+            "n_invalid": n_invalid, "n_covered": n_covered}
+
+
 def mesh_select(vertices, faces, labels, keep, extras=()):
     """The part of a mesh whose components are kept -- plain torch on whatever device the tensors live on, no kernel of this
     library.  ``vertices`` [V,...], ``faces`` int64 [F,3], ``labels`` [V] as ``mesh_components`` returns them, ``keep`` bool [V],

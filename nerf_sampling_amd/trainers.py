@@ -48,7 +48,8 @@ class Trainer:
                  cloud_min_weight: float = 0.0, cloud_points: Optional[int] = None, device_frames: bool = False,
                  device_video: bool = False, device_mesh: bool = False, mesh_resolution: int = 256,
                  mesh_threshold: float = 50.0, mesh_bound: float = 1.5, mesh_min_triangles: int = 0,
-                 mesh_keep_largest: int = 0, mesh_normals: bool = False, mesh_colour_view: str = "centre"):
+                 mesh_keep_largest: int = 0, mesh_normals: bool = False, mesh_colour_view: str = "centre",
+                 device_mesh_eval: bool = False):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -134,6 +135,15 @@ class Trainer:
             raise ValueError(f"mesh_colour_view: 'centre' or 'normal', got {mesh_colour_view!r}")
         if mesh_colour_view == "normal" and not self.mesh_normals:
             raise ValueError("mesh_colour_view='normal' looks along the vertex normals: it needs mesh_normals=True")
+        # device_mesh_eval (default off; it needs device_mesh): after scene_mesh.ply is written, render(render_test=True) rasterises
+        # the mesh from the held-out cameras (ns_mesh_raster) and scores it where it is made (nerf_utils.score_mesh_views):
+        # mesh_psnr.txt against the photographs, mesh_depth.txt and mesh_iou.txt against the field's own depth and opacity maps
+        # -- a number for mesh_threshold and for what the component filter dropped.  Off: no launch, no file, no changed byte.
+        if not isinstance(device_mesh_eval, (bool, np.bool_)):
+            raise ValueError(f"device_mesh_eval must be a bool, got {device_mesh_eval!r}")
+        self.device_mesh_eval = bool(device_mesh_eval)
+        if self.device_mesh_eval and not self.device_mesh:
+            raise ValueError("device_mesh_eval scores the mesh of device_mesh: it needs device_mesh=True")
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -266,6 +276,20 @@ class Trainer:
                     filtered += f"; normals, {mesh['n_degenerate_normals']} degenerate"
                 print(f"scene mesh: {mesh['faces'].shape[0]} triangles on {mesh['vertices'].shape[0]} vertices at density "
                       f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped{filtered}), written to {testsavedir}")
+                if self.device_mesh_eval:
+                    if not render_test or self.render_factor != 0:
+                        raise ValueError("device_mesh_eval scores the mesh against the held-out photographs at the dataset's "
+                                         "size: it needs render_test and render_factor 0")
+                    ds, ids = self._ray_dataset, i_test
+                    if ds is None:      # called on its own: the test views alone go to the device
+                        ds, ids = ops.ray_dataset(np.asarray(images, dtype=np.float32), render_poses, self.K, [0]), range(len(i_test))
+                    scored = nerf_utils.score_mesh_views(ds, ids, render_poses, hwf, self.K, mesh,
+                                                         float(render_kwargs_test["near"]), render_kwargs=render_kwargs_test,
+                                                         savedir=testsavedir,
+                                                         background=1.0 if render_kwargs_test["white_bkgd"] else 0.0)
+                    print(f"scene mesh from {len(scored['mesh_psnr'])} held-out views: PSNR {scored['avg_mesh_psnr']:.3f} dB, "
+                          f"depth MSE against the field {scored['avg_depth_mse']:.3e}, silhouette IoU "
+                          f"{scored['avg_silhouette_iou']:.4f}, {sum(scored['n_clipped'])} faces dropped at the near plane")
             if self.device_eval and render_test and self.render_factor == 0:
                 ds, ids = self._ray_dataset, i_test
                 if ds is None:          # called on its own: the test views alone go to the device
