@@ -433,13 +433,13 @@ struct Trig {
   __device__ __forceinline__ float operator()(int level, int h) const {
     const float scale = __builtin_ldexpf(1.0f, level);
     const float a = r.hi * scale;                    // exact (power of two)
-    float f = __builtin_amdgcn_fractf(a);            // exact, in [0, 1)
+    float f = __builtin_amdgcn_fractf(a);            // in [0, 1); exact but for -1/2 < a < 0, where 1 - |a| rounds to 2^-24
     const float lo = r.lo * scale + 0.25f * static_cast<float>(h);
     if constexpr (!PRECISE) {
       return __builtin_amdgcn_sinf(f + lo);          // v_sin_f32 takes revolutions
     } else {
-      f = (f >= 0.5f ? f - 1.0f : f) + lo;           // [-0.5, 0.75)
-      f = f > 0.5f ? f - 1.0f : f;                   // [-0.5, 0.5]
+      f = (f >= 0.5f ? f - 1.0f : f) + lo;           // [-0.5 - |r.lo| scale, 0.5 + 0.25 h): below 1 for h <= 2 (ns_tangent.h)
+      f = f > 0.5f ? f - 1.0f : f;                   // [-0.5 - |r.lo| scale, 0.5]: |g| <= 0.25 below
       const float g = (f > 0.25f ? 0.5f - f : (f < -0.25f ? -0.5f - f : f));  // sin(pi - x) = sin x
       const float x = g * 6.283185307179586f;
       const float x2 = x * x;

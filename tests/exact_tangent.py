@@ -56,6 +56,8 @@ write_jacobian:
       e_dq = inv (e_ddepth + |dacc| e_q + q e_dacc + 2u (|ddepth| + |q dacc|)) + |dq| (rel_inv + u)
   disp = rcp(max(1e-10, q)): rel_disp = e_q / q + 2u;  d disp = -disp^2 dq:  disp^2 e_dq + |d disp| (2 rel_disp + 2u); where
   q is within e_q of 1e-10 the branch may differ and the whole |disp^2 dq| is allowed.
+Two inputs per sample and colour channel, zero on these fields (tests/exact_tangent_probes.py sets them): e_raw_c and e_draw_c,
+what the kernel's raw_c and d raw_c may differ by from the tables; they enter c, c (1 - c) and dc to first order (jacobian64).
 Every entry is held to at least DENORMAL_FLOOR (composite_backward_bounds.py).  No constant is fitted to a kernel.
 One sample per ray (raw2outputs' N == 1 rule): |d rgb - ref| <= 6u |ref| + |d raw| E, E = 4u c the IEEE sigmoid's bound.
 
@@ -500,9 +502,10 @@ def _rows(net, ray, z):
     return ray[:, None] * K + k
 
 
-def samples64(net, case, mutant=None):
+def samples64(net, case, mutant=None, e_raw=None, e_draw=None):
     """Per sample of the finite-mean rays of `case`: z, dz, raw [R, N, 4] (r, g, b, sigma), draw = dz G, dist, ddist, and the
-    rays' |d|; `keep`: the indices of those rays in the case."""
+    rays' |d|; `keep`: the indices of those rays in the case.  e_raw, e_draw [P, 3]: what the kernel's raw_c and d raw_c / d z
+    of a pool row may differ by from net["raw"] and net["G"] (default: nothing, the exact fields); returned per sample."""
     keep = np.flatnonzero(np.isfinite(case["mean"]))
     ray, m, N = case["ray"][keep], case["mean"][keep], case["N"]
     z, dz, rank = place64(m, N, net["step"], mutant)
@@ -516,7 +519,9 @@ def samples64(net, case, mutant=None):
         ddist = np.zeros_like(ddist)
     if mutant == "ddist_last":
         ddist[:, -1] = -dz[:, -1] * nrm
-    return dict(keep=keep, ray=ray, mean=m, rank=rank, ray_d=net["rays"]["d"][ray], z=z, dz=dz, raw=raw, draw=draw, dist=dist, ddist=ddist, nrm=nrm)
+    zero = np.zeros(rows.shape + (3,))
+    return dict(keep=keep, ray=ray, mean=m, rank=rank, ray_d=net["rays"]["d"][ray], z=z, dz=dz, raw=raw, draw=draw, dist=dist, ddist=ddist, nrm=nrm,
+                e_raw=zero if e_raw is None else e_raw[rows], e_draw=zero if e_draw is None else e_draw[rows] * dz[..., None])
 
 
 # ---- the reference and the bound ------------------------------------------------------------------------------------
@@ -524,14 +529,16 @@ def _sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def jacobian64(net, case, mutant=None, instance="f16x3"):
+def jacobian64(net, case, mutant=None, instance="f16x3", e_raw=None, e_draw=None):
     """The float64 reference of a case's finite-mean rays: dict J [R, 6] (d r, g, b, disp, depth, acc / d m), out [R, 6] (the
     maps themselves), bound [R, 6] (the error model of the head of this file), keep (their indices in the case), and the
-    facts `applies` reads.  `mutant`: one of MUTANTS, a fault of the reference."""
+    facts `applies` reads.  `mutant`: one of MUTANTS, a fault of the reference.  e_raw, e_draw: see samples64; they enter c,
+    c (1 - c) and dc to first order, the slope of the sigmoid taken at its largest within e_raw (|sigmoid''| <= 0.1):
+    e_c = E_SIG + (c (1 - c) + 0.1 e_raw) e_raw,  e_cc += |1 - 2c| (e_c - E_SIG) + (e_c - E_SIG)^2,  e_dc += (cc + e_cc) e_draw."""
     N, white = case["N"], case["white"]
     if N == 1:
-        return _single64(net, case, mutant)
-    S = samples64(net, case, mutant)
+        return _single64(net, case, mutant, e_raw, e_draw)
+    S = samples64(net, case, mutant, e_raw, e_draw)
     R = len(S["ray"])
     sg, dsg = S["raw"][..., 3], S["draw"][..., 3]
     z, dz, dist, ddist = S["z"], S["dz"], S["dist"], S["ddist"]
@@ -557,8 +564,9 @@ def jacobian64(net, case, mutant=None, instance="f16x3"):
     rounds = (s != 0).astype(np.float64)                     # a factor that is not exactly 1 rounds the product once
     e_D = 9 * U * (np.abs(A) + np.abs(B)) + U * np.abs(D)
     e_dalpha = e_exp * np.abs(D) + e * e_D + U * np.abs(dalpha)
-    e_cc = E_SIG * np.abs(1.0 - 2.0 * c) + 2 * U * cc
-    e_dc = e_cc * np.abs(S["draw"][..., :3]) + U * np.abs(dc)
+    e_c_raw = (cc + 0.1 * S["e_raw"]) * S["e_raw"]                  # 0 on the exact fields
+    e_cc = E_SIG * np.abs(1.0 - 2.0 * c) + 2 * U * cc + np.abs(1.0 - 2.0 * c) * e_c_raw + e_c_raw ** 2
+    e_dc = e_cc * np.abs(S["draw"][..., :3]) + U * np.abs(dc) + (cc + e_cc) * S["e_draw"]
 
     zero = np.zeros(R)
     T, dT, relT, e_dT = np.ones(R), zero.copy(), np.full(R, U), zero.copy()
@@ -610,7 +618,7 @@ def jacobian64(net, case, mutant=None, instance="f16x3"):
         e_dw = T * eda + np.abs(Tda) * relT + al * e_dT + np.abs(dT) * ea + 2 * U * (np.abs(Tda) + np.abs(adT))
         x = np.concatenate([c[ar, jj], zz[:, None], np.ones((R, 1))], axis=1)                      # [R, 5]
         dx = np.concatenate([dc[ar, jj], zd[:, None], np.zeros((R, 1))], axis=1)
-        e_x = np.concatenate([np.full((R, 3), E_SIG), np.zeros((R, 2))], axis=1)
+        e_x = np.concatenate([E_SIG + e_c_raw[ar, jj], np.zeros((R, 2))], axis=1)
         e_dx = np.concatenate([e_dc[ar, jj], np.zeros((R, 2))], axis=1)
         t1, t2 = x * dw[:, None], w[:, None] * dx
         e_t = e_x * np.abs(dw)[:, None] + x * e_dw[:, None] + np.abs(w)[:, None] * e_dx + np.abs(dx) * e_w[:, None] \
@@ -674,7 +682,7 @@ def jacobian64(net, case, mutant=None, instance="f16x3"):
                 T=Tfull, samples=S)
 
 
-def _single64(net, case, mutant=None):
+def _single64(net, case, mutant=None, e_raw=None, e_draw=None):
     """raw2outputs' N == 1 rule at z = m, unclipped, dz = 1: rgb = sigmoid(raw), d rgb = c (1 - c) d raw, everything else 0."""
     keep = np.flatnonzero(np.isfinite(case["mean"]))
     ray, m = case["ray"][keep], case["mean"][keep]
@@ -686,6 +694,11 @@ def _single64(net, case, mutant=None):
     J[:, :3] = c * _sigmoid(-raw[:, :3]) * G[:, :3]
     out[:, :3], out[:, 3] = c, 1e10
     bound[:, :3] = 6 * U * np.abs(J[:, :3]) + np.abs(G[:, :3]) * 4 * U * c
+    if e_raw is not None:
+        cc = c * _sigmoid(-raw[:, :3])
+        e_c = (cc + 0.1 * e_raw[rows]) * e_raw[rows]
+        e_cc = np.abs(1.0 - 2.0 * c) * e_c + e_c ** 2
+        bound[:, :3] += e_cc * np.abs(G[:, :3]) + (cc + e_cc + 4 * U * c) * e_draw[rows]
     bound = np.maximum(bound, DENORMAL_FLOOR)          # (d disp = d depth = d acc = 0 exactly)
     mag = np.zeros((R, 6))
     mag[:, :3] = c * _sigmoid(-raw[:, :3]) * net["Gabs"][rows][:, :3]

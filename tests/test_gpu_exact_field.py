@@ -7,8 +7,9 @@ every schedule (generic, generated, four and five tiles) and every input form (e
 tolerance, and no other kernel on the other side of the comparison.  Every comparison is torch.equal on values (-0.0 equals
 0.0, a NaN equals nothing).
 
-What this cannot show is said in DESIGN.md section 5: the rounding of operands that are not exactly representable, the
-sines and cosines of the embedding, compositing and the DepthNet.
+What this cannot show is said in DESIGN.md section 5: the rounding of operands that are not exactly representable,
+compositing and the DepthNet.  The sines and cosines of the embedding, which these networks never read, are held column by
+column in tests/exact_field_probes.py and tests/test_gpu_exact_field_probes.py.
 """
 import numpy as np
 import pytest
