@@ -65,9 +65,12 @@ int ns_device_cu_count(void);
  *                            chunk steps whose MFMAs the K-block-skipping kernel jumped over;
  *   "kblock_skip" 0/1     -- 1: launches the render kernel takes run its K-block-skipping twin instead (same results bit for
  *                            bit; off by default: it measured no faster than the render kernel);
+ *   "kblock_suffix" 0/1/2 -- launches the render kernel takes run its dead-suffix twin instead (same results bit for bit): 0
+ *                            never, 1 on every handle with finite weights, 2 (the initial value) only on handles marked by
+ *                            ns_weights_set_unit_ordered; -1 restores the initial value; "kblock_skip" = 1 wins over it;
  *   "mesh_raster_big_box" n >= 0 -- ns_mesh_raster's faces whose clamped bounding box has more than n pixels take its workgroup
  *                            launch; 0 = NS_MESH_RASTER_BIG_BOX.
- * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES, NS_KBLOCK_SKIP), read once at first use. */
+ * Initial values come from the environment (NS_OB16_GENERIC, NS_OB16_TILES, NS_KBLOCK_SKIP, NS_KBLOCK_SUFFIX), read once at first use. */
 int ns_debug_set(const char* name, int value);
 /* Waves that skipped the colour layers in the LAST bf16 / f16 radiance-field launch on the current device that ran with
  * "count_colour_skips" set: 0 when that launch ran another kernel than the render kernel, and before any such launch.
@@ -77,6 +80,9 @@ int ns_colour_skip_count(int64_t* waves_out);
  * the LAST such launch with "count_colour_skips" set: 0 when it did not run the K-block-skipping render kernel.  Waits for the
  * device.                                                                                                          */
 int ns_kblock_skip_count(int64_t* steps_out);
+/* The same for the dead-suffix render kernel: chunk steps absent from the bodies its waves ran, i.e. sub-blocks x trailing dead
+ * K-blocks per statement; 0 when the launch did not run that kernel.  Waits for the device.                           */
+int ns_kblock_suffix_count(int64_t* steps_out);
 
 /* ---- a1  get_rays + prepare_rays  (run_nerf_helpers.py:187-202, nerf_utils.py:156-188) ----
  * Pixel rows [row0,row1) of an HxW pinhole camera, row-major.  c2w is 12 HOST floats (3x4,
@@ -515,6 +521,9 @@ int ns_pack_nerf_host_image(int D, int W, uint32_t skip_mask, int use_viewdirs, 
                             const float* const* b, int dtype, int sigma_first, void* stream_out, int64_t stream_cap,
                             float* bias_out, int64_t bias_cap, int64_t* stream_bytes, int64_t* bias_floats);
 void ns_weights_destroy(ns_weights* w);
+/* Tells the dispatch that the caller packed the handle's hidden units in descending firing rate (NeRF.packed() does, for the
+ * production 16-bit fields): a hint for the choice of kernel ("kblock_suffix" = 2), never for results.                 */
+int ns_weights_set_unit_ordered(ns_weights* w, int unit_ordered);
 /* bytes of the device weight stream (for roofline accounting) */
 int64_t ns_weights_stream_bytes(const ns_weights* w);
 

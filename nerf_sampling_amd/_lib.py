@@ -113,6 +113,7 @@ SIGNATURES = {
     "ns_debug_set": (_i, [C.c_char_p, _i]),
     "ns_colour_skip_count": (_i, [C.POINTER(_i64)]),
     "ns_kblock_skip_count": (_i, [C.POINTER(_i64)]),
+    "ns_kblock_suffix_count": (_i, [C.POINTER(_i64)]),
     "ns_get_rays": (_i, [_i, _i, _f, _f, _f, _f, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "ns_ray_batch_gather": (_i, [C.POINTER(RayDataset), _p, _i, _p, _i64, _p, _p, _p, _p, _p]),
     "ns_ray_batch_draw": (_i, [C.POINTER(RayDataset), _p, _i, _i, _p, C.POINTER(RayDrawParams), C.c_uint64, _i64, _p, _p,
@@ -151,6 +152,7 @@ SIGNATURES = {
     "ns_pack_nerf_host_image": (_i, [_i, _i, C.c_uint32, _i, _i, _p, _p, _i, _i, _p, _i64, _p, _i64, C.POINTER(_i64),
                                      C.POINTER(_i64)]),
     "ns_weights_destroy": (None, [_p]),
+    "ns_weights_set_unit_ordered": (_i, [_p, _i]),
     "ns_weights_stream_bytes": (_i64, [_p]),
     "ns_depthnet_forward": (_i, [_p, _p, _p, _i64, _f, _f, _f, _p, _p]),
     "ns_place_samples": (_i, [_i, _p, _p, _p, _p, _i64, _i, _f, _p, _p, _p]),

@@ -42,12 +42,13 @@ struct DebugFlags {
   int count_colour_skips;   // 1: the render kernels count the waves that skipped their colour statements (ns_colour_skip_count)
                             // and the chunk steps the K-block-skipping kernel jumped over (ns_kblock_skip_count)
   int kblock_skip;       // 1: launches of the render kernel run its K-block-skipping twin (off by default: measured no faster)
+  int kblock_suffix;     // launches of the render kernel run its dead-suffix twin: 0 never, 1 always, 2 (the initial value) on unit-ordered handles
   int mesh_raster_big_box;  // > 0: ns_mesh_raster hands faces whose clamped bounding box has more pixels than this to its workgroup
                             // launch; 0 = NS_MESH_RASTER_BIG_BOX (the results are the same bits for every value)
 };
 DebugFlags& debug_flags();
 // The render kernels' skip counters for a 16-bit field launch on `stream`: *counter = NULL unless count_colour_skips is set; then
-// the current device's two counters (colour-skipping waves, skipped K-block steps), zeroed on `stream` ahead of the launch (ns_colour_skip_count reads the last launch's value).
+// the current device's three counters (colour-skipping waves, skipped K-block steps, the dead-suffix kernel's absent steps), zeroed on `stream` ahead of the launch (ns_colour_skip_count reads the last launch's value).
 int colour_skip_counter(uint32_t** counter, hipStream_t stream);
 // Per-thread launch hint of the one-call renderers (ns_render.cpp): 4 = this call's per-sample outputs are about to be
 // copied to the host while the NEXT call's MLP kernel runs -- the four-tile production kernel leaves 64+ registers of every

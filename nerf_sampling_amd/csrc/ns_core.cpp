@@ -67,6 +67,13 @@ int launch_plan(const char* who, const void* kernel, size_t lds, int64_t work, i
 
 // Diagnostic switches: read from the environment ONCE (first use), changed afterwards only through ns_debug_set -- no
 // getenv on the launch path.
+// the dead-suffix render kernel's initial switch: 2 (unit-ordered handles) -- a measured gain by DESIGN section 6's rule
+// (profiles/r07_kblock_suffix.log); a handle packed in its trained order runs the render kernel as before
+constexpr int kKblockSuffixDefault = 2;
+static int kblock_suffix_initial() {
+  const char* v = std::getenv("NS_KBLOCK_SUFFIX");
+  return (v && v[0] >= '0' && v[0] <= '2') ? v[0] - '0' : kKblockSuffixDefault;
+}
 DebugFlags& debug_flags() {
   static DebugFlags f = [] {
     DebugFlags d{};
@@ -76,13 +83,16 @@ DebugFlags& debug_flags() {
     d.prod_tiles = (v && (v[0] == '4' || v[0] == '5')) ? v[0] - '0' : 0;
     v = std::getenv("NS_KBLOCK_SKIP");
     d.kblock_skip = (v && v[0] == '1') ? 1 : 0;
+    v = std::getenv("NS_KBLOCK_SUFFIX");
+    d.kblock_suffix = kblock_suffix_initial();
     return d;
   }();
   return f;
 }
 
-// The render kernels' skip counters: a diagnostic (ns_debug_set("count_colour_skips", 1)), two uint32 per device -- [0] the waves that
-// skipped their colour statements, [1] the chunk steps whose MFMAs the K-block-skipping kernel jumped over, summed over waves.  Allocated with
+// The render kernels' skip counters: a diagnostic (ns_debug_set("count_colour_skips", 1)), three uint32 per device -- [0] the waves that
+// skipped their colour statements, [1] the chunk steps whose MFMAs the K-block-skipping kernel jumped over, [2] the chunk steps absent
+// from the bodies the dead-suffix kernel's waves ran, summed over waves.  Allocated with
 // hipMalloc by the first counted launch on a device and kept for the life of the process (four bytes, never freed); neither
 // the allocation nor the host read-back in ns_colour_skip_count belongs in a stream capture -- do not set the switch while capturing.
 static std::map<int, uint32_t*> g_skip_counters;
@@ -94,7 +104,7 @@ static uint32_t* skip_counter_of_device(bool create) {
   if (it != g_skip_counters.end()) return it->second;
   if (!create) return nullptr;
   uint32_t* p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), 2 * sizeof(uint32_t)) != hipSuccess) return nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&p), 3 * sizeof(uint32_t)) != hipSuccess) return nullptr;
   g_skip_counters[dev] = p;
   return p;
 }
@@ -103,7 +113,7 @@ int colour_skip_counter(uint32_t** counter, hipStream_t stream) {
   if (!debug_flags().count_colour_skips) return NS_OK;
   uint32_t* p = skip_counter_of_device(true);
   if (!p) { set_error("colour_skip_counter: no device memory for the counter"); return NS_E_HIP; }
-  NS_HIP(hipMemsetAsync(p, 0, 2 * sizeof(uint32_t), stream));
+  NS_HIP(hipMemsetAsync(p, 0, 3 * sizeof(uint32_t), stream));
   *counter = p;
   return NS_OK;
 }
@@ -124,6 +134,10 @@ int ns_debug_set(const char* name, int value) {
   if (!std::strcmp(name, "hier_chain")) { f.hier_chain = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "no_colour_skip")) { f.no_colour_skip = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "kblock_skip")) { f.kblock_skip = value ? 1 : 0; return NS_OK; }
+  if (!std::strcmp(name, "kblock_suffix") && value >= -1 && value <= 2) {   // -1: back to the initial value
+    f.kblock_suffix = value < 0 ? ns::kblock_suffix_initial() : value;
+    return NS_OK;
+  }
   if (!std::strcmp(name, "mesh_raster_big_box") && value >= 0) { f.mesh_raster_big_box = value; return NS_OK; }
   if (!std::strcmp(name, "count_colour_skips")) { f.count_colour_skips = value ? 1 : 0; return NS_OK; }
   if (!std::strcmp(name, "prod_tiles") && (value == 0 || value == 4 || value == 5)) { f.prod_tiles = value; return NS_OK; }
@@ -143,6 +157,7 @@ static int read_skip_counter(int which, int64_t* out) {
 }
 int ns_colour_skip_count(int64_t* waves_out) { return read_skip_counter(0, waves_out); }
 int ns_kblock_skip_count(int64_t* steps_out) { return read_skip_counter(1, steps_out); }
+int ns_kblock_suffix_count(int64_t* steps_out) { return read_skip_counter(2, steps_out); }
 int ns_version(void) { return 1; }
 int ns_device_cu_count(void) { return ns::cu_count(); }
 }

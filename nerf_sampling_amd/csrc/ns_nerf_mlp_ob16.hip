@@ -10,10 +10,11 @@
 #include "ns_mlp_engine.h"
 #include "ns_weights.h"
 
-// This file is compiled four times: as itself; with -DNS_OB16_TU_T5 as a second translation unit that holds only the
+// This file is compiled five times: as itself; with -DNS_OB16_TU_T5 as a second translation unit that holds only the
 // five-tile production kernels; with -DNS_OB16_TU_RENDER as a third that holds only the five-tile RENDER kernels,
-// nerf_render_ob16_kernel; and with -DNS_OB16_TU_RENDER -DNS_OB16_TU_KBSKIP as a fourth that holds only the K-BLOCK-SKIPPING
-// render kernels, nerf_kbskip_ob16_kernel (the units build in parallel; each is minutes of register allocation).
+// nerf_render_ob16_kernel; with -DNS_OB16_TU_RENDER -DNS_OB16_TU_KBSKIP as a fourth that holds only the K-BLOCK-SKIPPING
+// render kernels, nerf_kbskip_ob16_kernel; and with -DNS_OB16_TU_RENDER -DNS_OB16_TU_KSUFFIX as a fifth that holds only the
+// DEAD-SUFFIX render kernels, nerf_ksuffix_ob16_kernel (the units build in parallel; each is minutes of register allocation).
 //
 // The render kernel is the five-tile production kernel on the sigma-first weight stream (ns_weights::stream2_dev: same chunks,
 // the tail re-ordered to sigma sub-block | eight colour sub-blocks | rgb head), for launches that composite in the kernel and
@@ -51,11 +52,20 @@
 // OFF by default: ns_debug_set("kblock_skip", 1) (or NS_KBLOCK_SKIP=1) sends the render kernel's launches here.  On the bench frame
 // the kernel skips 12.8 % of its chunk steps and is no faster than the render kernel on the same handle: a skipped step still
 // issues its seven gap instructions, and the mask ORs, tests and branches cost what the skipped MFMAs save.
+//
+// The dead-suffix render kernel (NS_OB16_TU_KSUFFIX) is the K-block-skipping kernel with the statements of
+// ns_ob16_ksuffix_asm.inc (tools/gen_ob16_asm.py --ksuffix): the same masks, but a consumer tests nothing per step -- at its start it
+// takes d = the trailing dead K-blocks of its input's mask (the unit order makes dead blocks a suffix) and runs the straight-line
+// body that lacks those d K-blocks' steps; a dead block above the suffix is computed.  It skips a subset of the steps the
+// K-block-skipping kernel skips, so the bit-identity argument above applies unchanged.  ns_debug_set("kblock_suffix", v) /
+// NS_KBLOCK_SUFFIX: 0 never, 1 every launch the render kernel takes on a kbskip_ok handle, 2 those on handles packed with the
+// unit order (ns_weights_set_unit_ordered); "kblock_skip" = 1 wins over it.
 namespace nsob16 {
 // the field inputs, and what in-kernel placement and compositing takes (ns_comp_epilogue.h)
 struct Nerf16Args : nsmlp::FieldArgs, nsepi::CompFields {
-  uint32_t* skip_count;   // render kernels only: NULL, or two device counters: [0] bumped once per wave that skipped its colour
-                          // statements, [1] (K-block-skipping kernel) by the chunk steps whose MFMAs a wave jumped over
+  uint32_t* skip_count;   // render kernels only: NULL, or three device counters: [0] bumped once per wave that skipped its colour
+                          // statements, [1] (K-block-skipping kernel) by the chunk steps whose MFMAs a wave jumped over, [2] (dead-
+                          // suffix kernel) by the chunk steps absent from the bodies a wave ran
 };
 // the five-tile production kernel (PROD, 80 samples per wave): defined in the NS_OB16_TU_T5 unit
 int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
@@ -63,12 +73,22 @@ int launch_prod_t5(int dtype, bool embedded, Nerf16Args& a, hipStream_t stream);
 int launch_render_t5(int dtype, Nerf16Args& a, hipStream_t stream);
 // the K-block-skipping render kernel (same stream, same launches): defined in the NS_OB16_TU_KBSKIP unit
 int launch_kbskip_t5(int dtype, Nerf16Args& a, hipStream_t stream);
+// the dead-suffix render kernel (same stream, same launches): defined in the NS_OB16_TU_KSUFFIX unit
+int launch_ksuffix_t5(int dtype, Nerf16Args& a, hipStream_t stream);
 }  // namespace nsob16
 
 #if defined(NS_OB16_TU_KBSKIP) && !defined(NS_OB16_TU_RENDER)
 #error "the K-block-skipping unit is a render unit: -DNS_OB16_TU_RENDER -DNS_OB16_TU_KBSKIP"
 #endif
-#ifdef NS_OB16_TU_KBSKIP
+#if defined(NS_OB16_TU_KSUFFIX) && (!defined(NS_OB16_TU_RENDER) || defined(NS_OB16_TU_KBSKIP))
+#error "the dead-suffix unit is a render unit of its own: -DNS_OB16_TU_RENDER -DNS_OB16_TU_KSUFFIX"
+#endif
+#if defined(NS_OB16_TU_KBSKIP) || defined(NS_OB16_TU_KSUFFIX)
+#define NS_OB16_TU_KMASK          // the unit's trunk layers 3..7, sigma and colour hand live masks on (kbs_*_asm_run of its .inc)
+#endif
+#ifdef NS_OB16_TU_KSUFFIX
+#define NS_OB16_KERNEL nerf_ksuffix_ob16_kernel
+#elif defined(NS_OB16_TU_KBSKIP)
 #define NS_OB16_KERNEL nerf_kbskip_ob16_kernel
 #elif defined(NS_OB16_TU_RENDER)
 #define NS_OB16_KERNEL nerf_render_ob16_kernel
@@ -111,6 +131,9 @@ using Ob16Lds = FieldLds<kWaves, T * 3 * 1024, 11 * (T * 64)>;
 #endif
 #ifdef NS_OB16_TU_KBSKIP
 #include "ns_ob16_kbskip_asm.inc"
+#endif
+#ifdef NS_OB16_TU_KSUFFIX
+#include "ns_ob16_ksuffix_asm.inc"
 #endif
 namespace {
 #ifdef NS_OB16_TU_RENDER
@@ -227,8 +250,8 @@ __device__ __forceinline__ void render_rgb_asm(PipeT& ring, const float* bias_ld
 }
 #endif
 
-#ifdef NS_OB16_TU_KBSKIP
-// the statements of ns_ob16_kbskip_asm.inc (five tiles): a trunk layer that returns the live mask of its output K-blocks and
+#ifdef NS_OB16_TU_KMASK
+// the statements of ns_ob16_kbskip_asm.inc / ns_ob16_ksuffix_asm.inc (five tiles): a trunk layer that returns the live mask of its output K-blocks and
 // (KIND > 0) skips the steps of its input's dead ones; sigma and colour as consumers of the trunk's mask
 template <class M, int KIND, bool IN_A, class PipeT>
 __device__ __forceinline__ uint32_t kbs_hidden_layer_asm(PipeT& ring, const float* bias_lds, int g, typename M::Block (&hA)[5][8],
@@ -515,11 +538,15 @@ NS_OB16_KERNEL(Nerf16Args a) {
       static_assert(NKB == 8 && (T == 4 || T == 5) && NWAVES == 4, "the generated streams are W = 256, four or five tiles, four waves");
       hidden_layer_asm<M, T, true, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;    // 1
       hidden_layer_asm<M, T, false, false>(ring, bias, g, hA, hB, xs); bias += NSB * 16;   // 2
-#ifdef NS_OB16_TU_KBSKIP
+#ifdef NS_OB16_TU_KMASK
       // live masks of the tested K-blocks travel from each layer to the next in an SGPR; `dead` counts the steps jumped over
       static_assert(T == 5, "the K-block-skipping statements are five-tile");
       constexpr uint32_t kAll = (1u << kKbsMaskBits) - 1u;
+#ifdef NS_OB16_TU_KSUFFIX
+      auto dead_of = [&](uint32_t m) { return static_cast<uint32_t>(__builtin_ctz(m | (1u << kKbsMaskBits))); };   // the body's d
+#else
       auto dead_of = [&](uint32_t m) { return static_cast<uint32_t>(__builtin_popcount(~m & kAll)); };
+#endif
       uint32_t km = kbs_hidden_layer_asm<M, 0, true>(ring, bias, g, hA, hB, xs, kAll); bias += NSB * 16;    // 3
       kb_dead += NSB * dead_of(km);
       km = kbs_hidden_layer_asm<M, 1, false>(ring, bias, g, hA, hB, xs, km); bias += NSB * 16;             // 4
@@ -595,9 +622,14 @@ NS_OB16_KERNEL(Nerf16Args a) {
       // the sigma-first stream: sigma, then EITHER colour and rgb OR their drain twins (see the file's header comment)
       u32x4 D[T];
       static_for<T>([&](auto t_) { D[decltype(t_)::value] = __builtin_bit_cast(u32x4, vs[decltype(t_)::value].v); });
-#ifdef NS_OB16_TU_KBSKIP
+#ifdef NS_OB16_TU_KMASK
+#ifdef NS_OB16_TU_KSUFFIX
+      const uint32_t dead7 = static_cast<uint32_t>(__builtin_ctz(kb_mask7 | (1u << kKbsMaskBits)));
+#else
+      const uint32_t dead7 = static_cast<uint32_t>(__builtin_popcount(~kb_mask7 & ((1u << kKbsMaskBits) - 1u)));
+#endif
       kbs_sigma_asm<M>(ring, bias, g, hB, D, sigma, kb_mask7); bias += 16;
-      kb_dead += static_cast<uint32_t>(__builtin_popcount(~kb_mask7 & ((1u << kKbsMaskBits) - 1u)));
+      kb_dead += dead7;
 #else
       render_sigma_asm<M, T>(ring, bias, g, hB, D, sigma); bias += 16;
 #endif
@@ -614,9 +646,9 @@ NS_OB16_KERNEL(Nerf16Args a) {
         render_drain_asm_run<M, T, 4>(ring, bias, g);
         static_for<T>([&](auto t_) { last[decltype(t_)::value] = f32x4a{0.0f, 0.0f, 0.0f, 0.0f}; });
       } else {
-#ifdef NS_OB16_TU_KBSKIP
+#ifdef NS_OB16_TU_KMASK
         kbs_colour_asm<M>(ring, bias, g, hB, D, hA, kb_mask7); bias += (NSB / 2) * 16;
-        kb_dead += (NSB / 2) * static_cast<uint32_t>(__builtin_popcount(~kb_mask7 & ((1u << kKbsMaskBits) - 1u)));
+        kb_dead += (NSB / 2) * dead7;
 #else
         render_colour_asm<M, T>(ring, bias, g, hB, D, hA); bias += (NSB / 2) * 16;
 #endif
@@ -650,7 +682,9 @@ NS_OB16_KERNEL(Nerf16Args a) {
     }
     if constexpr (kRenderTU) {
       if (skipped && a.skip_count && le == 0) atomicAdd(a.skip_count, 1u);
-#ifdef NS_OB16_TU_KBSKIP
+#ifdef NS_OB16_TU_KSUFFIX
+      if (kb_dead && a.skip_count && le == 0) atomicAdd(a.skip_count + 2, kb_dead);
+#elif defined(NS_OB16_TU_KBSKIP)
       if (kb_dead && a.skip_count && le == 0) atomicAdd(a.skip_count + 1, kb_dead);
 #endif
     }
@@ -699,6 +733,9 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
         r.stream = static_cast<const char*>(net->stream2_dev); r.bias = net->bias2_dev;
         // the K-block-skipping twin (opt-in): same launches, same stream; a handle with a non-finite weight stays on the render kernel
         if (net->kbskip_ok && ns::debug_flags().kblock_skip) return nsob16::launch_kbskip_t5(M::kDtype, r, stream);
+        // the dead-suffix twin: 1 every such handle, 2 only those packed with the unit order (where dead blocks are a suffix)
+        const int ksuffix = ns::debug_flags().kblock_suffix;
+        if (net->kbskip_ok && (ksuffix == 1 || (ksuffix == 2 && net->unit_ordered))) return nsob16::launch_ksuffix_t5(M::kDtype, r, stream);
         return nsob16::launch_render_t5(M::kDtype, r, stream);
       }
       return nsob16::launch_prod_t5(M::kDtype, EMB, a, stream);
@@ -712,7 +749,12 @@ int dispatch_m(const ns_weights* net, Nerf16Args& a, hipStream_t stream) {
 
 }  // namespace
 
-#if defined(NS_OB16_TU_KBSKIP)
+#if defined(NS_OB16_TU_KSUFFIX)
+int nsob16::launch_ksuffix_t5(int dtype, Nerf16Args& a, hipStream_t stream) {
+  if (dtype == Mma16BF16::kDtype) return launch<Mma16BF16, 8, false, true, 5>(a, stream);
+  return launch<Mma16F16, 8, false, true, 5>(a, stream);
+}
+#elif defined(NS_OB16_TU_KBSKIP)
 int nsob16::launch_kbskip_t5(int dtype, Nerf16Args& a, hipStream_t stream) {
   if (dtype == Mma16BF16::kDtype) return launch<Mma16BF16, 8, false, true, 5>(a, stream);
   return launch<Mma16F16, 8, false, true, 5>(a, stream);

@@ -700,6 +700,12 @@ void ns_weights_destroy(ns_weights* w) {
   delete w;
 }
 
+int ns_weights_set_unit_ordered(ns_weights* w, int unit_ordered) {
+  NS_REQUIRE(w, "null handle");
+  w->unit_ordered = unit_ordered ? 1 : 0;
+  return NS_OK;
+}
+
 int64_t ns_weights_stream_bytes(const ns_weights* w) {
   return w ? static_cast<int64_t>(w->n_slabs) * kSlabBytes : 0;
 }

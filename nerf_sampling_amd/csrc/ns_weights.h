@@ -26,6 +26,8 @@ struct ns_weights {
   void* stream2_dev;
   float* bias2_dev;
   int kbskip_ok;         // 1: every 16-bit weight of the sigma-first stream is finite (the K-block-skipping render kernel may run)
+  int unit_ordered;      // 1: the caller packed the hidden units by firing rate (ns_weights_set_unit_ordered): dead K-blocks are
+                         // mostly a suffix of a layer's output, which the dead-suffix render kernel is built for
 };
 
 enum { NS_KIND_NERF = 0, NS_KIND_DEPTHNET = 1 };

@@ -783,10 +783,12 @@ def _host_ptr_array(tensors: Sequence[Tensor]):
 
 
 def pack_nerf(weights: Sequence[Tensor], biases: Sequence[Tensor], D: int, W: int, skip,
-              dtype: Optional[str] = None, device="cuda", use_viewdirs: bool = True, output_ch: int = 4) -> PackedWeights:
+              dtype: Optional[str] = None, device="cuda", use_viewdirs: bool = True, output_ch: int = 4,
+              unit_ordered: bool = False) -> PackedWeights:
     """weights/biases in the order pts_linears.0..D-1, then feature_linear, alpha_linear, views_linears.0, rgb_linear
     (use_viewdirs) or output_linear (use_viewdirs=False: raw has ``output_ch`` channels).  ``skip``: the reference's
-    ``skips`` list (or one index / -1): layer i + 1 sees cat[x, h] for every i in it."""
+    ``skips`` list (or one index / -1): layer i + 1 sees cat[x, h] for every i in it.  ``unit_ordered``: the caller sorted the
+    hidden units by firing rate (NeRF.packed); marks the handle for the dispatch (ns_weights_set_unit_ordered)."""
     lib = _lib.load()
     skips = [skip] if isinstance(skip, int) else list(skip)
     skips = [int(i) for i in skips if int(i) >= 0]
@@ -805,6 +807,8 @@ def pack_nerf(weights: Sequence[Tensor], biases: Sequence[Tensor], D: int, W: in
     pw = PackedWeights(out.value, "nerf", name, torch.device(device))
     pw.out_ch = int(lib.ns_nerf_out_channels(pw.handle))
     pw.use_viewdirs = bool(use_viewdirs)
+    if unit_ordered:
+        check(lib.ns_weights_set_unit_ordered(pw.handle, 1), "ns_weights_set_unit_ordered")
     return pw
 
 
@@ -1344,7 +1348,9 @@ def render_rays_hierarchical(coarse: PackedWeights, fine: Optional[PackedWeights
 
 class debug_switch:
     """Context manager around ns_debug_set: ``with ops.debug_switch(generic_kernels=1, prod_tiles=4): ...`` (tests compare the
-    kernel variants inside one process); every switch is reset to 0 (= the dispatcher's own choice) on exit."""
+    kernel variants inside one process); every switch is reset to 0 (= the dispatcher's own choice) on exit, ``kblock_suffix`` to its initial value."""
+
+    RESET = {"kblock_suffix": -1}
 
     def __init__(self, **switches):
         self.switches = switches
@@ -1356,7 +1362,7 @@ class debug_switch:
 
     def __exit__(self, *exc):
         for k in self.switches:
-            check(_lib.load().ns_debug_set(k.encode(), 0), "ns_debug_set")
+            check(_lib.load().ns_debug_set(k.encode(), self.RESET.get(k, 0)), "ns_debug_set")
         return False
 
 
@@ -1374,6 +1380,15 @@ def kblock_skip_count() -> int:
     (0 when that launch ran another kernel); waits for the device."""
     n = C.c_int64(0)
     check(_lib.load().ns_kblock_skip_count(C.byref(n)), "ns_kblock_skip_count")
+    return int(n.value)
+
+
+def kblock_suffix_count() -> int:
+    """Chunk steps absent from the bodies the dead-suffix render kernel's waves ran (sub-blocks x trailing dead K-blocks of each
+    statement's input), summed over the waves of the last 16-bit radiance-field launch made under
+    ``debug_switch(count_colour_skips=1)`` (0 when that launch ran another kernel); waits for the device."""
+    n = C.c_int64(0)
+    check(_lib.load().ns_kblock_suffix_count(C.byref(n)), "ns_kblock_suffix_count")
     return int(n.value)
 
 

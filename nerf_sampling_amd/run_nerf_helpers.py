@@ -166,7 +166,7 @@ class NeRF(nn.Module):
                     ws, bs = permute_units(ws, bs, self.unit_orders, skips, self.input_ch)
             self._packed[name] = ops.pack_nerf(ws, bs, self.D, self.W, skips, name,
                                                dev if dev.type == "cuda" else "cuda", use_viewdirs=self.use_viewdirs,
-                                               output_ch=self.output_channels)
+                                               output_ch=self.output_channels, unit_ordered=self.unit_orders is not None)
         return self._packed[name]
 
     unit_order = True                  # False (or NS_NO_UNIT_ORDER=1 in the environment): pack the units in their own order

@@ -1,11 +1,12 @@
-"""Same-box, same-process A/B of the K-block-skipping render kernel against the render kernel, through
-ns_debug_set("kblock_skip"): whole 800 x 800 x 64 bf16 frames, the switch alternating after a warm-up, as tools/ab_colour_skip.py
+"""Same-box, same-process A/B of the K-block-skipping render kernel (--switch kblock_skip, the default) or of the dead-suffix
+render kernel (--switch kblock_suffix; --on-value 2, the default there, takes unit-ordered handles only, so input (c) shows that the
+render kernel runs: its counter reads 0) against the render kernel, through ns_debug_set: whole 800 x 800 x 64 bf16 frames, the switch alternating after a warm-up, as tools/ab_colour_skip.py
 does for the colour skip (a side of a pair is --frames consecutive spiral poses timed between two synchronisations; both sides
 see the same poses).  Three inputs: (a) the bench scene (shapes_fit) packed with the unit order, (b) lego_synth (seeded random
 weights) packed with the unit order, (c) the bench scene packed in its own order -- next to nothing skips there, so the pair shows
 the new kernel's overhead (mask ORs, tests and branches).  Prints per-pair times, the share of chunk steps skipped (the device
 counter, read on an untimed frame), the spread of each side and the verdict of the acceptance rule.
-    python tools/ab_kblock_skip.py [--pairs 6] [--frames 40] [--size 800]"""
+    python tools/ab_kblock_skip.py [--switch kblock_skip|kblock_suffix] [--on-value V] [--pairs 6] [--frames 40] [--size 800]"""
 import argparse
 import copy
 import json
@@ -31,8 +32,12 @@ def main():
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
+    ap.add_argument("--switch", default="kblock_skip", choices=["kblock_skip", "kblock_suffix"], help="the switch that alternates")
+    ap.add_argument("--on-value", type=int, default=None, help="its value on the 'on' side (default: 1 for kblock_skip, 2 for kblock_suffix)")
     a = ap.parse_args()
     assert a.pairs >= 6, "at least six pairs"
+    on_value = a.on_value if a.on_value is not None else {"kblock_skip": 1, "kblock_suffix": 2}[a.switch]
+    counter = {"kblock_skip": ops.kblock_skip_count, "kblock_suffix": ops.kblock_suffix_count}[a.switch]
     dev = torch.device("cuda", 0)
     H = W = a.size
     _, K = synthetic.blender_intrinsics(H, W)
@@ -51,7 +56,7 @@ def main():
         fr = FrameRenderer(H, W, hip_row_renderer(dw, nw, H, W, K, a.samples, "uniform", 0.1, device=dev, events=None), dev)
 
         def frame(first, off):
-            with ops.debug_switch(kblock_skip=int(not off)):
+            with ops.debug_switch(**{a.switch: 0 if off else on_value}):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for k in range(a.frames):
@@ -63,10 +68,10 @@ def main():
         for i in range(a.warmup):
             frame(i, False)
             frame(i, True)
-        with ops.debug_switch(count_colour_skips=1, kblock_skip=1):
+        with ops.debug_switch(count_colour_skips=1, **{a.switch: on_value}):
             fr.render(poses[a.warmup % 40])
             fr.finish()
-            share = ops.kblock_skip_count() / (waves * STEPS_PER_PASS)
+            share = counter() / (waves * STEPS_PER_PASS)
             colour = ops.colour_skip_count() / waves
         on, off = [], []
         for i in range(a.pairs):
@@ -79,7 +84,7 @@ def main():
         med = lambda v: sorted(v)[len(v) // 2] if len(v) % 2 else 0.5 * (sorted(v)[len(v) // 2 - 1] + sorted(v)[len(v) // 2])   # noqa: E731
         gains = [b - c for b, c in zip(off, on)]
         spread = max(max(on) - min(on), max(off) - min(off))
-        res = {"input": label, "pairs": a.pairs, "frames_per_side": a.frames, "steps_skipped": round(share, 4), "waves_skipping_colour": round(colour, 4),
+        res = {"switch": a.switch, "on_value": on_value, "input": label, "pairs": a.pairs, "frames_per_side": a.frames, "steps_skipped": round(share, 4), "waves_skipping_colour": round(colour, 4),
                "median_on_ms": round(med(on), 3), "median_off_ms": round(med(off), 3), "median_gain_ms": round(med(gains), 3),
                "spread_on_ms": round(max(on) - min(on), 3), "spread_off_ms": round(max(off) - min(off), 3),
                "every_pair_favours_skip": all(g > 0 for g in gains), "gain_over_3x_spread": med(gains) >= 3 * spread,

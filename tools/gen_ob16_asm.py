@@ -32,7 +32,8 @@ rule needs it and an independent checker pass re-verifies the final text (tests/
 gen_layer() is the layout in use (one dword converted per chunk step, a three-stage pipeline); gen_layer_q() issues the
 same micro-ops from a queue, one per MFMA gap -- measured 2-4 % slower and kept for that A/B
 (--queue4 / --queue5).  --exp-* flags build timing-only ablations (results wrong on purpose).  --render writes the sigma-first
-tail of the render kernel, --kbskip the statements of its K-block-skipping twin (their sections below).
+tail of the render kernel, --kbskip the statements of its K-block-skipping twin, --ksuffix those of its dead-suffix twin (their
+sections below).
 """
 import argparse
 import os
@@ -1678,11 +1679,12 @@ def gen_kbs(dt, kid, tested=KBS_TESTED):
     return gen_layer_kbs(dt, tested=tested, **kw) if kind == "hidden" else gen_special_kbs(dt, kind, tested)
 
 
-def cpp_kbs(dt, kid, prog):
+def cpp_kbs(dt, kid, prog, ksx=None):
+    """ksx (--ksuffix): the statement's suffix-variant bodies; the struct is then KsxAsm, its text ksx_text() of them"""
     mp, nt = Map5, 5
     mname = {"bf16": "Mma16BF16", "f16": "Mma16F16"}[dt]
     kind, kw = KBS_KINDS[kid]
-    text = "\\n\\t\"\n      \"".join(prog.text())
+    text = "\\n\\t\"\n      \"".join(prog.text() if ksx is None else ksx_text(ksx, len(prog.bits)))
     outs, ins, params = [], [], []
     clobber = list(mp.CLOBBER)
     if kind == "hidden":
@@ -1733,6 +1735,27 @@ def cpp_kbs(dt, kid, prog):
     n_steps = sum(s[0] == "s" for s in prog.segs)
     n_pad = sum(prog.pads.values())
     tail = ", uint32_t kmask" + (", uint32_t& omask" if kind == "hidden" else "")
+    if ksx is not None:
+        if len(ksx) > 1:
+            outs.append('[kd] "=&s"(kd)')
+        mfmas = ", ".join(str(sum(i.kind == "mfma" for i in b)) for b in ksx)
+        return f"""
+// {dt} KIND {kid} ({kind}{'' if kw is None else ' ' + ' '.join(k for k, v in kw.items() if v)}): {prog.slabs} slabs, {len(ksx)} bodies (dead suffix 0..{len(ksx) - 1}) of {mfmas} MFMAs
+template <> struct KsxAsm<{mname}, {kid}> {{
+  static constexpr int kSlabs = {prog.slabs};
+  static constexpr int kBodies = {len(ksx)};
+  static __device__ __forceinline__ void run({', '.join(params + ['u32x4 (&F)[4]'])},
+                                             uint32_t rb0, uint32_t rb1, uint32_t rb2, uint32_t rb3, uint32_t bias, uint32_t loff,
+                                             uint64_t sbase, uint32_t nsl, uint32_t ldsw, uint32_t& islab, uint32_t& dsto{tail}) {{
+    uint32_t keep{', kd' if len(ksx) > 1 else ''};
+    asm volatile(
+      "{text}"
+      : {', '.join(outs)}
+      : {', '.join(ins)}
+      : {', '.join(clob)});
+  }}
+}};
+"""
     return f"""
 // {dt} KIND {kid} ({kind}{'' if kw is None else ' ' + ' '.join(k for k, v in kw.items() if v)}): {prog.slabs} slabs, {n_steps} tested steps, {len(prog.bits)} mask bits, {n_pad} pad wait states for the skip paths
 template <> struct KbsAsm<{mname}, {kid}> {{
@@ -1815,6 +1838,110 @@ def kbs_main(path, tested=KBS_TESTED):
         f.write("".join(out))
 
 
+# --ksuffix: the statements of the dead-suffix render kernel (csrc/ns_ob16_ksuffix_asm.inc).
+#
+# The unit order puts a layer's rarely firing units last, so a wave's dead K-blocks are mostly a SUFFIX of the tested set.  A
+# consumer statement here makes ONE wave-uniform choice at its start -- d = the trailing zero bits of its live mask, 0 .. the
+# number of tested K-blocks -- and runs one of d + 1 straight-line bodies; body d is the K-block-skip program's path for the
+# mask whose last d K-blocks are dead, without the per-step test, branch and jump (ksx_body).  A dead block above the wave's
+# suffix is simply computed.  Everything the --kbskip section says of a path holds for a body: the non-MFMA instructions are
+# the same sequence in every body, so the ring protocol and the wait counts do not depend on the choice, and every body is a
+# producer of its output's live mask.  Leaving out a path's three control instructions shortens its distances, so each body is
+# re-padded on its own (kbs_deficits) and goes through check().
+def ksx_mask(d, nbits):
+    """the live mask of dead suffix d: the low d bits (the LAST d tested K-blocks) clear"""
+    assert 0 <= d <= nbits
+    return ((1 << nbits) - 1) & ~((1 << d) - 1)
+
+
+def ksx_body(prog, d):
+    """body d of a statement: the path of ksx_mask(d) with the pads kbs_repair found for it, less the control instructions, plus
+    the pads their absence makes necessary"""
+    seq = [i for i in prog.linearise(ksx_mask(d, len(prog.bits))) if i is not prog.test and i is not prog.cbr and i is not prog.jmp]
+    missing = {id(i): n for i, n in kbs_deficits(seq)}
+    out = []
+    for i in seq:
+        n = missing.get(id(i), 0)
+        while n > 0:
+            k = min(n, 8)
+            out.append(Ins(f"s_nop {k - 1}", "nop", ws=k))
+            n -= k
+        out.append(i)
+    check(out)
+    return out
+
+
+def ksx_bodies(prog):
+    return [ksx_body(prog, d) for d in range(len(prog.bits) + 1)]
+
+
+def ksx_dispatch(nbits):
+    """the scalar dispatch in front of the bodies: d = trailing zeros of (kmask | 1 << nbits); d = 0 falls through into body 0"""
+    lines = [f"s_or_b32 %[kd], %[kmask], {1 << nbits}", "s_ff1_i32_b32 %[kd], %[kd]"]
+    for d in range(1, nbits + 1):
+        lines += [f"s_cmp_eq_u32 %[kd], {d}", f"s_cbranch_scc1 .Lksd%=_{d}"]
+    return lines
+
+
+def ksx_text(bodies, nbits):
+    if len(bodies) == 1:                 # a producer only: nothing to choose
+        return [i.text for i in bodies[0]]
+    assert len(bodies) == nbits + 1
+    lines = ksx_dispatch(nbits)
+    for d, body in enumerate(bodies):
+        if d:
+            lines.append(f".Lksd%=_{d}:")
+        lines += [i.text for i in body]
+        if d + 1 < len(bodies):
+            lines.append("s_branch .Lksj%=")
+    lines.append(".Lksj%=:")
+    return lines
+
+
+def ksx_verify(prog, bodies):
+    """check() on every body; the non-MFMA, non-pad instructions of every body are body 0's, text for text; a body lacks exactly
+    the MFMAs of its dead suffix"""
+    def protocol(seq):
+        return [i.text for i in seq if i.kind not in ("mfma", "nop")]
+    want = protocol(bodies[0])
+    per_block = sum(s[0] == "s" for s in prog.segs) // max(len(prog.bits), 1)
+    full = sum(i.kind == "mfma" for i in bodies[0])
+    for d, body in enumerate(bodies):
+        check(body)
+        assert protocol(body) == want, f"body {d}: drops or reorders a non-MFMA instruction"
+        assert sum(i.kind == "mfma" for i in body) == full - 5 * per_block * d, f"body {d}: MFMA count"
+    return len(want)
+
+
+KSX_HEADER = """// GENERATED by tools/gen_ob16_asm.py --ksuffix -- do not edit; regenerate with `python tools/gen_ob16_asm.py --ksuffix`.
+// The five-tile statements of the dead-suffix render kernel (ns_nerf_mlp_ob16.hip, NS_OB16_TU_KSUFFIX): trunk layers 3..7, sigma
+// and colour with a live mask of the tested hidden K-blocks; a consumer runs the straight-line body of its mask's trailing dead
+// K-blocks (the generator's --ksuffix section has the rules).  Included after ns_ob16_asm.inc and ns_ob16_render_asm.inc.
+#pragma once
+namespace nsmlp {
+// KIND: 0 layer 3 (producer only), 1 layers 4 / 6, 2 layer 5 (skip), 3 layer 7, 4 sigma, 5 colour
+template <class M, int KIND> struct KsxAsm;
+constexpr uint32_t kKbsMaskBits = <NBITS>;      // live-mask bits: hidden K-block kb of the tested set <TESTED> is bit <BITS>
+"""
+
+
+def ksx_main(path, tested=KBS_TESTED):
+    """--ksuffix: every body of every statement verified (ksx_verify) before the file is written"""
+    bits = ", ".join(f"{kb} -> {kbs_bit(kb, tested)}" for kb in tested)
+    out = [KSX_HEADER.replace("<NBITS>", str(len(tested))).replace("<TESTED>", "{" + ", ".join(map(str, tested)) + "}").replace("<BITS>", bits)]
+    for dt in ("bf16", "f16"):
+        for kid in range(len(KBS_KINDS)):
+            prog = gen_kbs(dt, kid, tested)
+            bodies = ksx_bodies(prog)
+            ksx_verify(prog, bodies)
+            out.append(cpp_kbs(dt, kid, prog, ksx=bodies))
+            print(f"{dt} KIND {kid}: {len(bodies)} bodies, instructions {[len(b) for b in bodies]}, "
+                  f"pads {[sum(i.ws for i in b if i.kind == 'nop') for b in bodies]}", file=sys.stderr)
+    out.append(KBS_FOOTER.replace("KbsAsm", "KsxAsm"))
+    with open(path, "w") as f:
+        f.write("".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "nerf_sampling_amd", "csrc")
@@ -1823,7 +1950,9 @@ def main():
                     help="write the sigma-first tail of the renderer (sigma, colour, rgb and the drain twins; five tiles) instead")
     ap.add_argument("--kbskip", action="store_true",
                     help="write the statements of the K-block-skipping render kernel (csrc/ns_ob16_kbskip_asm.inc) instead")
-    ap.add_argument("--kbs-tested", default=",".join(map(str, KBS_TESTED)), help="with --kbskip: the hidden K-blocks the consumers test")
+    ap.add_argument("--ksuffix", action="store_true",
+                    help="write the statements of the dead-suffix render kernel (csrc/ns_ob16_ksuffix_asm.inc) instead")
+    ap.add_argument("--kbs-tested", default=",".join(map(str, KBS_TESTED)), help="with --kbskip / --ksuffix: the hidden K-blocks the consumers test")
     ap.add_argument("--render-tiles4",action="store_true", help="with --render: the four-tile statements as well")
     ap.add_argument("--dump", help="write the plain instruction stream of one variant (e.g. bf16_AV) here")
     for k in ("no_wait", "no_dma", "no_conv", "no_lds", "no_barrier"):
@@ -1839,6 +1968,9 @@ def main():
         setattr(OPT, k, getattr(a, k))
     if a.kbskip:
         kbs_main(a.o or os.path.join(csrc, "ns_ob16_kbskip_asm.inc"), tuple(int(x) for x in a.kbs_tested.split(",")))
+        return
+    if a.ksuffix:
+        ksx_main(a.o or os.path.join(csrc, "ns_ob16_ksuffix_asm.inc"), tuple(int(x) for x in a.kbs_tested.split(",")))
         return
     if a.render:
         render_main(a.o or os.path.join(csrc, "ns_ob16_render_asm.inc"), (Map4, Map5) if a.render_tiles4 else (Map5,))

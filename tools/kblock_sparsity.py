@@ -6,7 +6,9 @@ consecutive samples and a group 320, as the five-tile kernel forms them.  The un
 (run_nerf_helpers.firing_counts / unit_orders: calibrated on seeded points in a ball, not on the frame); --natural keeps the
 trained order.  Per layer: the share of (wave, K-block) pairs that are all zero, the same for whole groups, the share for the
 K-blocks the kernel tests (tools/gen_ob16_asm.py KBS_TESTED), and the histogram of the number of dead blocks at the END of a
-wave's mask (the order makes dead blocks a suffix).  Last: the chunk steps of a wave pass those blocks stand for.
+wave's mask, 0 .. 8 (the order makes dead blocks a suffix).  Last: the chunk steps of a wave pass those blocks stand for -- any
+dead tested block (the K-block-skipping kernel) next to the trailing dead tested blocks alone, min(suffix, 4) (the dead-suffix
+kernel) -- and, of the waves whose suffix is 4 or longer in some layer, the share whose suffix is 6 or longer in two layers or more.
     python tools/kblock_sparsity.py [--scene shapes_fit] [--pose 17] [--row-step 80] [--natural]"""
 import argparse
 import os
@@ -59,8 +61,9 @@ def main():
                 h = torch.cat([emb, h], -1)
     print(f"{a.scene} pose {a.pose}, every {a.row_step}th row, {S} samples, {dead[0].shape[0]} waves, "
           f"{'trained' if a.natural else 'firing'} order")
-    print("layer | (wave, K-block) dead | whole group dead | tested blocks dead | dead blocks at the end of the mask: 0 1 2 3 4+")
-    steps = 0.0
+    print("layer | (wave, K-block) dead | whole group dead | tested blocks dead | dead blocks at the end of the mask: 0 1 2 3 4 5 6 7 8")
+    steps = steps_suffix = 0.0
+    runs = {}
     for i in range(8):
         dw = dead[i]
         dg = dw.reshape(-1, 4, 8).all(1)
@@ -70,13 +73,21 @@ def main():
         for kb in range(7, -1, -1):
             alive &= dw[:, kb]
             run += alive.long()
-        hist = [float((run == k).float().mean()) for k in range(4)] + [float((run >= 4).float().mean())]
+        hist = [float((run == k).float().mean()) for k in range(9)]
+        runs[i] = run
         print(f"  {i}   | {100 * float(dw.float().mean()):5.1f} % | {100 * float(dg.float().mean()):5.1f} % | "
               f"{100 * float(tested.float().mean()):5.1f} % | " + " ".join(f"{100 * x:5.1f}" for x in hist))
         if i in CONSUMER_CHUNKS:
             steps += CONSUMER_CHUNKS[i] * float(tested.float().sum(1).mean())
+            steps_suffix += CONSUMER_CHUNKS[i] * float(run.clamp(max=len(TESTED)).float().mean())
     print(f"chunk steps a wave pass skips (tested blocks {TESTED}, colour statements of every wave counted): "
           f"{steps:.1f} of {STEPS_PER_PASS} ({100 * steps / STEPS_PER_PASS:.1f} %)")
+    print(f"... of them by the trailing dead tested blocks alone (one choice per statement): {steps_suffix:.1f} "
+          f"({100 * steps_suffix / STEPS_PER_PASS:.1f} % of the pass, {100 * steps_suffix / max(steps, 1e-9):.0f} % of the any-mask figure)")
+    long4 = torch.stack([runs[i] >= 4 for i in CONSUMER_CHUNKS]).any(0)
+    long6 = torch.stack([runs[i] >= 6 for i in CONSUMER_CHUNKS]).long().sum(0) >= 2
+    print(f"waves with a suffix >= 4 in some consumed layer: {100 * float(long4.float().mean()):.1f} %; of them, suffix >= 6 in two or "
+          f"more layers: {100 * float((long6 & long4).float().sum() / max(int(long4.sum()), 1)):.1f} %")
 
 
 if __name__ == "__main__":
