@@ -403,6 +403,63 @@ int ns_mesh_raster(const float* vertices_dev, int64_t V, const int64_t* faces_de
                    float background, float* depth_out, int32_t* tri_out, float* rgb_out, int64_t* count_dev,
                    void* workspace_dev, void* stream);
 
+/* ---- the device mesh simplified by vertex clustering  (what every NeRF mesh export does on the host before it hands the mesh
+ * to a viewer -- the lattice-resolution surface is millions of slivers; not in the reference) ----  Rossignac and Borrel's vertex
+ * clustering on a coarse lattice, with one change: a cluster is represented by ONE OF ITS OWN vertices, the member nearest the
+ * cluster's centroid, not by a new point.  Every vertex that stays is an input vertex bit for bit: its lattice-edge key, its
+ * ns_mesh_normals normal and its colour stay valid, and it still lies on the isosurface.  A result is a function of the inputs
+ * alone.  The arithmetic is csrc/ns_mesh_cluster.h, one text for the kernels and the CPU, every fp64 operation rounded on its own.
+ * INPUTS: vertices_dev fp32 [V,3]; faces_dev int64 [F,3]; lo_host, cell_host: three host floats each; dims_host: three host ints.
+ * CLUSTER LATTICE: lo and cell finite, cell > 0; dims Cx, Cy, Cz each in [1, 2^15], Cx * Cy * Cz <= 2^24 (the table is dense: 40
+ * bytes per cell, 640 MiB at the limit; 128^3 is 80 MiB).
+ * COORDINATE of a vertex per axis, 16 fractional bits: u = llrint((((double) v - (double) lo) / (double) cell) * 65536.0), round
+ * half to even, clamped to [0, C * 65536 - 1] -- a vertex outside the lattice belongs to the nearest boundary cell.  CELL per axis:
+ * u >> 16; linear (cz * Cy + cy) * Cx + cx.  A vertex with a NaN or infinite coordinate belongs to no cluster: rep_out[v] = -1,
+ * and it is counted in count_dev[3].
+ * ACCUMULATE: per cluster S = the three sums of u over its members (int64; u < 2^31 and n < 2^31, so S < 2^62) and n = their
+ * number (int32), by integer atomicAdd.
+ * REPRESENTATIVE: for a member v, d = sum over x, y, z in that order of ((double) u - (double) S / (double) n)^2 in fp64, every
+ * operation rounded on its own, d32 = (float) d.  The representative is the member with the smallest 64-bit word
+ * ((uint64) bits(d32) << 32) | v, merged by a 64-bit unsigned atomic minimum (ns_mesh_raster's z-buffer pattern): d32 >= 0, so
+ * the bits order as the values do -- the member nearest the centroid wins, at equal d32 the smaller index.  rep_out[v] int32,
+ * v in [0, V): the representative of v's cluster, in the input numbering; rep_out[rep_out[v]] == rep_out[v].
+ * FACES: face (a, b, c) is judged in this order: an index outside [0, V) -> INVALID, counted in count_dev[2] (none of its indices
+ * is used as an address); else a corner with rep == -1 -> counted in count_dev[4]; else two of rep[a], rep[b], rep[c] equal ->
+ * COLLAPSED, counted in count_dev[1]; else KEPT: (rep[a], rep[b], rep[c]) is written to faces_out (int64 [capacity,3], input
+ * vertex numbering, winding kept) at its rank among the kept faces in input order.  count_dev[0] = the number of kept faces,
+ * whatever the capacity: those at rank >= capacity are counted and never written (capacity == 0: a pure count).
+ * count_dev[5] = the number of representatives (the occupied clusters).  All six int64 are overwritten, not accumulated.
+ * Nothing is written outside rep_out[0 .. V), faces_out[0 .. 3 min(kept, capacity)), count_dev[0 .. 6) and workspace_dev
+ * (ns_mesh_simplify_workspace_bytes(V, F, Cx, Cy, Cz) bytes; what it holds before the call does not matter).
+ * LAUNCHES, all on `stream`, nothing read back in between, no workgroup waiting for another: (1) the table and two 32-bit
+ * counters cleared; (2) accumulate: workgroup g takes the NS_MESH_SIMPLIFY_SHARE vertices from g * NS_MESH_SIMPLIFY_SHARE on
+ * (thread t takes g * NS_MESH_SIMPLIFY_SHARE + s * 256 + t); (3) choose: every member reads its cluster's finished sums and
+ * offers its word; (4) resolve: rep_out written, the representatives counted; (5) count: workgroup g judges the
+ * NS_MESH_SIMPLIFY_SHARE faces from g * NS_MESH_SIMPLIFY_SHARE on, four int64 per share into the workspace; (6) ONE workgroup
+ * turns the kept counts into output indices and writes count_dev; (7) emit: every workgroup judges its faces again and places the
+ * kept ones by ns_block.h's share_place -- no atomics on the output.  Integer atomics only (atomicAdd on 64- and 32-bit words,
+ * the 64-bit atomicMin); no floating-point atomic anywhere, so nothing depends on the order of the atomics.  V == 0 skips (2) to
+ * (4) (every face is invalid), F == 0 skips (5) and (7).
+ * Checked before any launch (NS_E_INVALID): V or F < 0 or >= 2^31; lo_host, cell_host or dims_host NULL; a non-finite lo or
+ * cell, cell <= 0; a dimension below 1 or above 2^15, a product above 2^24; capacity < 0; count_dev or workspace_dev NULL; with
+ * V > 0 vertices_dev or rep_out NULL; with F > 0 faces_dev NULL, and faces_out NULL unless capacity == 0; faces_dev, faces_out,
+ * count_dev or workspace_dev not 8-byte aligned; vertices_dev or rep_out not 4-byte aligned.
+ * ns_mesh_simplify_workspace_bytes is 0 for a shape that would be refused.
+ * ns_mesh_cluster_coord and ns_mesh_cluster_distance run csrc/ns_mesh_cluster.h on the host for one vertex (no device, no
+ * launch): u_out[3] and *cell_out (the linear cell, -1 for a non-finite vertex) -- returns 1 for a finite vertex, 0 for a
+ * non-finite one, NS_E_INVALID for a lattice the entry would refuse --, and *d_out = d32 of a member with coordinate u_host[3] in
+ * a cluster with sums sums_host[3] and n >= 1 members.  They exist so that the tests compare the library's own text with numpy.
+ * Not part of this: quadric error metrics, new vertex positions at the centroid, manifold or topology guarantees, the removal of
+ * duplicate faces (ops.mesh_simplify does that in torch), and meshes of 2^31 vertices or faces or more.                       */
+#define NS_MESH_SIMPLIFY_SHARE 1024
+int64_t ns_mesh_simplify_workspace_bytes(int64_t V, int64_t F, int Cx, int Cy, int Cz);
+int ns_mesh_simplify(const float* vertices_dev, int64_t V, const int64_t* faces_dev, int64_t F, const float* lo_host,
+                     const float* cell_host, const int* dims_host, int32_t* rep_out, int64_t* faces_out, int64_t capacity,
+                     int64_t* count_dev, void* workspace_dev, void* stream);
+int ns_mesh_cluster_coord(const float* vertex_host, const float* lo_host, const float* cell_host, const int* dims_host,
+                          int32_t* u_out, int32_t* cell_out);
+int ns_mesh_cluster_distance(const int32_t* u_host, const int64_t* sums_host, int32_t n, float* d_out);
+
 /* ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b = (255 * np.clip(x, 0, 1)).astype(np.uint8);
  * nerf_utils.py:322-325 render_path's rgb8 = to8b(rgbs[-1]) written as {i:03d}.png) ----  Quantised on the device, so that a
  * quarter of the frame's bytes cross to the host:

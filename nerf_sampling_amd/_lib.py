@@ -135,6 +135,10 @@ SIGNATURES = {
     "ns_mesh_normals": (_i, [_p, _i64, _i, _i, _i, _f, _f, _f, _f, _p, _i64, _p, _p, _p, _p]),
     "ns_mesh_raster_workspace_bytes": (_i64, [_i64, _i64, _i, _i]),
     "ns_mesh_raster": (_i, [_p, _i64, _p, _i64, _p, _p, _f, _f, _f, _f, _i, _i, _f, _i, _f, _p, _p, _p, _p, _p, _p]),
+    "ns_mesh_simplify_workspace_bytes": (_i64, [_i64, _i64, _i, _i, _i]),
+    "ns_mesh_simplify": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "ns_mesh_cluster_coord": (_i, [_p, _p, _p, _p, _p, _p]),
+    "ns_mesh_cluster_distance": (_i, [_p, _p, C.c_int32, _p]),
     "ns_frame_to8b": (_i, [_p, _i64, _p, _i64, _p, _i, _p]),
     "ns_map_max_workspace_bytes": (_i64, [_i64]),
     "ns_map_max": (_i, [_p, _i64, _i64, _i, _p, _p, _p]),

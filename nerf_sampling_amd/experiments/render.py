@@ -102,6 +102,11 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
               show_default=True,
               help="(not in the reference) --device-mesh queries a vertex's colour looking towards the box centre, or with "
                    "'normal' (it needs --mesh-normals) looking at the surface along its inward normal.")
+@click.option("--mesh-simplify", "mesh_simplify", default=0.0, type=click.FloatRange(min=0.0), show_default=True,
+              help="(not in the reference) --device-mesh simplifies its surface by vertex clustering before it is coloured and "
+                   "written (ns_mesh_simplify, nerf_utils.scene_mesh_simplified): the vertices within a cluster cell this many "
+                   "lattice cells wide collapse onto the one of them nearest their centroid -- about K^2 times fewer "
+                   "triangles, every vertex one of the unsimplified surface's.  0: off.")
 @click.option("--device-mesh-eval", "device_mesh_eval", is_flag=True, default=False,
               help="(not in the reference) --device-mesh also rasterises scene_mesh.ply's mesh from the held-out cameras "
                    "(ns_mesh_raster) and scores it on the device (nerf_utils.score_mesh_views): mesh_psnr.txt against the "
@@ -134,6 +139,8 @@ def main(**kw):
                  mesh_bound=kw["mesh_bound"], mesh_min_triangles=kw["mesh_min_triangles"],
                  mesh_keep_largest=kw["mesh_keep_largest"], mesh_normals=kw["mesh_normals"],
                  mesh_colour_view=kw["mesh_colour_view"])
+        if kw["mesh_simplify"]:
+            k["mesh_simplify"] = kw["mesh_simplify"]
     if kw["device_mesh_eval"]:
         if not kw["device_mesh"]:
             raise click.UsageError("--device-mesh-eval scores the mesh of --device-mesh")

@@ -64,6 +64,9 @@ ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                    "installed) through nerf_utils.write_video -- one render per pose, the disparity's maximum over all frames "
                    "kept on the device (ns_map_max, ns_map_to8b; Trainer(device_video=True)).  Not with --fit-field, which "
                    "renders no spiral.")
+@click.option("--mesh-simplify", "mesh_simplify", default=0.0, type=click.FloatRange(min=0.0), show_default=True,
+              help="Trainer(mesh_simplify=K), not in the reference: where the configuration sets device_mesh, scene_mesh.ply is "
+                   "simplified by vertex clustering on cluster cells K lattice cells wide (ns_mesh_simplify).  0: off.")
 @click.option("--root", default=os.getcwd(), show_default=True, help="Directory holding dataset/ pretrained/ logs/.")
 def main(**kw):
     """Run sampling-network training with the provided configuration (reference flow: run.py:79-155)."""
@@ -89,6 +92,8 @@ def main(**kw):
         k["fused_step"] = True
     if kw["device_batches"]:
         k["device_batches"] = kw["device_batches"]
+    if kw["mesh_simplify"]:
+        k["mesh_simplify"] = kw["mesh_simplify"]
     if kw["device_eval"] or kw["device_ssim"] or kw["device_depth"] or kw["device_frames"] or kw["device_video"]:
         k["device_eval"] = True
     if kw["device_video"]:

@@ -1387,9 +1387,74 @@ def scene_mesh_shaded(network, bound=1.5, resolution=256, threshold=50.0, colour
     "normal" (it needs ``normals``) looks at the surface along its inward normal -n -- on a concave part of an object the
     direction to the box centre is arbitrary --, and along the centre direction exactly where the normal is (0, 0, 0).  With
     ``normals=False`` and "centre" this is scene_mesh_filtered to the launch and to the byte.  Not part of this: normals of
-    meshes that did not come from a lattice (no keys), the field's analytic gradient, normal maps of rendered frames,
-    simplification."""
+    meshes that did not come from a lattice (no keys), the field's analytic gradient, normal maps of rendered frames.
+    Simplification is scene_mesh_simplified's, of which this is the call without it: the same launches, the same dict, the
+    same file."""
+    return scene_mesh_simplified(network, bound=bound, resolution=resolution, threshold=threshold, colours=colours,
+                                 savedir=savedir, capacity=capacity, return_grid=return_grid,
+                                 min_component_triangles=min_component_triangles, keep_largest=keep_largest, normals=normals,
+                                 colour_view=colour_view, simplify=0)
+
+
+SIMPLIFY_COUNTERS = ("n_collapsed", "n_invalid", "n_nonfinite", "n_nonfinite_faces", "n_duplicate", "n_clusters")
+
+
+def simplify_lattice(lo, h, G, simplify):
+    """(lo [3], cell [3], dims [3]) of the cluster lattice whose cells are ``simplify`` density-lattice cells wide: it starts at
+    the density lattice's own ``lo``, cell = (float32)(simplify * h) per axis, and ceil((G - 1) / simplify) cells cover it (a
+    vertex on the far boundary belongs to the last cell: ops.mesh_simplify clamps)."""
+    import math
+
+    import numpy as np
+
+    k = float(simplify)
+    if not (math.isfinite(k) and k > 0.0):
+        raise ValueError(f"simplify must be finite and positive, got {simplify!r}")
+    cell = [float(np.float32(k * float(v))) for v in h]
+    dims = [max(1, int(math.ceil((int(g) - 1) / k))) for g in G]
+    return [float(v) for v in lo], cell, dims
+
+
+def mesh_simplify(mesh, lo, cell, dims, dedupe=True):
+    """Any mesh dict -- scene_mesh_shaded's, or dict(vertices, faces[, rgb][, normals]) from anywhere else -- simplified by
+    vertex clustering on the device (ops.mesh_simplify): the vertices of one cell of the lattice (``lo``, ``cell``, ``dims``)
+    collapse onto the one of them nearest the cell's centroid, so every vertex that stays keeps its bits, and rgb and normals
+    (where the dict has them; a None stays None) are cut as the vertices are.  Returns a copy of the dict with vertices, faces,
+    rgb and normals replaced, and with index (old -> new vertex, -1 where not kept), rep, n_input_vertices, n_input_faces and
+    ops.mesh_simplify's counters.  Not part of this: quadric error metrics, new vertex positions at the centroid, manifold or
+    topology guarantees."""
+    vertices, faces, _ = _mesh_tensors(mesh)
+    names = [k for k in ("rgb", "normals") if k in mesh]
+    got = ops.mesh_simplify(vertices, faces, lo, cell, dims, extras=tuple(mesh[k] for k in names), dedupe=dedupe)
+    out = dict(mesh, vertices=got["vertices"], faces=got["faces"], index=got["index"], rep=got["rep"],
+               n_input_vertices=int(vertices.shape[0]), n_input_faces=int(faces.shape[0]))
+    out.update({k: got["extras"][i] for i, k in enumerate(names)})
+    out.update({k: got[k] for k in SIMPLIFY_COUNTERS})
+    return out
+
+
+def scene_mesh_simplified(network, bound=1.5, resolution=256, threshold=50.0, colours=True, savedir=None, capacity=None,
+                          return_grid=False, min_component_triangles=0, keep_largest=0, normals=True, colour_view="centre",
+                          simplify=0):
+    """scene_mesh_shaded, and the mesh simplified by vertex clustering before it is coloured: the lattice-resolution surface
+    is millions of slivers, which nobody hands to a viewer.  ``simplify`` = k > 0 (a float): ops.mesh_simplify on a cluster
+    lattice of cells k density-lattice cells wide, on the density lattice's own lo (simplify_lattice) -- about k^2 times fewer
+    triangles; every vertex that stays is a vertex of the unsimplified surface, bit for bit, with its normal.  The order is
+    extract, weld, normals, filter, simplify, colour query: a vertex that leaves is never evaluated.  The dict gains
+    n_input_vertices and n_input_faces (what went into the simplification), its counters (n_collapsed, n_invalid, n_nonfinite,
+    n_nonfinite_faces, n_duplicate, n_clusters) and simplify_index (int64: the new index of a vertex that went in, -1 where
+    it left); scene_mesh.ply is the simplified mesh.  0, the default: nothing is launched and nothing changes -- this is
+    scene_mesh_shaded to the launch and to the byte.  Not part of this: quadric error metrics, new vertex positions at the
+    centroid, manifold or topology guarantees."""
     lo3, h3, _G = mesh_lattice(-float(bound), float(bound), resolution)
+    cluster = None
+    import numbers
+
+    if isinstance(simplify, bool) or not isinstance(simplify, numbers.Real) or not float(simplify) >= 0.0:
+        raise ValueError(f"simplify must be a number >= 0, got {simplify!r}")
+    if float(simplify) != 0.0:
+        cluster = simplify_lattice(lo3, h3, _G, simplify)
+        ops._cluster_lattice(*cluster)
     if int(min_component_triangles) < 0 or int(keep_largest) < 0:
         raise ValueError("min_component_triangles and keep_largest must be >= 0")
     if colour_view not in ("centre", "normal"):
@@ -1412,6 +1477,11 @@ def scene_mesh_shaded(network, bound=1.5, resolution=256, threshold=50.0, colour
         if int(min_component_triangles) != 0 or int(keep_largest) != 0:
             kept = _mesh_filter(vertices, faces, (vertex_normals,), min_component_triangles, keep_largest)
             vertices, faces, vertex_normals = kept["vertices"], kept["faces"], kept["extras"][0]
+        simplified = None
+        if cluster is not None:
+            n_input = (int(vertices.shape[0]), int(faces.shape[0]))
+            simplified = ops.mesh_simplify(vertices.contiguous(), faces.contiguous(), *cluster, extras=(vertex_normals,))
+            vertices, faces, vertex_normals = simplified["vertices"], simplified["faces"], simplified["extras"][0]
         rgb = None
         if colours:
             rgb = torch.empty((vertices.shape[0], 3), dtype=torch.float32, device=vertices.device)
@@ -1427,6 +1497,9 @@ def scene_mesh_shaded(network, bound=1.5, resolution=256, threshold=50.0, colour
         out.update(normals=vertex_normals, n_degenerate_normals=n_degenerate)
     if kept is not None:
         out.update({k: kept[k] for k in ("n_components", "n_kept_components", "n_dropped_triangles", "component_triangles")})
+    if simplified is not None:
+        out.update(n_input_vertices=n_input[0], n_input_faces=n_input[1], simplify_index=simplified["index"])
+        out.update({k: simplified[k] for k in SIMPLIFY_COUNTERS})
     if return_grid:
         out["grid"] = grid
     if savedir is not None:

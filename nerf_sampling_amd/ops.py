@@ -609,6 +609,104 @@ def mesh_select(vertices, faces, labels, keep, extras=()):
             "extras": tuple(None if e is None else e[kept_vertex] for e in extras), "index": index}
 
 
+def _cluster_lattice(lo, cell, dims):
+    """(lo [3], cell [3] as float32 values, dims [3]) of ``mesh_simplify``'s cluster lattice, or ValueError: what
+    ns_mesh_simplify refuses (csrc/ns_mesh_cluster.h's lattice_ok)"""
+    try:
+        lo3, cell3 = [float(np.float32(v)) for v in lo], [float(np.float32(v)) for v in cell]
+        dims3 = [int(v) for v in dims]
+        whole = all(float(v) == int(v) for v in dims)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError(f"lo, cell and dims: three numbers each ({e})") from e
+    if len(lo3) != 3 or len(cell3) != 3 or len(dims3) != 3:
+        raise ValueError("lo, cell and dims: three numbers each")
+    if not all(np.isfinite(v) for v in lo3):
+        raise ValueError(f"lo must be finite, got {lo3}")
+    if not all(np.isfinite(v) and v > 0.0 for v in cell3):
+        raise ValueError(f"cell must be finite and positive in float32, got {cell3}")
+    if not (whole and all(1 <= c <= 2 ** 15 for c in dims3) and dims3[0] * dims3[1] * dims3[2] <= 2 ** 24):
+        raise ValueError(f"dims: three whole numbers in [1, 2^15] whose product is at most 2^24, got {list(dims)}")
+    return lo3, cell3, dims3
+
+
+def mesh_simplify_workspace_bytes(n_vertices: int, n_faces: int, dims) -> int:
+    """ns_mesh_simplify_workspace_bytes: the counters, per-share face counts and the dense cluster table (40 bytes per cell)
+    ``mesh_simplify`` needs (0: a shape it refuses)"""
+    Cx, Cy, Cz = (int(v) for v in dims)
+    fits = all(-2 ** 31 <= c < 2 ** 31 for c in (Cx, Cy, Cz))
+    return int(_lib.load().ns_mesh_simplify_workspace_bytes(int(n_vertices), int(n_faces), Cx, Cy, Cz)) if fits else 0
+
+
+def _first_of_each_vertex_set(faces, n_vertices: int):
+    """bool [F]: True where no earlier face has the same three vertices as a set -- plain torch.  The rows sorted, then two
+    rounds of (pair -> dense id): id * n_vertices + vertex stays below 2^62"""
+    F = int(faces.shape[0])
+    if F == 0:
+        return torch.zeros((0,), dtype=torch.bool, device=faces.device)
+    s = torch.sort(faces, dim=1).values
+    pair = torch.unique(s[:, 0] * n_vertices + s[:, 1], return_inverse=True)[1]
+    sets, which = torch.unique(pair * n_vertices + s[:, 2], return_inverse=True)
+    order = torch.arange(F, device=faces.device)
+    first = torch.full((sets.shape[0],), F, dtype=torch.int64, device=faces.device).scatter_reduce_(0, which, order, "amin")
+    return first[which] == order
+
+
+def mesh_simplify(vertices, faces, lo, cell, dims, extras=(), dedupe=True, workspace=None):
+    """ns_mesh_simplify: a mesh simplified by vertex clustering on the device.  The cluster lattice has ``dims`` = (Cx, Cy, Cz)
+    cells of size ``cell`` from ``lo`` on (three numbers each, rounded to float32; a vertex outside belongs to the nearest
+    boundary cell); the vertices of a cell collapse onto ONE OF THEM, the member nearest the cell's centroid (a tie: the smaller
+    index), so every vertex of the result is an input vertex bit for bit and its colour, normal and key stay valid.  A face
+    with two corners in one cell is dropped.  ``vertices``: fp32 contiguous [V,3] on the device; ``faces``: int64 contiguous
+    [F,3] there.  ONE call of the entry with room for F faces and ONE readback of its counters; then the renumbering of
+    ``mesh_select``, in plain torch: the kept vertices are the representatives in ascending input index, the kept faces stay
+    in their order and winding, every tensor of ``extras`` (one row per vertex; a None stays None) is cut as the vertices are.
+    ``dedupe``: a face whose three vertices, as a set, already occurred in an earlier kept face is dropped and counted --
+    collapsing a thin sheet produces such faces in pairs; the first occurrence stays, with its winding.  ``workspace``: a
+    contiguous 8-byte-aligned device tensor of at least ``mesh_simplify_workspace_bytes(V, F, dims)`` bytes (None: allocated);
+    what it holds does not matter.  Returns dict(vertices, faces, extras, index int64 [V]: old -> new vertex, -1 where it is not
+    kept; rep int32 [V]: the representative of every input vertex in the input numbering, -1 for a non-finite one; n_collapsed;
+    n_invalid: faces with an index outside [0, V); n_nonfinite: vertices with a NaN or infinite coordinate; n_nonfinite_faces:
+    faces on one; n_duplicate; n_clusters: the occupied cells, which is the number of vertices kept).  The same bits on every
+    call.  What is wrong with the arguments raises ValueError before any launch.  Not part of this: quadric error metrics, new
+    vertex positions at the centroid, manifold or topology guarantees, meshes of 2^31 vertices or faces or more."""
+    lo3, cell3, dims3 = _cluster_lattice(lo, cell, dims)
+    if not (isinstance(vertices, Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2
+            and vertices.shape[1] == 3 and vertices.is_contiguous()):
+        raise ValueError("vertices: a contiguous float32 device tensor [V,3]")
+    dev = vertices.device
+    if not (isinstance(faces, Tensor) and faces.device == dev and faces.dtype == torch.int64 and faces.dim() == 2
+            and faces.shape[1] == 3 and faces.is_contiguous()):
+        raise ValueError("faces: a contiguous int64 tensor [F,3] on vertices' device")
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if V >= 2 ** 31 or F >= 2 ** 31:
+        raise ValueError(f"V = {V} and F = {F} must be below 2^31")
+    extras = tuple(extras)
+    if not all(e is None or (isinstance(e, Tensor) and e.device == dev and e.dim() >= 1 and e.shape[0] == V) for e in extras):
+        raise ValueError(f"extras: tensors of {V} rows on vertices' device, or None")
+    workspace = _scratch(workspace, mesh_simplify_workspace_bytes(V, F, dims3), dev, "vertices")
+    rep = torch.empty((V,), dtype=torch.int32, device=dev)
+    mapped = torch.empty((F, 3), dtype=torch.int64, device=dev)
+    counters = torch.empty((6,), dtype=torch.int64, device=dev)
+    lo_h, cell_h, dims_h = np.array(lo3, np.float32), np.array(cell3, np.float32), np.array(dims3, np.int32)
+    host = lambda a: a.ctypes.data_as(C.c_void_p)                              # noqa: E731
+    check(_lib.load().ns_mesh_simplify(_ptr(vertices) if V else None, V, _ptr(faces) if F else None, F, host(lo_h), host(cell_h),
+                                       host(dims_h), _ptr(rep) if V else None, _ptr(mapped) if F else None, F, _ptr(counters),
+                                       _ptr(workspace), _stream(dev)), "ns_mesh_simplify")
+    n_kept, n_collapsed, n_invalid, n_nonfinite, n_nonfinite_faces, n_clusters = (int(v) for v in counters.cpu())   # the one readback
+    kept_vertex = rep.long() == torch.arange(V, device=dev)
+    index = torch.where(kept_vertex, torch.cumsum(kept_vertex, 0) - 1, torch.full((V,), -1, dtype=torch.int64, device=dev))
+    new_faces = index[mapped[:n_kept]]
+    n_duplicate = 0
+    if dedupe:
+        first = _first_of_each_vertex_set(new_faces, max(n_clusters, 1))
+        n_duplicate = n_kept - int(first.sum())
+        new_faces = new_faces[first]
+    return {"vertices": vertices[kept_vertex], "faces": new_faces,
+            "extras": tuple(None if e is None else e[kept_vertex] for e in extras), "index": index, "rep": rep,
+            "n_collapsed": n_collapsed, "n_invalid": n_invalid, "n_nonfinite": n_nonfinite,
+            "n_nonfinite_faces": n_nonfinite_faces, "n_duplicate": n_duplicate, "n_clusters": n_clusters}
+
+
 # ---- a rendered frame as 8-bit pixels (run_nerf_helpers.py:11 to8b, quantised on the device) -----------------------------
 def frame_to8b(rgb, alpha=None, out=None, channels: int = 3):
     """ns_frame_to8b: ``run_nerf_helpers.to8b`` of a rendered frame on the device -- (uint8) trunc(255 * clip(x, 0, 1)), one fp32

@@ -49,7 +49,7 @@ class Trainer:
                  device_video: bool = False, device_mesh: bool = False, mesh_resolution: int = 256,
                  mesh_threshold: float = 50.0, mesh_bound: float = 1.5, mesh_min_triangles: int = 0,
                  mesh_keep_largest: int = 0, mesh_normals: bool = False, mesh_colour_view: str = "centre",
-                 device_mesh_eval: bool = False):
+                 device_mesh_eval: bool = False, mesh_simplify: float = 0):
         for k, v in list(locals().items()):
             if k != "self":
                 setattr(self, k, v)
@@ -144,6 +144,13 @@ class Trainer:
         self.device_mesh_eval = bool(device_mesh_eval)
         if self.device_mesh_eval and not self.device_mesh:
             raise ValueError("device_mesh_eval scores the mesh of device_mesh: it needs device_mesh=True")
+        # mesh_simplify (default 0: off, no launch, no changed byte): scene_mesh.ply is the surface simplified by vertex clustering
+        # (nerf_utils.scene_mesh_simplified, ns_mesh_simplify) on cluster cells mesh_simplify lattice cells wide -- about
+        # mesh_simplify^2 times fewer triangles, every vertex one of the unsimplified surface's; device_mesh_eval scores that mesh.
+        if isinstance(mesh_simplify, (bool, np.bool_)) or not isinstance(mesh_simplify, (int, float, np.integer, np.floating)) \
+                or not (float(mesh_simplify) >= 0.0 and np.isfinite(float(mesh_simplify))):
+            raise ValueError(f"mesh_simplify must be a finite number >= 0, got {mesh_simplify!r}")
+        self.mesh_simplify = float(mesh_simplify)
         self.no_reload = False
         self.start = None
         self.K = self.global_step = self.W = self.H = self.c2w = None
@@ -262,18 +269,21 @@ class Trainer:
                       f", {cloud['pts'].shape[0]} written to {testsavedir}")
             if self.device_mesh:
                 fine = render_kwargs_test.get("network_fine")
-                mesh = nerf_utils.scene_mesh_shaded(fine if fine is not None else render_kwargs_test["network_fn"],
-                                                    bound=self.mesh_bound, resolution=self.mesh_resolution,
-                                                    threshold=self.mesh_threshold, savedir=testsavedir,
-                                                    min_component_triangles=self.mesh_min_triangles,
-                                                    keep_largest=self.mesh_keep_largest, normals=self.mesh_normals,
-                                                    colour_view=self.mesh_colour_view)
+                mesh = nerf_utils.scene_mesh_simplified(fine if fine is not None else render_kwargs_test["network_fn"],
+                                                        bound=self.mesh_bound, resolution=self.mesh_resolution,
+                                                        threshold=self.mesh_threshold, savedir=testsavedir,
+                                                        min_component_triangles=self.mesh_min_triangles,
+                                                        keep_largest=self.mesh_keep_largest, normals=self.mesh_normals,
+                                                        colour_view=self.mesh_colour_view, simplify=self.mesh_simplify)
                 filtered = ""
                 if "n_components" in mesh:
                     filtered = (f"; {mesh['n_kept_components']} of {mesh['n_components']} components kept, "
                                 f"{mesh['n_dropped_triangles']} triangles dropped")
                 if "normals" in mesh:
                     filtered += f"; normals, {mesh['n_degenerate_normals']} degenerate"
+                if "n_clusters" in mesh:
+                    filtered += (f"; simplified from {mesh['n_input_faces']} triangles on {mesh['n_input_vertices']} vertices, "
+                                 f"{mesh['n_duplicate']} duplicates dropped")
                 print(f"scene mesh: {mesh['faces'].shape[0]} triangles on {mesh['vertices'].shape[0]} vertices at density "
                       f"{self.mesh_threshold} ({mesh['n_skipped']} cells skipped{filtered}), written to {testsavedir}")
                 if self.device_mesh_eval:
